@@ -38,7 +38,11 @@ all-gather of the pose records (``--gather-to-rank0``: a gather to the main proc
 one write), and rank 0 checks that the gathered block holds every ROI id exactly once.  ``--force-dist`` runs the same path with a
 one-rank process group (what a 1-GPU box can show of it); the line's ``collective`` block is read from the process group itself.
 
-Rank 0 prints ONE JSON line (driver contract) carrying two extra objects:
+A plain run sets up, warms up, times the ``--steps`` steps and prints the line (``--dump-outputs DIR``: the records of the last
+timed step as DIR/records.npy, f32[n, 16], before anything else runs).  Everything else the benchmark measures or checks runs
+only with ``--full``: the objects below, the other GEMM mode and one-stream lines, the stage timings and the collective timing.
+
+Rank 0 prints ONE JSON line (driver contract); with ``--full`` it carries these extra objects:
   roofline      the dominant kernel family, the split GEMMs (MFMA-bound): MFMA flops executed / summed launch durations,
                 every launch bracketed by HIP events on the launch stream in a SEPARATE pass of the same steps right after
                 the timed region (the timed region itself carries no per-launch events); ``traffic`` = HBM-side bytes per launch
@@ -105,6 +109,11 @@ def parse(argv=None):
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=10)
     p.add_argument("--warmup", type=int, default=3)
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also run everything beyond the headline: per-launch roofline pass, live PMC traffic, in-run "
+                        "parity, CPU baseline, stage timings, the other GEMM mode and one-stream lines, the collective alone")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the records of the last timed step (what the timed entry point returns) as DIR/records.npy, float32")
     p.add_argument("--workload", default="auto", choices=["auto"] + sorted(WORKLOADS),
                    help="auto = refine (BASELINE configs[2]) below 8 GPUs, tless (config 4: 1024 ROIs over 8 ranks) at 8")
     p.add_argument("--batch", type=int, default=0, help="ROIs per GPU per step (0 = the workload's batch)")
@@ -365,9 +374,12 @@ def worker(args):
             assert len(ids) == n_global and len(set(ids.tolist())) == n_global, "gathered records: ROI ids not distinct"
         else:
             assert len(ids) == n_global and np.array_equal(np.sort(ids), np.arange(n_global)), "gathered records: ROI ids not a permutation"
+        if args.dump_outputs and rank == 0:                 # the last timed step's records, before any later pass reuses a buffer
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            np.save(os.path.join(args.dump_outputs, "records.npy"), rec.detach().cpu().numpy().astype(np.float32))
 
     gather_ms, collective = None, None
-    if use_dist:                                            # the collective alone, after the timed region
+    if use_dist and args.full:                              # the collective alone, after the timed region
         local = torch.zeros((b, 16), dtype=torch.float32, device=dev)
         local[:, 14] = roi_ids.float()
         for _ in range(3):
@@ -391,9 +403,9 @@ def worker(args):
             dist.destroy_process_group()
         print(json.dumps({"pmc_child": True, "ms_per_step": dt / args.steps * 1e3}), flush=True)
         return
-    if state is not None:
+    if state is not None and args.full:
         extras = state["measure_after"](rank == 0 and world == 1)
-    if state is not None and rank == 0 and world == 1 and not args.no_pmc and not args.graph and extras.get("roofline"):
+    if state is not None and args.full and rank == 0 and world == 1 and not args.no_pmc and not args.graph and extras.get("roofline"):
         live, note = pmc_traffic_live(args, wname, b)
         rl = extras["roofline"]
         if live is not None:
@@ -413,7 +425,7 @@ def worker(args):
             extras["pmc_live_seconds"] = live["seconds"]
         else:
             rl["traffic_live_error"] = note
-    if state is not None and world == 1 and not args.no_other_mode_line and args.mlp_gemm == "split" and not args.graph \
+    if state is not None and args.full and world == 1 and not args.no_other_mode_line and args.mlp_gemm == "split" and not args.graph \
             and not args.no_hip_layers:
         # the same K steps once more with the other split-GEMM setting (reported beside the headline, never as `value`)
         other = 6 if args.gemm_products == 3 else 3
@@ -426,7 +438,7 @@ def worker(args):
                             "note": "MFMA flops of one step / ms_per_step of the timed region; gemm_share_of_step_alone = summed GEMM launch time "
                                     "measured alone / the timed step time (can exceed what a single stream could hold: the rest of the step runs beside them)"}
     n_cs = state["compute_streams"] if state is not None else 1
-    if state is not None and world == 1 and not args.no_other_mode_line and n_cs > 1 and state["single_stream_line"] is not None:
+    if state is not None and args.full and world == 1 and not args.no_other_mode_line and n_cs > 1 and state["single_stream_line"] is not None:
         extras["single_stream_mode"] = state["single_stream_line"](args.steps, n_global, sync, rec)
     if rank == 0:
         metric = ("ROIs/sec (GDRNPP fwd + PnP + depth refine), 256x256 crops" if refine else

@@ -12,6 +12,8 @@ outputs on seeded inputs:
                    makes batches > 1 meaningless)
   ransac_golden.npz  the four kernels of core/csrc/ransac_voting/src/ransac_voting_kernel.cu, extracted verbatim and
                    compiled for the host behind a grid emulator (oracle/ref_shims/ransac_ref_shim.cpp)
+  fps_live_golden.npz  the FPS library on the cases of tests/test_oracle_golden.py's live test, which checks against these
+                   recorded outputs where the library cannot be built (``python tests/golden/make_golden.py fps_live``)
 The fixtures travel to the GPU box; /root/reference does not.
 """
 import ctypes
@@ -60,6 +62,22 @@ def make_flow_case(rng, h, w, motion):
     return np.ascontiguousarray(ds[None, None]), np.ascontiguousarray(dt[None, None]), np.ascontiguousarray(KT), np.ascontiguousarray(Kinv)
 
 
+FPS_LIVE_CASES = [(3000, 32), (17, 17), (257, 300)]
+
+
+def record_fps_live(lib_path):
+    ref = ctypes.CDLL(lib_path)
+    rng = np.random.default_rng(1)
+    out = {}
+    for k, (pn, sn) in enumerate(FPS_LIVE_CASES):
+        pts = rng.standard_normal((pn, 3)).astype(np.float32)
+        idx = np.zeros(sn, np.int32)
+        ref.farthest_point_sampling_init_center(P(pts, f32p), P(idx, i32p), pn, sn)
+        out[f"pts{k}"] = pts
+        out[f"idx{k}"] = idx
+    np.savez_compressed(os.path.join(HERE, "fps_live_golden.npz"), **out)
+
+
 def main():
     libs = oracle.build_ref(force=True)
     assert set(libs) == {"fps", "nnd", "upnp", "flow", "ransac"}, libs
@@ -80,6 +98,7 @@ def main():
         out[f"init_center{k}"] = ic
         out[f"random{k}"] = rd
     np.savez_compressed(os.path.join(HERE, "fps_golden.npz"), **out)
+    record_fps_live(libs["fps"])
 
     # ---- NN distance -----------------------------------------------------------------
     ref = ctypes.CDLL(libs["nnd"])
@@ -184,4 +203,7 @@ def main():
 
 
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] == ["fps_live"]:
+        record_fps_live(oracle.build_ref()["fps"])
+    else:
+        main()

@@ -125,7 +125,7 @@ def test_gpus_flag_spawns_ranks_and_gathers_every_roi_once():
     import subprocess
     import sys
 
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--stub-step",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--stub-step", "--full",
                         "--steps", "3", "--warmup", "1", "--batch", "5"], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -144,7 +144,7 @@ def test_eight_ranks_1024_tless_roi_ids_and_the_collective_block():
     import subprocess
     import sys
 
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--backend", "gloo", "--stub-step",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--backend", "gloo", "--stub-step", "--full",
                         "--steps", "2", "--warmup", "1"], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
@@ -162,7 +162,7 @@ def test_gather_to_rank0_mirrors_the_main_process_only_write():
     import subprocess
     import sys
 
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--stub-step", "--gather-to-rank0",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--stub-step", "--gather-to-rank0", "--full",
                         "--steps", "2", "--warmup", "1", "--batch", "7"], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
@@ -176,7 +176,7 @@ def test_force_dist_runs_the_collective_with_one_rank():
     import subprocess
     import sys
 
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--force-dist", "--backend", "gloo", "--stub-step", "--steps", "2",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--force-dist", "--backend", "gloo", "--stub-step", "--full", "--steps", "2",
                         "--warmup", "1", "--batch", "6"], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
@@ -202,9 +202,34 @@ def test_steps_resolved_two_launches_late_still_gather_every_step_once():
     import subprocess
     import sys
 
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--stub-step", "--compute-streams", "2",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--stub-step", "--compute-streams", "2", "--full",
                         "--steps", "5", "--warmup", "1", "--batch", "6"], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
     assert d["n_gpus"] == 2 and d["steps"] == 5 and d["config"]["global_batch"] == 12 and d["collective"]["calls_per_step"] == 1
     assert abs(d["value"] - 12 * 1000.0 / d["ms_per_step"]) < 1e-6 * d["value"]
+
+
+def test_plain_run_is_lean_and_dumps_the_last_steps_records(tmp_path):
+    """Without --full the line carries the headline only (no collective timing); --dump-outputs writes the records of the last
+    timed step (every ROI id once, float32) — the same file from two runs with the same arguments."""
+    import subprocess
+    import sys
+
+    import numpy as np
+
+    recs = []
+    for run in range(2):
+        out = tmp_path / f"run{run}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--stub-step",
+                            "--steps", "3", "--warmup", "1", "--batch", "5", "--dump-outputs", str(out)],
+                           capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stderr[-2000:]
+        d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
+        assert d["steps"] == 3 and d["ms_per_step"] > 0 and abs(d["value"] - 10 * 1000.0 / d["ms_per_step"]) < 1e-6 * d["value"]
+        assert d["collective"] is None and d["gather_ms"] is None and d["roofline"] is None and d["cpu_baseline"] is None
+        rec = np.load(out / "records.npy")
+        assert rec.dtype == np.float32 and rec.shape == (10, 16)
+        assert np.array_equal(np.sort(rec[:, 14].astype(np.int64)), np.arange(10))
+        recs.append(rec)
+    assert np.array_equal(recs[0], recs[1])

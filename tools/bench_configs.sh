@@ -7,7 +7,7 @@ mkdir -p "$(dirname "$out")"
 for w in lmo_upnp rgb refine tless bop7; do
   extra="--no-cpu-baseline --no-pmc"
   [ "$w" = refine ] && extra=""
-  python bench.py --workload $w --steps 20 --warmup 3 $extra 2>>"$out.err" | grep '^{' >> "$out"
+  python bench.py --full --workload $w --steps 20 --warmup 3 $extra 2>>"$out.err" | grep '^{' >> "$out"
 done
 python - "$out" <<'PY'
 import json, sys

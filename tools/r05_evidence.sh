@@ -12,12 +12,12 @@ export PYTHONUNBUFFERED=1
 ( timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -3 ) >> $O/gpu_tests.txt
 ( for i in $(seq 1 400); do echo "== $(date +%s.%N)"; timeout 5 /opt/rocm/bin/rocm-smi --showclocks --showpower --showuse 2>/dev/null | grep -i "sclk\|mclk\|power\|busy" ; sleep 0.25; done ) > $O/smi_during_bench.txt &
 SMI=$!
-( timeout 600 python bench.py --steps 20 2> $O/bench.err ) > $O/bench_refine_b128.json
+( timeout 600 python bench.py --full --steps 20 2> $O/bench.err ) > $O/bench_refine_b128.json
 kill $SMI 2>/dev/null; wait $SMI 2>/dev/null
-( timeout 300 python bench.py --steps 20 --workload stream --no-cpu-baseline --no-pmc 2> $O/bench_stream.err ) > $O/bench_stream.json
-( timeout 300 python bench.py --steps 20 --workload stream --host-fed --no-cpu-baseline --no-pmc 2> $O/bench_stream_hostfed.err ) > $O/bench_stream_hostfed.json
-( timeout 400 python bench.py --steps 21 --workload bop7_stream --host-fed --no-cpu-baseline --no-pmc 2> $O/bench_bop7_stream_hostfed.err ) > $O/bench_bop7_stream_hostfed.json
-( timeout 300 python bench.py --workload lmo_upnp --steps 30 --warmup 5 --no-pmc 2> $O/bench_lmo_upnp.err ) > $O/bench_lmo_upnp.json
+( timeout 300 python bench.py --full --steps 20 --workload stream --no-cpu-baseline --no-pmc 2> $O/bench_stream.err ) > $O/bench_stream.json
+( timeout 300 python bench.py --full --steps 20 --workload stream --host-fed --no-cpu-baseline --no-pmc 2> $O/bench_stream_hostfed.err ) > $O/bench_stream_hostfed.json
+( timeout 400 python bench.py --full --steps 21 --workload bop7_stream --host-fed --no-cpu-baseline --no-pmc 2> $O/bench_bop7_stream_hostfed.err ) > $O/bench_bop7_stream_hostfed.json
+( timeout 300 python bench.py --full --workload lmo_upnp --steps 30 --warmup 5 --no-pmc 2> $O/bench_lmo_upnp.err ) > $O/bench_lmo_upnp.json
 timeout 900 bash tools/bench_configs.sh $O/bench_configs.jsonl > $O/bench_configs.txt 2>&1
 timeout 900 bash tools/small_batch_lines.sh $O/small_batch.jsonl > $O/small_batch.md 2>&1
 ( timeout 400 python tools/microbench_ops.py 2> $O/ops.err ) > $O/ops_microbench.json

@@ -20,22 +20,22 @@ cp gpurun_out/pk_hazard_probe.json $O/pk_hazard_probe.json 2>/dev/null
 cp gpurun_out/large_parity_tless_b1024.txt gpurun_out/large_parity_ycbv_b512.txt $O/ 2>/dev/null
 ( for i in $(seq 1 400); do echo "== $(date +%s.%N)"; timeout 5 /opt/rocm/bin/rocm-smi --showclocks --showpower --showuse 2>/dev/null | grep -i "sclk\|mclk\|power\|busy" ; sleep 0.25; done ) > $O/smi_during_bench.txt &
 SMI=$!
-( timeout 600 python bench.py --steps 20 --warmup 5 2> $O/bench.err ) > $O/bench_refine_b128.json
+( timeout 600 python bench.py --full --steps 20 --warmup 5 2> $O/bench.err ) > $O/bench_refine_b128.json
 kill $SMI 2>/dev/null; wait $SMI 2>/dev/null
 S="--no-cpu-baseline --no-pmc"
-( timeout 300 python bench.py --steps 20 --workload stream $S 2> $O/bench_stream.err ) > $O/bench_stream.json
-( timeout 300 python bench.py --steps 20 --workload stream --host-fed $S 2> $O/bench_stream_hostfed.err ) > $O/bench_stream_hostfed.json
-( timeout 300 python bench.py --steps 20 --workload stream --host-fed --with-yolox-post $S 2> $O/bench_stream_hostfed_yolox.err ) > $O/bench_stream_hostfed_yolox.json
-( timeout 400 python bench.py --steps 28 --workload bop7_stream --host-fed --with-yolox-post $S 2> $O/bench_bop7_stream_hostfed_yolox.err ) > $O/bench_bop7_stream_hostfed_yolox.json
-( timeout 400 python bench.py --steps 28 --workload bop7_stream --host-fed $S 2> $O/bench_bop7_stream_hostfed.err ) > $O/bench_bop7_stream_hostfed.json
-( timeout 300 python bench.py --workload lmo_upnp --steps 30 --warmup 5 --no-pmc 2> $O/bench_lmo_upnp.err ) > $O/bench_lmo_upnp.json
+( timeout 300 python bench.py --full --steps 20 --workload stream $S 2> $O/bench_stream.err ) > $O/bench_stream.json
+( timeout 300 python bench.py --full --steps 20 --workload stream --host-fed $S 2> $O/bench_stream_hostfed.err ) > $O/bench_stream_hostfed.json
+( timeout 300 python bench.py --full --steps 20 --workload stream --host-fed --with-yolox-post $S 2> $O/bench_stream_hostfed_yolox.err ) > $O/bench_stream_hostfed_yolox.json
+( timeout 400 python bench.py --full --steps 28 --workload bop7_stream --host-fed --with-yolox-post $S 2> $O/bench_bop7_stream_hostfed_yolox.err ) > $O/bench_bop7_stream_hostfed_yolox.json
+( timeout 400 python bench.py --full --steps 28 --workload bop7_stream --host-fed $S 2> $O/bench_bop7_stream_hostfed.err ) > $O/bench_bop7_stream_hostfed.json
+( timeout 300 python bench.py --full --workload lmo_upnp --steps 30 --warmup 5 --no-pmc 2> $O/bench_lmo_upnp.err ) > $O/bench_lmo_upnp.json
 timeout 900 bash tools/bench_configs.sh $O/bench_configs.jsonl > $O/bench_configs.txt 2>&1
 timeout 900 bash tools/small_batch_lines.sh $O/small_batch.jsonl > $O/small_batch.md 2>&1
 # the image stream at the reference's own step sizes: eager scheduler (two streams) against graph-backed steps (four in flight)
 : > $O/stream_small_steps.jsonl
 for b in 8 16 32; do
-  python bench.py --workload stream --batch $b --steps 60 --warmup 4 $S --no-roofline-pass --no-other-mode-line 2>/dev/null | grep '^{' >> $O/stream_small_steps.jsonl
-  python bench.py --workload stream --graph --batch $b --steps 60 --warmup 4 $S --no-roofline-pass --no-other-mode-line 2>/dev/null | grep '^{' >> $O/stream_small_steps.jsonl
+  python bench.py --full --workload stream --batch $b --steps 60 --warmup 4 $S --no-roofline-pass --no-other-mode-line 2>/dev/null | grep '^{' >> $O/stream_small_steps.jsonl
+  python bench.py --full --workload stream --graph --batch $b --steps 60 --warmup 4 $S --no-roofline-pass --no-other-mode-line 2>/dev/null | grep '^{' >> $O/stream_small_steps.jsonl
 done
 ( timeout 400 python tools/microbench_ops.py 2> $O/ops.err ) > $O/ops_microbench.json
 ( timeout 200 python tools/roi_align_variants.py 2>/dev/null ) > $O/roi_align_variants.jsonl
