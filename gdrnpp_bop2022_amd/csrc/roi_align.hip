@@ -51,6 +51,11 @@ __device__ __forceinline__ AxisTap axis_tap(float v, int size) {
 // = 0.17 of HBM against the round-5 kernel's 85 us (0.15).
 // Per output the samples are still added iy-major, ix-minor, each as w1*v1 + w2*v2 + w3*v3 + w4*v4 left to right, then divided by
 // the sample count (multiplied by its reciprocal when that is a power of two: the same bits): bit for bit roi_align_oracle.c.
+//
+// INVARIANT: no lane of a live wave leaves before the wave's y taps are computed and consumed.  Lane L holds tap L of the wave's
+// ROWS x gh taps and the loops fetch them with v_readlane, which ignores EXEC: a tap whose lane has already returned is whatever
+// that register last held, and the rows it names are loaded unconditionally.  So only whole waves return (first column >= PW, or
+// ph0 >= PH); the lanes of a partial wave beyond PW - 1 compute column PW - 1 again and only their STORES are masked off.
 
 
 struct RoiGeom {
@@ -63,7 +68,7 @@ struct RoiGeom {
 // in registers for all rows), 0 = any number (recomputed per sample row).
 template <int GW, int ROWS, bool NT, int CH, bool FULL>
 __device__ __forceinline__ void roi_align_rows(const float* __restrict__ data, float* __restrict__ o, const RoiGeom& g, int nch,
-                                               size_t plane, int H, int W, int PH, int PW, int ph0, int pw) {
+                                               size_t plane, int H, int W, int PH, int PW, int ph0, int pw, bool store) {
   const float x0 = g.sw + pw * g.bin_w;
   // The y taps are uniform per wave, but gfx950's scalar unit has no float arithmetic: computed per sample row they cost every
   // wave ~35 vector instructions (an IEEE division among them) per (row, sample row) — 40 % of the kernel.  So the wave computes
@@ -72,8 +77,9 @@ __device__ __forceinline__ void roi_align_rows(const float* __restrict__ data, f
   const bool lane_taps = ROWS * g.gh <= 64;                            // uniform
   AxisTap tl = AxisTap{false, 0, 0, 0.f, 0.f};
   if (lane_taps) {
-    const int k = lane / g.gh, iy = lane - k * g.gh;
-    tl = axis_tap(g.sh + (ph0 + k) * g.bin_h + (iy + .5f) * g.bin_h / (float)g.gh, H);
+    const int gh1 = max(g.gh, 1);                                      // an inverted box has gh <= 0: no taps are read, none divide by it
+    const int k = lane / gh1, iy = lane - k * gh1;
+    tl = axis_tap(g.sh + (ph0 + k) * g.bin_h + (iy + .5f) * g.bin_h / (float)gh1, H);
   }
   AxisTap txs[GW > 0 ? GW : 1];
   int xbs[GW > 0 ? GW : 1];
@@ -141,7 +147,7 @@ __device__ __forceinline__ void roi_align_rows(const float* __restrict__ data, f
     }
 #pragma unroll
     for (int c = 0; c < CH; ++c)
-      if (FULL || c < nch) {
+      if (store && (FULL || c < nch)) {
         const float v = g.pow2 ? acc[c] * g.rcount : acc[c] / g.count;
         if (NT) __builtin_nontemporal_store(v, o + ((size_t)c * PH + ph) * PW);
         else o[((size_t)c * PH + ph) * PW] = v;
@@ -156,7 +162,7 @@ __global__ __launch_bounds__(256) void roi_align_kernel(const float* __restrict_
   const int row_group = blockIdx.x / col_tiles, col_tile = blockIdx.x - row_group * col_tiles;
   // row lane (uniform per wave: cols % 64 == 0 — readfirstlane tells the compiler, so the y taps stay on the scalar unit), column
   const int ry = __builtin_amdgcn_readfirstlane((int)threadIdx.x / cols), cx = (int)threadIdx.x - ry * cols;
-  const int pw = col_tile * cols + cx;
+  const int pw_lane = col_tile * cols + cx;
   const int ph0 = (row_group * (256 / cols) + ry) * ROWS;
   const int c0 = blockIdx.y * CH, n = blockIdx.z;
   const float* r = rois + 5 * (size_t)n;
@@ -176,18 +182,21 @@ __global__ __launch_bounds__(256) void roi_align_kernel(const float* __restrict_
   const int icount = g.gh * g.gw;
   g.pow2 = icount >= 1 && (icount & (icount - 1)) == 0;     // x / 2^k == x * 2^-k exactly, also into the subnormals
   g.rcount = 1.f / g.count;
-  if (pw >= PW || ph0 >= PH) return;
+  // whole waves only (a wave = 64 consecutive columns of one row lane, so its first lane has its first column): see INVARIANT
+  if (__builtin_amdgcn_readfirstlane(pw_lane) >= PW || ph0 >= PH) return;
+  const bool store = pw_lane < PW;
+  const int pw = min(pw_lane, PW - 1);                      // column used for sampling and addressing
   const size_t plane = (size_t)H * W;
   const float* data = x + ((size_t)bi * C + c0) * plane;
   const int nch = FULL ? CH : min(CH, C - c0);              // uniform
   float* o = out + (((size_t)n * C + c0) * PH) * PW + pw;
   // the adaptive sampling grid (sampling_ratio = 0, the reference's setting) is per ROI, i.e. uniform in the workgroup
   switch (g.gw) {
-    case 1: roi_align_rows<1, ROWS, NT, CH, FULL>(data, o, g, nch, plane, H, W, PH, PW, ph0, pw); break;
-    case 2: roi_align_rows<2, ROWS, NT, CH, FULL>(data, o, g, nch, plane, H, W, PH, PW, ph0, pw); break;
-    case 3: roi_align_rows<3, ROWS, NT, CH, FULL>(data, o, g, nch, plane, H, W, PH, PW, ph0, pw); break;
-    case 4: roi_align_rows<4, ROWS, NT, CH, FULL>(data, o, g, nch, plane, H, W, PH, PW, ph0, pw); break;
-    default: roi_align_rows<0, ROWS, NT, CH, FULL>(data, o, g, nch, plane, H, W, PH, PW, ph0, pw);
+    case 1: roi_align_rows<1, ROWS, NT, CH, FULL>(data, o, g, nch, plane, H, W, PH, PW, ph0, pw, store); break;
+    case 2: roi_align_rows<2, ROWS, NT, CH, FULL>(data, o, g, nch, plane, H, W, PH, PW, ph0, pw, store); break;
+    case 3: roi_align_rows<3, ROWS, NT, CH, FULL>(data, o, g, nch, plane, H, W, PH, PW, ph0, pw, store); break;
+    case 4: roi_align_rows<4, ROWS, NT, CH, FULL>(data, o, g, nch, plane, H, W, PH, PW, ph0, pw, store); break;
+    default: roi_align_rows<0, ROWS, NT, CH, FULL>(data, o, g, nch, plane, H, W, PH, PW, ph0, pw, store);
   }
 }
 

@@ -95,38 +95,87 @@ def test_warp_float_bilinear_and_nearest_against_grid_sample():
     assert clear.mean() > 0.99
 
 
-def _roi_align_independent(x, rois, out, sampling_ratio=0):
-    """ROIAlign (aligned=True) written from its definition with torch ops: every bin is the mean of a regular grid of
-    bilinear samples; sample (y, x) outside [-1, H] x [-1, W] contributes 0, coordinates are clamped to the image."""
+EPS32 = float(np.finfo(np.float32).eps)
+# Rounding steps (each <= eps32 / 2 relative to a magnitude <= 2 M, M = the largest |coordinate| the box reaches) on the way to
+# one fp32 sample coordinate  start + p * bin + (i + .5) * bin / g  of oracle/roi_align_oracle.c:
+#   start = r * scale - offset                      2        (end likewise 2; their difference +1 on a value <= 2 M: 6 in all)
+#   bin = size / P                                  6 + 1    (relative to M / P)
+#   p * bin                                         7 + 1
+#   (i + .5) * bin / g                              7 + 1 + 1
+#   the two additions                               2 + 2
+# = 2 + 8 + 9 + 4 = 23 half-eps steps -> |coordinate error| <= 12 eps32 M per axis.  A bilinear surface is continuous and piecewise
+# linear along each axis with slope <= D = max |neighbour difference|, so the two axes move a sample by <= 2 * 12 eps32 M D, and
+# the mean over the bin's samples by no more.
+K_COORD = 24
+# Value arithmetic per sample: hy = 1 - ly (1 step), w = hy * hx (1), w * v (1), three additions (3), the accumulation's own
+# addition (counted below): <= 7 half-eps steps on sum(w |v|) <= max |x|  ->  3.5 eps32; adding n = gh * gw samples left to right
+# rounds n partial sums of magnitude <= n max |x|, divided by n at the end (+1): (n + 1) / 2 eps32.
+def _k_value(n):
+    return 3.5 + (n + 1) / 2.0
+
+
+def _roi_align_independent(x, rois, out, sampling_ratio=0, aligned=True, spatial_scale=1.0):
+    """ROIAlign written from its definition in fp64, separably: every bin is the mean of a regular gh x gw grid of bilinear
+    samples; a sample row (column) outside [-1, H] ([-1, W]) contributes 0, coordinates are clamped to the image; rows are
+    interpolated first, then columns — all sample rows and columns of a box at once.  ``rois`` are taken as the fp32 values
+    the forward is given.  -> (f64[n, C, oh, ow], M = largest |coordinate| reached, near = bool[n, oh, ow]: a sample of that
+    bin lies within the fp32 coordinate error of the validity window's edge, where the two may legitimately disagree)."""
+    oh, ow = (out, out) if isinstance(out, int) else out
     b, c, h, w = x.shape
-    res = []
-    xt = torch.from_numpy(x).double()
+    xd = x.astype(np.float64)
+    off = 0.5 if aligned else 0.0
+    res, near, M = [], [], 0.0
+
+    def axis(start, size, p, g, n):
+        """sample coordinates [p * g] of one axis -> validity, low / high index, weight of high"""
+        bin_ = size / p
+        v = start + (np.arange(p)[:, None] + (np.arange(g)[None, :] + 0.5) / g) * bin_ if g > 0 else np.zeros((p, 0))
+        v = v.reshape(-1)
+        valid = (v >= -1) & (v <= n)
+        vc = np.clip(v, 0, n - 1)
+        lo = np.minimum(np.floor(vc).astype(int), n - 1)
+        hi = np.minimum(lo + 1, n - 1)
+        return v, valid, lo, hi, vc - lo
+
     for r in rois:
         bi = int(r[0])
-        x1, y1, x2, y2 = [float(v) - 0.5 for v in r[1:]]
-        bw, bh = (x2 - x1) / out, (y2 - y1) / out
-        gh = sampling_ratio if sampling_ratio > 0 else int(np.ceil((y2 - y1) / out))
-        gw = sampling_ratio if sampling_ratio > 0 else int(np.ceil((x2 - x1) / out))
-        acc = torch.zeros(c, out, out, dtype=torch.float64)
-        for iy in range(gh):
-            ys = y1 + (torch.arange(out, dtype=torch.float64) + (iy + 0.5) / gh) * bh
-            for ix in range(gw):
-                xs = x1 + (torch.arange(out, dtype=torch.float64) + (ix + 0.5) / gw) * bw
-                valid = ((ys >= -1) & (ys <= h))[:, None] & ((xs >= -1) & (xs <= w))[None, :]
-                yc, xc = ys.clamp(0, h - 1), xs.clamp(0, w - 1)
-                y0, x0 = yc.floor().long().clamp(max=h - 1), xc.floor().long().clamp(max=w - 1)
-                y1i, x1i = (y0 + 1).clamp(max=h - 1), (x0 + 1).clamp(max=w - 1)
-                ly, lx = (yc - y0)[:, None], (xc - x0)[None, :]
-                img = xt[bi]
-                v = (img[:, y0][:, :, x0] * (1 - ly) * (1 - lx) + img[:, y0][:, :, x1i] * (1 - ly) * lx
-                     + img[:, y1i][:, :, x0] * ly * (1 - lx) + img[:, y1i][:, :, x1i] * ly * lx)
-                acc += v * valid
-        res.append(acc / (gh * gw))
-    return torch.stack(res).numpy()
+        x1, y1, x2, y2 = [float(v) * spatial_scale - off for v in r[1:]]
+        rw, rh = x2 - x1, y2 - y1
+        if not aligned:
+            rw, rh = max(rw, 1.0), max(rh, 1.0)
+        gh = sampling_ratio if sampling_ratio > 0 else int(np.ceil(rh / oh))
+        gw = sampling_ratio if sampling_ratio > 0 else int(np.ceil(rw / ow))
+        if gh <= 0 or gw <= 0:                                 # no samples: the mean over max(gh * gw, 1) of nothing
+            res.append(np.zeros((c, oh, ow)))
+            near.append(np.zeros((oh, ow), bool))
+            continue
+        m = max(abs(x1), abs(x2), abs(y1), abs(y2), abs(x1 + rw), abs(y1 + rh), rw, rh, 1.0)
+        M = max(M, m)
+        ys, vy, ylo, yhi, ly = axis(y1, rh, oh, gh, h)
+        xs, vx, xlo, xhi, lx = axis(x1, rw, ow, gw, w)
+        img = xd[bi]
+        rows = (img[:, ylo, :] * (1 - ly)[None, :, None] + img[:, yhi, :] * ly[None, :, None]) * vy[None, :, None]
+        smp = (rows[:, :, xlo] * (1 - lx)[None, None, :] + rows[:, :, xhi] * lx[None, None, :]) * vx[None, None, :]
+        res.append(smp.reshape(c, oh, gh, ow, gw).sum((2, 4)) / (gh * gw))
+        d = K_COORD / 2 * EPS32 * m
+        ny = ((np.abs(ys + 1) <= d) | (np.abs(ys - h) <= d)).reshape(oh, gh).any(1)
+        nx = ((np.abs(xs + 1) <= d) | (np.abs(xs - w) <= d)).reshape(ow, gw).any(1)
+        near.append(ny[:, None] | nx[None, :])
+    return np.stack(res), M, np.stack(near)
+
+
+def _neighbour_difference(x):
+    d = [np.abs(np.diff(x.astype(np.float64), axis=a)).max() for a in (2, 3) if x.shape[a] > 1]
+    return max(d) if d else 0.0
+
+
+def _roi_align_bound(x, M, n_samples):
+    """k eps32 max|coordinate| max|neighbour difference| + k' eps32 max|x| (derivation above K_COORD / _k_value)."""
+    return K_COORD * EPS32 * M * _neighbour_difference(x) + _k_value(n_samples) * EPS32 * float(np.abs(x).max())
 
 
 def test_roi_align_oracle_against_independent_formulation():
-    """oracle/roi_align_oracle.c (detectron2 ROIAlign restated) against the definition written with torch tensor ops, on
+    """oracle/roi_align_oracle.c (detectron2 ROIAlign restated) against the definition written with array ops in fp64, on
     boxes inside, across and beyond the image border, adaptive and fixed sampling ratios."""
     rng = np.random.default_rng(5)
     x = rng.normal(size=(2, 3, 37, 45)).astype(np.float32)
@@ -134,8 +183,78 @@ def test_roi_align_oracle_against_independent_formulation():
                      [1, 30.0, 20.0, 60.0, 50.0], [0, 0.0, 0.0, 45.0, 37.0], [1, 7.25, 3.5, 9.0, 5.0]], np.float32)
     for sr in (0, 2):
         got = P.roi_align(x, rois, 8, 1.0, sr, True)
-        want = _roi_align_independent(x, rois, 8, sr)
+        want, _, near = _roi_align_independent(x, rois, 8, sr)
+        assert not near.any()
         np.testing.assert_allclose(got, want, rtol=0, atol=2e-5)
+
+
+def test_roi_case_list_covers_every_launch_axis():
+    """tests/roi_cases.py: every value of every axis the launcher and kernel branch on appears, each partial-wave pooled_w with
+    a gh below (where one exists) and at its threshold 4 * gh > active lanes, and the boxes give the gh / gw the case names."""
+    from tests import roi_cases as RC
+
+    cs = RC.ALIGN_CASES
+    assert len({c.id for c in cs}) == len(cs)
+    assert {c.pw for c in cs} >= {1, 7, 16, 63, 64, 65, 100, 128, 130, 200, 256}
+    assert {c.ph for c in cs} >= {1, 5, 16, 33}
+    assert {c.gh for c in cs} >= {1, 2, 3, 5, 9, 10, 16, 17, 20} and {c.gw for c in cs} >= {1, 2, 3, 4, 5, 9}
+    assert {c.c for c in cs} >= {1, 2, 3, 4, 5, 8} and {c.w for c in cs} >= {1, 2, 3, 80} and {c.h for c in cs} >= {1, 2, 60}
+    assert {c.aligned for c in cs} == {True, False} and {c.sampling_ratio for c in cs} >= {0, 2, 3}
+    assert {c.scale for c in cs} >= {1.0, 0.25}
+    pairs = {(c.pw, c.gh) for c in cs if c.w > 1 and c.sampling_ratio == 0}
+    assert pairs >= {(7, 1), (7, 2), (16, 3), (16, 5), (100, 9), (100, 10), (130, 1), (200, 2), (200, 3)}
+    assert pairs >= {(7, 5), (16, 9), (16, 16), (100, 16), (130, 3), (200, 9), (16, 17), (16, 20)}
+    n = [c.gh * c.gw for c in cs]
+    assert any(v & (v - 1) == 0 for v in n) and any(v & (v - 1) for v in n)              # reciprocal multiply and division
+    # a thread's 4 rows end inside pooled_h: 4 * (256 / cols) rows per workgroup, pooled_h not a multiple of 4
+    assert {(c.ph % 4 != 0, 64 if c.pw <= 64 else 128 if c.pw <= 128 else 256) for c in cs} >= {(True, 64), (True, 128), (True, 256)}
+    for c in cs + RC.CONTAINMENT_CASES:
+        gh, gw = RC.align_grid(c, RC.align_rois(c))
+        assert (gh == c.gh).all() and (gw == c.gw).all(), c.id
+    assert all(c in cs for c in RC.CONTAINMENT_CASES) and {c.pw for c in RC.CONTAINMENT_CASES} == {7, 100, 130}
+
+
+def test_roi_align_oracle_against_fp64_over_the_gpu_case_list(capsys):
+    """The cases tests/test_gpu_roi_shapes.py holds the kernel to (bit for bit against the oracle), here the oracle against the
+    fp64 formulation: outputs (oh, ow) from 1 x 1 to 33 x 256, aligned or not, spatial_scale, fixed and adaptive grids up to
+    20 x 3 samples, sources down to 1 x 1.  Bound per case = 24 eps32 max|coordinate| max|neighbour difference|
+    + (3.5 + (gh gw + 1) / 2) eps32 max|x|, from the operation count of the fp32 restatement (see K_COORD), not from the observed
+    error.  Bins with a sample within the coordinate error of the validity window's edge are left out (fp32 and fp64 may
+    disagree there by a whole sample); there are none in this list.  Largest observed / bound over the list: 0.018
+    (observed errors up to 9.8e-5 where coordinates reach 400; printed per case with -s)."""
+    from tests import roi_cases as RC
+
+    worst = 0.0
+    lines = []
+    for case in RC.ALIGN_CASES + [RC.DEGENERATE_CASE]:
+        x = RC.align_input(case)
+        rois = RC.DEGENERATE_ROIS if case is RC.DEGENERATE_CASE else RC.align_rois(case)
+        got = P.roi_align(x, rois, (case.ph, case.pw), case.scale, case.sampling_ratio, case.aligned)
+        want, M, near = _roi_align_independent(x, rois, (case.ph, case.pw), case.sampling_ratio, case.aligned, case.scale)
+        assert not near.any(), case.id
+        err = float((np.abs(got - want) * ~near[:, None]).max())
+        bound = _roi_align_bound(x, M, max(case.gh * case.gw, 1))
+        lines.append(f"{case.id}: observed {err:.3g} bound {bound:.3g} ratio {err / bound:.3g}")
+        assert err <= bound, lines[-1]
+        worst = max(worst, err / bound)
+    with capsys.disabled():
+        print("\n" + "\n".join(lines) + f"\nroi_align oracle vs fp64: largest observed / bound = {worst:.3g}")
+    assert worst > 1e-4                                      # the bound is not vacuous: rounding error is seen
+
+
+def test_roi_align_oracle_linear_ramp_closed_form():
+    """On x[c, y, x] = a x + b y + d bilinear interpolation is exact, so with every sample inside [0, W - 1] x [0, H - 1] each
+    output is the ramp at its bin centre.  a, b, d, the box corners and the bin sizes are small dyadic rationals and gh * gw is a
+    power of two, so every fp32 operation is exact: the oracle meets EQUALITY (the GPU suite asks the same of the kernel)."""
+    from tests import roi_cases as RC
+
+    x = RC.ramp_input()
+    for case in RC.RAMP_CASES:
+        rois, want = RC.ramp_rois_and_expected(case)
+        got = P.roi_align(x, rois, (case.ph, case.pw), case.scale)
+        assert np.array_equal(got.astype(np.float64), want), case.id
+        ind, _, _ = _roi_align_independent(x, rois, (case.ph, case.pw), 0, True, case.scale)
+        assert np.array_equal(ind, want), case.id
 
 
 def _preds(boxes, scores, classes, num_classes):
@@ -178,6 +297,36 @@ def test_nms_oracle_closed_form_cases():
     assert P.yolox_postprocess(_preds([[0, 0, 10, 10]], [0.5], [0], 1), 1, 0.7, 0.45)[0] is None
 
 
+def _roi_pool_independent(x, rois, size, spatial_scale=1.0):
+    """RoIPool from its published definition in NumPy: corners rounded half away from zero, width / height = max(end - start
+    + 1, 1), bin [floor(p * bin), ceil((p + 1) * bin)) in fp32, shifted by the start and clipped to the image; max, 0 if empty."""
+    import math
+
+    oh, ow = size
+    c, h, w = x.shape[1:]
+    f = np.float32
+
+    def rnd(v):                                    # std::round: half away from zero
+        v = float(f(v) * f(spatial_scale))
+        return int(math.floor(abs(v) + 0.5) * (1 if v >= 0 else -1))
+
+    out = np.zeros((len(rois), c, oh, ow), np.float32)
+    for n, r in enumerate(rois):
+        sw, sh, ew, eh = rnd(r[1]), rnd(r[2]), rnd(r[3]), rnd(r[4])
+        rw, rh = max(ew - sw + 1, 1), max(eh - sh + 1, 1)
+        bh, bw = f(rh) / f(oh), f(rw) / f(ow)
+        img = x[int(r[0])]
+        for ph in range(oh):
+            h0 = min(max(int(np.floor(f(ph) * bh)) + sh, 0), h)
+            h1 = min(max(int(np.ceil(f(ph + 1) * bh)) + sh, 0), h)
+            for pw in range(ow):
+                w0 = min(max(int(np.floor(f(pw) * bw)) + sw, 0), w)
+                w1 = min(max(int(np.ceil(f(pw + 1) * bw)) + sw, 0), w)
+                if h1 > h0 and w1 > w0:
+                    out[n, :, ph, pw] = img[:, h0:h1, w0:w1].reshape(c, -1).max(1)
+    return out
+
+
 def test_roi_pool_oracle_against_an_independent_formulation_and_closed_forms():
     """RoIPool (batch_crop_resize(interpolation="nearest"), core/utils/zoom_utils.py:92-93): torchvision is absent, so the
     restatement (oracle/roi_align_oracle.c, parity unpinned) is held against an independent NumPy formulation of the published
@@ -194,26 +343,27 @@ def test_roi_pool_oracle_against_an_independent_formulation_and_closed_forms():
                      [0, 5, 5, 5, 5], [1, 10.5, 2.5, 3.5, 1.5]], np.float32)
     out = P.roi_pool(x, rois, (4, 5))
 
-    def rnd(v):                                    # std::round: half away from zero
-        return int(math.floor(abs(float(v)) + 0.5) * (1 if v >= 0 else -1))
-
-    for n, r in enumerate(rois):
-        sw, sh, ew, eh = rnd(r[1]), rnd(r[2]), rnd(r[3]), rnd(r[4])
-        rw, rh = max(ew - sw + 1, 1), max(eh - sh + 1, 1)
-        bh, bw = np.float32(rh) / np.float32(4), np.float32(rw) / np.float32(5)
-        for ph in range(4):
-            for pw in range(5):
-                h0 = min(max(int(np.floor(np.float32(ph) * bh)) + sh, 0), 17)
-                h1 = min(max(int(np.ceil(np.float32(ph + 1) * bh)) + sh, 0), 17)
-                w0 = min(max(int(np.floor(np.float32(pw) * bw)) + sw, 0), 23)
-                w1 = min(max(int(np.ceil(np.float32(pw + 1) * bw)) + sw, 0), 23)
-                want = x[int(r[0]), :, h0:h1, w0:w1].reshape(3, -1).max(1) if (h1 > h0 and w1 > w0) else np.zeros(3, np.float32)
-                assert np.array_equal(out[n, :, ph, pw], want), (n, ph, pw)
+    assert np.array_equal(out, _roi_pool_independent(x, rois, (4, 5)))
     assert not out[2].any()                                                        # box outside the image
     px = P.roi_pool(x, np.array([[0, 4, 6, 8, 9]], np.float32), (4, 5))            # 5 x 4 pixels, one per bin
     assert np.array_equal(px[0], x[0, :, 6:10, 4:9])
     whole = P.roi_pool(x[:, :, :16, :20], np.array([[1, 0, 0, 19, 15]], np.float32), (4, 5))
     assert np.array_equal(whole[0], F.max_pool2d(torch.from_numpy(x[1:2, :, :16, :20]), 4)[0].numpy())
+
+
+def test_roi_pool_oracle_against_the_independent_formulation_over_the_gpu_shapes():
+    """The outputs, sources and boxes of tests/test_gpu_roi_shapes.py (1 x 1 .. 33 x 65 outputs, C = 1 / 4 / 5, sources one pixel
+    wide or high, boxes across every border, .5 corners of both signs, spatial_scale 0.25): oracle == NumPy formulation."""
+    from tests import roi_cases as RC
+
+    for k, (c, h, w) in enumerate(RC.POOL_SOURCES):
+        x = RC.pool_input(c, h, w)
+        for j, size in enumerate(RC.POOL_OUTPUTS):
+            for scale in (1.0, 0.25) if (k + j) % 2 == 0 else (1.0,):
+                rois = RC.pool_rois(h, w, scale)
+                got = P.roi_pool(x, rois, size, scale)
+                assert np.array_equal(got, _roi_pool_independent(x, rois, size, scale)), (c, h, w, size, scale)
+                assert got[5].any() and not got[6].any() and not got[7].any()
 
 
 def test_nms_oracle_equals_the_reference_postprocess_executed_from_source(golden_dir):
