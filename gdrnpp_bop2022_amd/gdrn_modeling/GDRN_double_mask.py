@@ -321,7 +321,12 @@ def build_model_optimizer(cfg, is_test=True, model_cls=None):
                "allo_lie_vec": 3, "ego_lie_vec": 3}[p.ROT_TYPE]
     pnp_cfg = copy.deepcopy(dict(p.INIT_CFG))
     pnp_type = pnp_cfg.pop("type")
-    pnp_cfg.update(nIn=n_in, rot_dim=rot_dim, num_regions=g.NUM_REGIONS, mask_attention_type=p.MASK_ATTENTION)
+    if pnp_type == "ConvPnPNet":
+        pnp_cfg.update(nIn=n_in, rot_dim=rot_dim, num_regions=g.NUM_REGIONS, mask_attention_type=p.MASK_ATTENTION)
+    elif pnp_type == "SimplePointPnPNet":      # model_utils.py:250-256: no num_regions
+        pnp_cfg.update(nIn=n_in, rot_dim=rot_dim, mask_attention_type=p.MASK_ATTENTION)
+    else:
+        raise ValueError(f"Unknown pnp head type: {pnp_type}")
     pnp_net = HEADS[pnp_type](**pnp_cfg)
 
     model = (model_cls or GDRN_DoubleMask)(cfg, backbone, neck=None, geo_head_net=geo_head, pnp_net=pnp_net)

@@ -3,6 +3,7 @@
 * ``TopDownDoubleMaskXyzRegionHead`` / ``TopDownMaskXyzRegionHead``
   (models/heads/top_down_doublemask_xyz_region_head.py:9-211, top_down_mask_xyz_region_head.py)
 * ``ConvPnPNet`` (models/heads/conv_pnp_net.py:10-183)
+* ``SimplePointPnPNet`` (models/heads/point_pnp_net.py:208-293)
 * ``ConvModule`` (lib/torch_utils/layers/conv_module.py:103-236): sub-modules ``conv``, ``gn``, ``activate``.
 
 Parameter names equal the reference's so that ``geo_head_net.*`` / ``pnp_net.*`` checkpoint keys load
@@ -316,8 +317,70 @@ class ConvPnPNet(nn.Module):
         return self._fc_tail(x, pose)
 
 
+class SimplePointPnPNet(nn.Module):
+    """Point-wise PnP head: 3 x Conv1d(k=1) (nIn -> 128 -> 128 -> 1024, LeakyReLU(0.1) between) over the H*W points -> max over
+    the points -> fc1 -> fc2 -> fc_pose = [rot | t].  PyTorch's default initialisers, like the reference (no normal_init)."""
+
+    def __init__(self, nIn, rot_dim=6, use_softpool=False, softpool_topk=32, mask_attention_type="none"):
+        super().__init__()
+        if use_softpool:
+            raise NotImplementedError("SimplePointPnPNet: use_softpool=True is not carried by this build (max pooling only)")
+        self.mask_attention_type = mask_attention_type
+        self.use_softpool = use_softpool
+        self.softpool_topk = softpool_topk
+        self.conv1 = nn.Conv1d(nIn, 128, 1)
+        self.conv2 = nn.Conv1d(128, 128, 1)
+        self.conv3 = nn.Conv1d(128, 1024, 1)
+        self.fc1 = nn.Linear(1024, 512)
+        self.fc2 = nn.Linear(512, 256)
+        self.fc_pose = nn.Linear(256, rot_dim + 3)
+        self.act = nn.LeakyReLU(0.1, inplace=True)
+        self.rot_dim = rot_dim
+
+    def forward(self, coor_feat, region=None, extents=None, mask_attention=None, pose=None):
+        bs, in_c, fh, fw = coor_feat.shape
+        hip_layers.foreign("SimplePointPnPNet.forward: the head as PyTorch operators (module path)", coor_feat)
+        if in_c in (3, 5):
+            coor_feat[:, :3] = (coor_feat[:, :3] - 0.5) * extents.view(bs, 3, 1, 1)  # in place, like :250
+        x = torch.cat([coor_feat, region], dim=1) if region is not None else coor_feat
+        if self.mask_attention_type != "none":
+            assert mask_attention is not None
+            if self.mask_attention_type == "mul":
+                x = x * mask_attention
+            elif self.mask_attention_type == "concat":
+                x = torch.cat([x, mask_attention], dim=1)
+            else:
+                raise ValueError(f"Wrong mask attention type: {self.mask_attention_type}")
+        return self.mlp_tail(x.reshape(bs, x.shape[1], -1))
+
+    def mlp_tail(self, x):
+        """x [B, nIn, N] -> (rot [B, rot_dim], t [B, 3]) with PyTorch operators."""
+        x = self.act(self.conv1(x))
+        x = self.act(self.conv2(x))
+        x = self.conv3(x)                      # [B, 1024, N]
+        x = torch.max(x, dim=2)[0]
+        x = self.act(self.fc1(x))
+        x = self.act(self.fc2(x))
+        pose = self.fc_pose(x)
+        return pose[:, :self.rot_dim], pose[:, self.rot_dim:self.rot_dim + 3]
+
+    # ---- NHWC entry used by the fused head tail (hip_lib.head_tail_nhwc) ------------------------------------------------
+    def accepts_prepared_input(self) -> bool:
+        """The prepared [xyz * extent | coord2d | region softmax | zero pad] NHWC input has this head's own channel order: taken
+        for the plain configuration (69 input channels, no mask attention, max pooling)."""
+        return self.conv1.in_channels == 69 and self.mask_attention_type == "none" and not self.use_softpool
+
+    def forward_prepared(self, x96_cl, pose=None):
+        """``x96_cl``: [B, 96, H, W] channels_last, channels 69..95 unused.  The whole head in three HIP launches
+        (hip_layers.point_pnp); the last one also produces the pose."""
+        bs, c, h, w = x96_cl.shape
+        x2d = x96_cl.permute(0, 2, 3, 1).reshape(bs * h * w, c)      # a view of the NHWC memory
+        return hip_layers.point_pnp(self, x2d, bs, h * w, pose)
+
+
 HEADS = {
     "TopDownMaskXyzRegionHead": TopDownMaskXyzRegionHead,
     "TopDownDoubleMaskXyzRegionHead": TopDownDoubleMaskXyzRegionHead,
     "ConvPnPNet": ConvPnPNet,
+    "SimplePointPnPNet": SimplePointPnPNet,
 }

@@ -648,3 +648,30 @@ def pnp_fc_heads(fc_r: nn.Linear, fc_t: nn.Linear, x: torch.Tensor, pose: dict |
         return hip_lib.pnp_fc_heads(x, w_r, fc_r.bias, w_t, fc_t.bias)
     _fallback("pnp_fc_heads: pose heads outside the one-launch kernel (hipBLASLt)", x)
     return fc_r(x), fc_t(x)
+
+
+def point_pnp(head: nn.Module, x2d: torch.Tensor, b: int, hw: int, pose: dict | None = None):
+    """SimplePointPnPNet on a prepared NHWC input ``x2d`` f32[b*hw, pitch] whose first ``head.conv1.in_channels`` channels are
+    the head's own concatenation: three launches — point-wise MLP + max over the points (``gdrnpp_point_pnp_pool``), fc1 / fc2
+    (``gdrnpp_point_pnp_fc``), fc_pose as the two row slices of its weight through ``pnp_fc_heads`` (which also leaves the pose
+    in ``pose["result"]``).  Outside the kernels (CPU tensor, HIP layers off, hw not a multiple of the point tile, more than 128
+    input channels) the same layers run as PyTorch operators, counted as a fallback."""
+    cin = head.conv1.in_channels
+    if (enabled_for(x2d) and x2d.dim() == 2 and x2d.is_contiguous() and hw % hip_lib.POINT_PNP_TILE == 0 and x2d.shape[1] % 32 == 0
+            and cin <= min(128, x2d.shape[1]) and not head.use_softpool):
+        _, ws = hip_lib.point_pnp_pool(x2d, cin, head.conv1.weight.detach(), head.conv1.bias.detach(), head.conv2.weight.detach(),
+                                       head.conv2.bias.detach(), head.conv3.weight.detach(), head.conv3.bias.detach(), b, hw,
+                                       want_pooled=False)
+        feat = hip_lib.point_pnp_fc(ws, head.fc1.weight.detach(), head.fc1.bias.detach(), head.fc2.weight.detach(),
+                                    head.fc2.bias.detach(), b, hw)
+        rd = head.rot_dim
+        w, bias = head.fc_pose.weight.detach(), head.fc_pose.bias.detach()      # row slices of a contiguous matrix are contiguous
+        w_r, w_t, b_r, b_t = w[:rd], w[rd:rd + 3], bias[:rd], bias[rd:rd + 3]
+        if pose is not None and rd == {"rot6d": 6, "quat": 4, "mat": 9, "log_quat": 3, "lie_vec": 3}[pose["rot_mode"]]:
+            kw = {k: v for k, v in pose.items() if k != "result"}
+            rot_, t_, R, trans = hip_lib.pnp_fc_heads_pose(feat, w_r, b_r, w_t, b_t, **kw)
+            pose["result"] = (R, trans)
+            return rot_, t_
+        return hip_lib.pnp_fc_heads(feat, w_r, b_r, w_t, b_t)
+    _fallback("point_pnp: SimplePointPnPNet outside the fused point-MLP kernel (PyTorch operators)", x2d)
+    return head.mlp_tail(x2d.view(b, hw, x2d.shape[1])[:, :, :cin].transpose(1, 2))

@@ -107,6 +107,9 @@ SIGNATURES = {
     "gdrnpp_deconv_col2im_gn_nhwc": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
     "gdrnpp_pnp_fc_heads": (c_int, [_P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, _P]),
     "gdrnpp_pnp_fc_heads_pose": (c_int, [_P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, c_int, _P]),
+    "gdrnpp_point_pnp_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "gdrnpp_point_pnp_pool": (c_int, [_P, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, _P, c_size_t, _P]),
+    "gdrnpp_point_pnp_fc": (c_int, [_P, c_size_t, _P, _P, _P, _P, _P, c_int, c_int, _P]),
     "gdrnpp_conv3x3_gnstats_partials": (c_int, [c_int, c_int]),
     "gdrnpp_conv3x3_f32_split_gnstats": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
     "gdrnpp_groupnorm_apply_nhwc": (c_int, [_P, _P, c_int, _P, _P, _P, c_int, c_int, c_int, c_int, c_float, c_int, _P]),
@@ -1118,6 +1121,44 @@ def pnp_fc_heads(x, w_r, b_r, w_t, b_t):
                                       _dev(b_t, torch.float32, "b_t") if b_t is not None else None, rot_.data_ptr(), t_.data_ptr(),
                                       b, k, rot_dim, _stream()), "gdrnpp_pnp_fc_heads")
     return rot_, t_
+
+
+POINT_PNP_TILE = 128     # points per workgroup of gdrnpp_point_pnp_pool: hw must be a multiple
+
+
+def point_pnp_pool(x2d, cin: int, w1, b1, w2, b2, w3, b3, b: int, hw: int, want_pooled: bool = True):
+    """SimplePointPnPNet's point-wise MLP + max over the points (``gdrnpp_point_pnp_pool``): x2d f32[b*hw, pitch] (NHWC rows, the
+    first ``cin`` channels used), Conv1d weights w1 [128,cin(,1)], w2 [128,128(,1)], w3 [1024,128(,1)] with their biases
+    -> (pooled f32[b,1024] or None, workspace holding the per-tile maxima for ``point_pnp_fc``)."""
+    if x2d.dim() != 2 or x2d.shape[0] != b * hw:
+        raise RuntimeError(f"point_pnp_pool: x2d must be [b*hw, pitch] = [{b * hw}, pitch], got {tuple(x2d.shape)}")
+    if tuple(w1.shape[:2]) != (128, cin) or tuple(w2.shape[:2]) != (128, 128) or tuple(w3.shape[:2]) != (1024, 128) \
+            or w1.numel() != 128 * cin or w2.numel() != 128 * 128 or w3.numel() != 1024 * 128 \
+            or b1.numel() != 128 or b2.numel() != 128 or b3.numel() != 1024:
+        raise RuntimeError("point_pnp_pool: weights must be Conv1d(cin,128,1), Conv1d(128,128,1), Conv1d(128,1024,1) with biases")
+    lib = load()
+    nbytes = lib.gdrnpp_point_pnp_workspace_bytes(b, hw)
+    if nbytes == 0:
+        raise RuntimeError(f"point_pnp_pool: b={b} hw={hw}: hw must be a positive multiple of {POINT_PNP_TILE}")
+    ws = torch.empty((nbytes // 4,), dtype=torch.float32, device=x2d.device)
+    pooled = torch.empty((b, 1024), dtype=torch.float32, device=x2d.device) if want_pooled else None
+    f = lambda v, n: _dev(v, torch.float32, n)  # noqa: E731
+    a = (f(x2d, "x"), x2d.shape[1], cin, f(w1, "w1"), f(b1, "b1"), f(w2, "w2"), f(b2, "b2"), f(w3, "w3"), f(b3, "b3"),
+         pooled.data_ptr() if want_pooled else None, b, hw, ws.data_ptr(), nbytes, _stream())
+    _check(_timed("mfma_f32:point_pnp_pool", 2.0 * b * hw * (128 * cin + 128 * 128 + 1024 * 128), lambda: lib.gdrnpp_point_pnp_pool(*a)),
+           "gdrnpp_point_pnp_pool")
+    return pooled, ws
+
+
+def point_pnp_fc(ws, w_fc1, b_fc1, w_fc2, b_fc2, b: int, hw: int):
+    """fc1 -> LeakyReLU(0.1) -> fc2 -> LeakyReLU(0.1) on the max over the tiles of ``ws`` (``gdrnpp_point_pnp_fc``) -> f32[b,256]."""
+    if tuple(w_fc1.shape) != (512, 1024) or tuple(w_fc2.shape) != (256, 512) or b_fc1.numel() != 512 or b_fc2.numel() != 256:
+        raise RuntimeError("point_pnp_fc: weights must be Linear(1024,512) and Linear(512,256) with biases")
+    feat = torch.empty((b, 256), dtype=torch.float32, device=ws.device)
+    f = lambda v, n: _dev(v, torch.float32, n)  # noqa: E731
+    _check(load().gdrnpp_point_pnp_fc(f(ws, "workspace"), ws.numel() * 4, f(w_fc1, "w_fc1"), f(b_fc1, "b_fc1"), f(w_fc2, "w_fc2"),
+                                      f(b_fc2, "b_fc2"), feat.data_ptr(), b, hw, _stream()), "gdrnpp_point_pnp_fc")
+    return feat
 
 
 ROT_MODES = {"rot6d": 0, "quat": 1, "mat": 2, "log_quat": 3, "lie_vec": 4}

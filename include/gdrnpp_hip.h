@@ -236,6 +236,31 @@ int gdrnpp_pnp_fc_heads_pose(const float* x, const float* w_r, const float* b_r,
                              float* t_, int b, int K, int rot_mode, int t_mode, const float* cams, const float* centers,
                              const float* whs, const float* resize_ratios, float* rot, float* trans, int is_allo, void* stream);
 
+/* ---- SimplePointPnPNet (core/gdrn_modeling/models/heads/point_pnp_net.py:208-293), use_softpool=False ---------------------
+ * The point-wise MLP conv1 -> LeakyReLU(0.1) -> conv2 -> LeakyReLU(0.1) -> conv3 (1x1 Conv1d, cin -> 128 -> 128 -> 1024) over
+ * the hw points of each ROI with the global max over the points in the last layer's epilogue: neither hidden layer nor the
+ * [b,1024,hw] tensor leaves the chip.  Exact-f32 matrix instructions (a k-ordered fmaf chain per output).
+ *   x  f32[b*hw][pitch]  NHWC, the first cin channels of a row are used; pitch % 32 == 0, cin <= pitch, cin <= 128
+ *   w1 f32[128][cin], b1 f32[128], w2 f32[128][128], b2 f32[128], w3 f32[1024][128], b3 f32[1024]   (Conv1d weights, kernel 1)
+ *   hw % 128 == 0: one workgroup per (ROI, tile of 128 points)
+ *   workspace: gdrnpp_point_pnp_workspace_bytes(b, hw) bytes (0 for sizes the kernel does not take); receives the per-tile
+ *              maxima f32[b][hw/128][1024] that gdrnpp_point_pnp_fc reads
+ *   pooled f32[b][1024] | NULL: the max over the ROI's points of W3 lrelu(W2 lrelu(W1 x + b1) + b2) + b3, written by a second
+ *              small launch; NULL when only gdrnpp_point_pnp_fc follows
+ * fp32 max is order-independent: results are bit-reproducible, no atomics, any number of streams.
+ * Argument errors (null pointer, b <= 0, hw % 128 != 0, cin > pitch, pitch % 32 != 0, small workspace) return a negative
+ * status before anything is launched. */
+size_t gdrnpp_point_pnp_workspace_bytes(int b, int hw);
+int gdrnpp_point_pnp_pool(const float* x, int pitch, int cin, const float* w1, const float* b1, const float* w2, const float* b2,
+                          const float* w3, const float* b3, float* pooled, int b, int hw, void* workspace, size_t workspace_bytes,
+                          void* stream);
+/* feat f32[b][256] = lrelu(fc2(lrelu(fc1(max over the tiles of the workspace)))), LeakyReLU slope 0.1 (point_pnp_net.py:287-288).
+ * w_fc1 f32[512][1024], b_fc1 f32[512], w_fc2 f32[256][512], b_fc2 f32[256] (nn.Linear layout).  fp32 fmaf chains in a fixed
+ * order, four ROIs per workgroup.  The last layer (fc_pose) is gdrnpp_pnp_fc_heads / gdrnpp_pnp_fc_heads_pose on feat with the
+ * rows [0, rot_dim) and [rot_dim, rot_dim + 3) of its weight. */
+int gdrnpp_point_pnp_fc(const void* workspace, size_t workspace_bytes, const float* w_fc1, const float* b_fc1, const float* w_fc2,
+                        const float* b_fc2, float* feat, int b, int hw, void* stream);
+
 /* ---- crop-resize intrinsics (a8.2) — camera_geometry.py:6-21 --------------
  * K f32[b,9], centers f32[b,2], scales f32[b] -> K_crop f32[b,9],
  * with crop_xy = center - scale/2 and ratio = out_res/scale
