@@ -1,0 +1,43 @@
+"""The YOLOX detector: PAFPN over CSPDarknet, decoupled head; inference only.
+
+``forward(x)`` on an eval-mode model returns ``{"det_preds": f32[B, A, 5 + num_classes]}`` — the tensor
+``det.yolox.utils.boxes.postprocess`` takes.  On the GPU with the HIP layers enabled the whole forward runs on
+csrc/yolox_net.hip (``hip_forward``); everywhere else it is the plain-PyTorch module path."""
+import torch.nn as nn
+
+from ....gdrn_modeling import hip_layers
+from . import hip_forward
+from .yolo_head import YOLOXHead
+from .yolo_pafpn import YOLOPAFPN
+
+
+class YOLOX(nn.Module):
+    def __init__(self, backbone=None, head=None):
+        super().__init__()
+        self.backbone = YOLOPAFPN() if backbone is None else backbone
+        self.head = YOLOXHead(80) if head is None else head
+        self.init_yolo()
+
+    def init_yolo(self):
+        for m in self.modules():
+            if isinstance(m, nn.BatchNorm2d):
+                m.eps = 1e-3
+                m.momentum = 0.03
+        self.head.initialize_biases(prior_prob=0.01)
+
+    def forward(self, x, targets=None, augment=False, cfg=None):
+        if augment:
+            raise NotImplementedError("augment=True (multi-scale test: needs scale_img's interpolation) is not implemented")
+        if targets is not None or self.training:
+            raise NotImplementedError("training mode (targets / self.training: the SimOTA assignment and losses) is not implemented")
+        if hip_layers.enabled_for(x) and hip_forward.supported(self, x):
+            return hip_forward.forward(self, x)
+        hip_layers.foreign("YOLOX: forward outside the HIP path (PyTorch operators)", x)
+        return self.head(self.backbone(x))
+
+
+def build_yolox(depth: float = 1.33, width: float = 1.25, num_classes: int = 21, act: str = "silu") -> YOLOX:
+    """YOLOX of the given size (s: 0.33 / 0.50, m: 0.67 / 0.75, l: 1.0 / 1.0, x: 1.33 / 1.25) in eval mode."""
+    in_channels = [256, 512, 1024]
+    model = YOLOX(YOLOPAFPN(depth, width, in_channels=in_channels, act=act), YOLOXHead(num_classes, width, in_channels=in_channels, act=act))
+    return model.eval()

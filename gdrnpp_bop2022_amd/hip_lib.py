@@ -93,6 +93,11 @@ SIGNATURES = {
         c_int, [_P, _P, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, _P, _P, _P]),
     "gdrnpp_yolox_postprocess_workspace_bytes": (c_size_t, [c_int, c_int]),
     "gdrnpp_yolox_postprocess": (c_int, [_P, c_int, c_int, c_int, c_float, c_float, c_int, _P, _P, c_int, _P, c_size_t, _P]),
+    "gdrnpp_conv_bias_act_f32": (c_int, [_P, c_int, c_int, _P, c_int, _P, _P, c_int, c_int, _P, c_int, c_int, c_long, c_long, c_int, c_int,
+                                         c_int, c_int, c_int, c_int, c_int, c_int, c_float, _P]),
+    "gdrnpp_yolox_focus": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
+    "gdrnpp_spp_maxpool_5_9_13": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
+    "gdrnpp_upsample_nearest2x_slice": (c_int, [_P, c_int, c_int, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
     "gdrnpp_paste_masks_rle": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_float, _P, _P, c_int, _P]),
     "gdrnpp_flow_forward": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, _P]),
     "gdrnpp_pack_pose_records": (c_int, [_P, _P, _P, _P, _P, _P, _P, c_int, _P]),
@@ -1240,6 +1245,83 @@ def yolox_postprocess(det_preds, num_classes: int, conf_thre: float = 0.7, nms_t
                                            float(nms_thre), 1 if class_agnostic else 0, dets.data_ptr(), count.data_ptr(), max_det,
                                            ws.data_ptr(), nbytes, _stream()), "gdrnpp_yolox_postprocess")
     return dets, count
+
+
+# ---- YOLOX detector forward (csrc/yolox_net.hip) ------------------------------------------------------------------------------
+CONV_ACTS = {"none": 0, "silu": 1, "sigmoid": 2, "yolox_box": 3}
+
+
+def pack_conv_weight_kmajor(weight: torch.Tensor) -> torch.Tensor:
+    """Conv2d weight f32[Cout,Cin,k,k] -> the B operand of ``gdrnpp_conv_bias_act_f32``: f32[k*k*Cin, ldw], row
+    (ky * k + kx) * Cin + ci, column = output channel, ldw = Cout rounded up to 4 (zero columns)."""
+    cout, cin, kh, kw = weight.shape
+    ldw = (cout + 3) // 4 * 4
+    out = torch.zeros((kh * kw * cin, ldw), dtype=torch.float32, device=weight.device)
+    out[:, :cout] = weight.detach().float().permute(2, 3, 1, 0).reshape(kh * kw * cin, cout)
+    return out
+
+
+def _nhwc_buf(t: torch.Tensor, name: str) -> int:
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous():
+        raise RuntimeError(f"{name} must be a contiguous float32 CUDA(HIP) tensor")
+    return t.data_ptr()
+
+
+def conv_bias_act_f32(a, a_off: int, cin: int, w_kmajor, bias, c, c_off: int, cout: int, ks: int, stride: int, act: str = "none",
+                      res=None, r_off: int = 0, c_img_rows: int = 0, c_row0: int = 0, dec_stride: float = 0.0):
+    """``gdrnpp_conv_bias_act_f32``: channels [a_off, a_off + cin) of a f32[B,H,W,lda] -> channels [c_off, c_off + cout) of c
+    (f32[B,OH,OW,ldc], or f32[B,c_img_rows,ldc] written from row c_row0 of every image); res (same pixels as c) is added after
+    the activation.  w_kmajor from ``pack_conv_weight_kmajor``.  Returns c."""
+    if a.dim() != 4:
+        raise RuntimeError(f"conv_bias_act_f32: a must be [B,H,W,lda], got {tuple(a.shape)}")
+    b, h, w, lda = a.shape
+    pad = (ks - 1) // 2
+    oh, ow = (h + 2 * pad - ks) // max(stride, 1) + 1, (w + 2 * pad - ks) // max(stride, 1) + 1
+    ldc = c.shape[-1]
+    want = (b, c_img_rows, ldc) if c_img_rows else (b, oh, ow, ldc)
+    if tuple(c.shape) != want:
+        raise RuntimeError(f"conv_bias_act_f32: c must be {want}, got {tuple(c.shape)}")
+    if res is not None and tuple(res.shape[:3]) != (b, oh, ow):
+        raise RuntimeError(f"conv_bias_act_f32: res must be [{b},{oh},{ow},ldr], got {tuple(res.shape)}")
+    if w_kmajor.dim() != 2 or w_kmajor.shape[0] != ks * ks * cin:
+        raise RuntimeError(f"conv_bias_act_f32: weight must be [{ks * ks * cin}, ldw], got {tuple(w_kmajor.shape)}")
+    if bias is not None and bias.numel() != cout:
+        raise RuntimeError(f"conv_bias_act_f32: bias must hold {cout} values")
+    args = (_nhwc_buf(a, "a"), lda, a_off, _nhwc_buf(w_kmajor, "weight"), w_kmajor.shape[1],
+            None if bias is None else _dev(bias, torch.float32, "bias"), None if res is None else _nhwc_buf(res, "res"),
+            0 if res is None else res.shape[-1], r_off, _nhwc_buf(c, "c"), ldc, c_off, c_img_rows, c_row0, b, h, w, cin, cout, ks, stride,
+            CONV_ACTS[act], float(dec_stride), _stream())
+    _check(_timed("mfma_f32:conv_bias_act", 2.0 * b * oh * ow * cout * ks * ks * cin, lambda: load().gdrnpp_conv_bias_act_f32(*args),
+                  4.0 * b * (h * w * cin + oh * ow * cout) + 4.0 * cout * ks * ks * cin), "gdrnpp_conv_bias_act_f32")
+    return c
+
+
+def yolox_focus(x_nchw, y, y_off: int = 0):
+    """``gdrnpp_yolox_focus``: x f32[B,3,H,W] -> 12 channels at y_off of y f32[B,H/2,W/2,ldy]."""
+    b, ch, h, w = x_nchw.shape
+    if ch != 3 or tuple(y.shape[:3]) != (b, h // 2, w // 2):
+        raise RuntimeError(f"yolox_focus: x [B,3,H,W] -> y [B,H/2,W/2,ldy], got {tuple(x_nchw.shape)} -> {tuple(y.shape)}")
+    _check(load().gdrnpp_yolox_focus(_dev(x_nchw, torch.float32, "x"), _nhwc_buf(y, "y"), y.shape[-1], y_off, b, h, w, _stream()),
+           "gdrnpp_yolox_focus")
+    return y
+
+
+def spp_maxpool_5_9_13(buf, off: int, c: int):
+    """``gdrnpp_spp_maxpool_5_9_13`` on buf f32[B,H,W,ld]: channels [off, off + c) -> their 5 / 9 / 13 max pools in the next three
+    slices of c channels."""
+    b, h, w, ld = buf.shape
+    _check(load().gdrnpp_spp_maxpool_5_9_13(_nhwc_buf(buf, "buf"), ld, off, c, b, h, w, _stream()), "gdrnpp_spp_maxpool_5_9_13")
+    return buf
+
+
+def upsample_nearest2x_slice(x, x_off: int, y, y_off: int, c: int):
+    """``gdrnpp_upsample_nearest2x_slice``: channels [x_off, x_off + c) of x f32[B,h,w,ldx] -> [y_off, y_off + c) of y f32[B,2h,2w,ldy]."""
+    b, h, w, ldx = x.shape
+    if tuple(y.shape[:3]) != (b, 2 * h, 2 * w):
+        raise RuntimeError(f"upsample_nearest2x_slice: y must be [{b},{2 * h},{2 * w},ldy], got {tuple(y.shape)}")
+    _check(load().gdrnpp_upsample_nearest2x_slice(_nhwc_buf(x, "x"), ldx, x_off, _nhwc_buf(y, "y"), y.shape[-1], y_off, b, h, w, c,
+                                                  _stream()), "gdrnpp_upsample_nearest2x_slice")
+    return y
 
 
 def paste_masks_rle(mask_probs, boxes_xyxy, im_h: int, im_w: int, threshold: float = 0.5, max_runs: int = 4096):

@@ -575,6 +575,43 @@ int gdrnpp_yolox_postprocess(const float* det_preds, int B, int A, int C, float 
                              int class_agnostic, float* out_dets, int* out_count, int max_det,
                              void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- YOLOX detector forward (det/yolox/models: CSPDarknet + PAFPN + decoupled head), csrc/yolox_net.hip.  All tensors NHWC fp32;
+ * a "slice" is `n` channels starting at channel `off` of a buffer whose pixel rows are `ld` channels long.  No atomics, no split
+ * over K: every launch is bit-reproducible.
+ *
+ * gdrnpp_conv_bias_act_f32: c = act(conv(a, w) + bias) + res — implicit GEMM on v_mfma_f32_32x32x2_f32, fp32 accumulation in
+ * a fixed two-level order per output (partial sums of about sqrt(K) products, then their sum).  Kernel ks x ks with ks in {1, 3}, stride in {1, 2}, padding (ks - 1) / 2, so
+ * OH = (H + 2 pad - ks) / stride + 1 (OW alike).
+ *   a    f32[B,H,W,lda], channels a_off .. a_off + cin; cin, lda and a_off multiples of 4.
+ *   w    f32[ks*ks*cin, ldw]: row (ky * ks + kx) * cin + ci, column = output channel; ldw a multiple of 4, >= cout (columns
+ *        beyond cout are not read into a result).  BatchNorm is folded by the caller.  Any cout: the last N tile may be partial.
+ *   bias f32[cout] or NULL.
+ *   res  NULL or f32[B,OH,OW,ldr], channels r_off .. r_off + cout, added AFTER the activation; may be the output slice itself.
+ *   c    channels c_off .. c_off + cout of rows of ldc channels.  c_img_rows = 0: c is f32[B,OH,OW,ldc] (c_row0 must be 0).
+ *        Otherwise c is f32[B,c_img_rows,ldc] and output pixel (oy, ox) of image b is row c_row0 + oy * OW + ox of that image
+ *        (a prediction layer writing at its level's anchor offset of det_preds).  Nothing outside the slice is written.
+ *        a must not overlap the output slice.
+ *   act  GDRNPP_ACT_*.  GDRNPP_ACT_YOLOX_BOX (cout = 4, no res): channel 0 -> (v + ox) * dec_stride, 1 -> (v + oy) * dec_stride,
+ *        2 and 3 -> exp(v) * dec_stride (the reference head's decode_outputs on the box columns).
+ * Argument errors return GDRNPP_EINVAL / GDRNPP_ELIMIT with gdrnpp_last_error text and launch nothing. */
+#define GDRNPP_ACT_NONE 0
+#define GDRNPP_ACT_SILU 1
+#define GDRNPP_ACT_SIGMOID 2
+#define GDRNPP_ACT_YOLOX_BOX 3
+int gdrnpp_conv_bias_act_f32(const float* a, int lda, int a_off, const float* w, int ldw, const float* bias, const float* res, int ldr,
+                             int r_off, float* c, int ldc, int c_off, long c_img_rows, long c_row0, int B, int H, int W, int cin,
+                             int cout, int ks, int stride, int act, float dec_stride, void* stream);
+/* Focus stem: x f32[B,3,H,W] (NCHW, H and W even) -> 12 channels at y_off of y f32[B,H/2,W/2,ldy]; channel 3 q + c holds colour c
+ * of the 2x2 cell's pixel q = top-left, bottom-left, top-right, bottom-right (the reference's concatenation order). */
+int gdrnpp_yolox_focus(const float* x_nchw, float* y, int ldy, int y_off, int B, int H, int W, void* stream);
+/* SPP: buf f32[B,H,W,ld]; reads channels off .. off + C and writes their stride-1 max pools with windows 5, 9 and 13 (borders
+ * padded with -inf, as nn.MaxPool2d) into channels off + C .., off + 2 C .., off + 3 C ..; off + 4 C <= ld.  One launch, exact. */
+int gdrnpp_spp_maxpool_5_9_13(float* buf, int ld, int off, int C, int B, int H, int W, void* stream);
+/* Nearest-neighbour x2 upsample of a slice into a slice: x f32[B,h,w,ldx] -> y f32[B,2h,2w,ldy]; C, offsets and row lengths
+ * multiples of 4. */
+int gdrnpp_upsample_nearest2x_slice(const float* x, int ldx, int x_off, float* y, int ldy, int y_off, int B, int h, int w, int C,
+                                    void* stream);
+
 /* ---- instance masks for SAVE_RESULTS_ONLY — gdrn_evaluator.py:914-945:
  * detectron2 paste_masks_in_image(mask_probs, boxes, (im_H, im_W), threshold) + the uncompressed COCO run-length
  * encoding of lib/utils/mask_utils.py:96-109, fused: the full-size masks are never materialised.
