@@ -79,7 +79,7 @@ __global__ __launch_bounds__(64 * WAVES, FC <= 128 ? 2 : 1) void mlp_fused_x3_ke
   const int g = lane >> 5;                              // k-block of the lane in a B operand / row group in an accumulator
   const float* trailer = reinterpret_cast<const float*>(Wp + (size_t)NT * TILE_SLOTS);
   const float wsc1 = trailer[1], wsc2 = trailer[5];
-  const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) const char*)smem;
+  const unsigned lds0 = lds_addr(smem);
 
   // 1 KB pieces of tile t's packed image: W1 part = pieces [0, W1_SLOTS / 64), W2 part behind it; each wave moves its share
   auto dma_part = [&](int t, int src_slot0, int n_pieces, unsigned dst_slot0) {

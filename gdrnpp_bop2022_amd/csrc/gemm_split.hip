@@ -24,7 +24,7 @@
 //   LDS image per operand: [split][k-block of 8][row] 16-byte slots, plane pitch 132 slots: the 32 lanes of a
 //      ds_read_b128 lane group read 32 consecutive slots (conflict-free), a fragment is one ds_read_b128;
 //   per k-tile: 12 fragment reads (ds_read_b128) feed 24 MFMAs.
-#include "gemm_split.hpp"
+#include "split_gemm_device.hpp"
 
 namespace {
 
@@ -83,12 +83,8 @@ __global__ __launch_bounds__(256, MI == 2 ? SPLIT_OCC : 2) void gemm_split_kerne
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave >> 1, wn = wave & 1;
   const int ntn = N / BN;
-  // XCD-aware map: hardware deals consecutive workgroup ids round-robin to the 8 XCDs; give each XCD a contiguous
-  // range of tile ids (bijective for any grid size)
-  const int nwg = gridDim.x, xcd = blockIdx.x & 7, q8 = nwg >> 3, r8 = nwg & 7;
-  const int tile = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (blockIdx.x >> 3);
-  const int tile_m = tile / ntn, tile_n = tile % ntn;
-  const int m0 = tile_m * BMT, n0 = tile_n * BN;  // the last m-tile may hang over M: its loads are clamped to row
+  const TileMN tile = tile_coords(xcd_tile_id(), ntn);
+  const int tile_n = tile.n, m0 = tile.m * BMT, n0 = tile_n * BN;  // the last m-tile may hang over M: its loads are clamped to row
                                                    // M-1 and its stores masked, so any M >= 1 is accepted
   // split-K (skinny problems: few rows, long K): workgroup (x, y) accumulates k-tiles [y*nk, (y+1)*nk) into its own
   // partial result C + y*M*N; gdrnpp_linear_f32_splitk sums the partials and applies the bias afterwards
@@ -116,7 +112,7 @@ __global__ __launch_bounds__(256, MI == 2 ? SPLIT_OCC : 2) void gemm_split_kerne
     }
   }
   if (CONV) cpt = cg.C / BK;
-  const int ntaps = CONV ? nk_total / cpt : 1, cps = (cpt & 1) ? 1 : 2;  // conv k-tile order: gemm_split.hpp
+  const int ntaps = CONV ? nk_total / cpt : 1;
   const uint4* Wg = Wp + ((size_t)tile_n * nk_total + kt0) * W_TILE_SLOTS + tid;
   struct Stage { float4 a[MI]; uint4 b0, b1, b2; };
   auto gload = [&](int kt) {
@@ -126,8 +122,8 @@ __global__ __launch_bounds__(256, MI == 2 ? SPLIT_OCC : 2) void gemm_split_kerne
       // the loads are unconditional (address clamped to the centre pixel, value zeroed afterwards): a predicated load
       // would make the outstanding-load count unknown to the compiler and collapse the software pipeline
       const int ka = kt0 + kt;   // absolute k-tile (split-K chunks of a convolution start mid-sequence)
-      const int sup = ka / (ntaps * cps), rem = ka - sup * (ntaps * cps), tap = rem / cps;
-      const int chunk = sup * cps + (rem - tap * cps), c0 = chunk * BK;
+      GDRNPP_CONV_KTILE(ka, cpt, ntaps);
+      const int c0 = chunk * BK;
       wkt = tap * cpt + chunk - kt0;   // Wg already points at weight tile kt0
       const int KW = CONV == 1 ? 3 : cg.KW, pad = CONV == 1 ? 1 : cg.pad;
       const int ky = tap / KW, dy = ky - pad, dx = tap - ky * KW - pad;
@@ -215,83 +211,36 @@ __global__ __launch_bounds__(256, MI == 2 ? SPLIT_OCC : 2) void gemm_split_kerne
     __syncthreads();
   }
 
-  // epilogue: lane holds column (lane & 31) of rows (r&3) + 8*(r>>2) + 4*(lane>>5).  Each wave parks one 16x64 slice
-  // of its tile in LDS (the A images are dead: the loop ends on a barrier) and writes it back row-wise as float4.
-  static_assert(2 * A_SLOTS * sizeof(uint4) >= 4 * 16 * 65 * sizeof(float), "epilogue staging fits the A images");
-  float* T = reinterpret_cast<float*>(sA) + wave * 16 * 65;  // [16][65] per wave
-  const int c4 = (lane & 15) * 4;
-  const int nb = n0 + wn * 64 + c4;
-  const float4 bv = bias ? *reinterpret_cast<const float4*>(bias + nb) : make_float4(0.f, 0.f, 0.f, 0.f);
-  float4 gv = make_float4(1.f, 1.f, 1.f, 1.f);
-  if (EPI == EPI_SCALE_RES) gv = *reinterpret_cast<const float4*>(gamma + nb);
-#pragma unroll
-  for (int ih = 0; ih < 2 * MI; ++ih) {
-    const int i = ih >> 1, h = ih & 1;  // 32-row MFMA tile i, its 16-row half h (accumulator registers h*8 .. h*8+7)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 8; ++r)
-        T[((r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)) * 65 + j * 32 + (lane & 31)] = acc[i][j][h * 8 + r];
-    __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): same wave reads back
-#pragma unroll
-    for (int rr = 0; rr < 4; ++rr) {
-      const int row = rr * 4 + (lane >> 4);
-      const float* t = T + row * 65 + c4;
-      float4 v = make_float4(t[0] + bv.x, t[1] + bv.y, t[2] + bv.z, t[3] + bv.w);
-      const int grow = m0 + wm * (MI * 32) + i * 32 + h * 16 + row;
-      if (grow >= M) continue;  // overhang of the last m-tile
-      const size_t off = (size_t)grow * N + nb;
-      if (EPI == EPI_GELU) { v.x = gelu_erf(v.x); v.y = gelu_erf(v.y); v.z = gelu_erf(v.z); v.w = gelu_erf(v.w); }
-      if (EPI == EPI_SCALE_RES) {
-        const float4 rs = *reinterpret_cast<const float4*>(resid + off);
-        v.x = rs.x + gv.x * v.x; v.y = rs.y + gv.y * v.y; v.z = rs.z + gv.z * v.z; v.w = rs.w + gv.w * v.w;
-      }
-      // streaming store: the result is not read again by this kernel, keep it from displacing the weights in L2
-      // (-4 % on the fc1 shapes, whose output is 4x their input)
-      { const f32x4v t4 = {v.x, v.y, v.z, v.w}; __builtin_nontemporal_store(t4, reinterpret_cast<f32x4v*>(C + off)); }
-    }
-    __builtin_amdgcn_s_waitcnt(0xc07f);  // reads done before the next slice overwrites T
-  }
+  // epilogue: each wave's 64 columns are one half
+#define EPI_TILES_M MI
+#define EPI_HALVES 1
+#define EPI_ACC(i, j) acc[i][j]
+#define EPI_ROW0 m0 + wm * (MI * 32)
+#define EPI_COL0 n0 + wn * 64
+#define EPI_BIAS bias
+#define EPI_STAGE sA
+#define EPI_STAGE_BYTES (2 * A_SLOTS * sizeof(uint4))
+#include "split_epilogue_body.hpp"
 }
 
 // ----------------------------------------------------------------------------------------------------------------
 // LDS-DMA form of the same GEMM (gdrnpp_set_option("split_gemm_glds", 1)): 256x128x16 block tile, 4 waves stacked along M
 // (each wave 64 rows x 128 columns = 2 x 4 MFMA tiles), NO register staging and NO ds_write in the k-loop:
-//   A  stays fp32 in HBM and goes HBM -> LDS by global_load_lds_dwordx4 (16 B per lane, four lanes cover one 64-byte row
+//   A  stays fp32 in HBM and goes HBM -> LDS by LDS-DMA (glds16: 16 B per lane, four lanes cover one 64-byte row
 //      segment, so the loads stay coalesced).  The LDS image is lane-linear (slot = 4*row + p); which 16-byte chunk q of
 //      the row segment a lane fetches is swizzled, q = p ^ ((row >> 2) & 3), so that the 16 lanes of a ds_read_b128 lane
 //      group hit 16 different bank quads when a fragment (32 rows x 8 k) is read back.  The exact 3-way bf16 split is
 //      done at fragment-read time in registers; with the waves stacked along M every A row is read and split by exactly
 //      one wave (same VALU work as splitting before the LDS store), and each wave stages precisely the rows it consumes;
-//   W  packed image (already the LDS image) by three global_load_lds_dwordx4 per wave and k-tile;
+//   W  packed image (already the LDS image) by three LDS-DMA loads per wave and k-tile;
 //   two LDS stages of 28 KB: the DMA of k-tile t+1 is issued before the MFMAs of k-tile t and waited for (vmcnt(0), the
 //      only VMEM traffic of the loop) in front of the one barrier per k-tile; two workgroups per CU.
 //   CONV taps outside the image fetch from a zero page instead of being predicated.
 // The DMA is issued from inline asm (the compiler would otherwise drain it in front of every LDS read it cannot prove
-// disjoint); M0 is set and restored inside the statement (cdna_hip_programming.md §5.7).
+// disjoint); M0 is set and restored inside the statement (glds16, split_gemm_device.hpp).
 // ----------------------------------------------------------------------------------------------------------------
-__device__ __attribute__((aligned(64))) float g_zero_page[16];
-
-__device__ __forceinline__ void glds16(const void* gsrc, unsigned lds_dst) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep)
-               : "v"(gsrc), "s"(lds_dst)
-               : "memory");
-}
-
-__device__ __forceinline__ unsigned lds_addr(const void* p) {
-  return (unsigned)(size_t)(__attribute__((address_space(3))) const char*)p;
-}
-
 constexpr int GA_SLOTS = 256 * 4;   // fp32 A image of one stage: 256 rows x 4 chunks of 16 B
 constexpr int GB_SLOTS = 3 * KB * BN;  // packed weight tile image
-
-// GroupNorm statistics of the result, taken in the epilogue of the convolution that produces it (GNS): every wave writes
-// the fp64 (sum, sum of squares) of its 64 rows x 8-channel groups to part[image][P][G][2], P = 4 * (256-row tiles per
-// image), slot 4 * tile + wave — the layout gn_apply_kernel (net_kernels.hip) reduces, so the separate statistics pass over
-// the stored tensor is not needed.  Requires 8 channels per group and images of a multiple of 256 pixels.
-struct GnStats { double* part; int G; int tiles_per_img; };
 
 template <int EPI, int CONV, bool GNS = false>
 __global__ __launch_bounds__(256, 2) void gemm_split_glds_kernel(const float* __restrict__ A, const uint4* __restrict__ Wp,
@@ -304,10 +253,8 @@ __global__ __launch_bounds__(256, 2) void gemm_split_glds_kernel(const float* __
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int ntn = N / BN;
-  const int nwg = gridDim.x, xcd = blockIdx.x & 7, q8 = nwg >> 3, r8 = nwg & 7;
-  const int tile = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (blockIdx.x >> 3);
-  const int tile_m = tile / ntn, tile_n = tile % ntn;
-  const int m0 = tile_m * 256, n0 = tile_n * BN;
+  const TileMN tile = tile_coords(xcd_tile_id(), ntn);
+  const int tile_n = tile.n, m0 = tile.m * 256, n0 = tile_n * BN;
   const int nk = K / BK;
 
   // A staging: DMA c (0..3) of this wave fills slots (wave*4 + c)*64 + lane = rows wave*64 + c*16 + lane/4
@@ -331,7 +278,7 @@ __global__ __launch_bounds__(256, 2) void gemm_split_glds_kernel(const float* __
     }
   }
   if (CONV) cpt = cg.C / BK;
-  const int ntaps = CONV ? nk / cpt : 1, cps = (cpt & 1) ? 1 : 2;  // conv k-tile order: gemm_split.hpp
+  const int ntaps = CONV ? nk / cpt : 1;
   const uint4* Wg = Wp + (size_t)tile_n * nk * W_TILE_SLOTS + (wave * 3) * 64 + lane;
   const unsigned ldsA = lds_addr(sA) + (unsigned)(wave * 4) * 1024u;
   const unsigned ldsB = lds_addr(sB) + (unsigned)(wave * 3) * 1024u;
@@ -340,8 +287,8 @@ __global__ __launch_bounds__(256, 2) void gemm_split_glds_kernel(const float* __
     const unsigned da = ldsA + (unsigned)stage * (GA_SLOTS * 16u), db = ldsB + (unsigned)stage * (GB_SLOTS * 16u);
     int wkt = kt;
     if (CONV) {
-      const int sup = kt / (ntaps * cps), rem = kt - sup * (ntaps * cps), tap = rem / cps;
-      const int chunk = sup * cps + (rem - tap * cps), c0 = chunk * BK;
+      GDRNPP_CONV_KTILE(kt, cpt, ntaps);
+      const int c0 = chunk * BK;
       wkt = tap * cpt + chunk;
       const int KW = CONV == 1 ? 3 : cg.KW, pad = CONV == 1 ? 1 : cg.pad;
       const int ky = tap / KW, dy = ky - pad, dx = tap - ky * KW - pad;
@@ -422,61 +369,16 @@ __global__ __launch_bounds__(256, 2) void gemm_split_glds_kernel(const float* __
     __syncthreads();
   }
 
-  // epilogue: as in gemm_split_kernel, per wave one 16x64 slice at a time through LDS (the A images are dead)
-  static_assert(2 * GA_SLOTS * sizeof(uint4) >= 4 * 16 * 65 * sizeof(float), "epilogue staging fits the A images");
-  float* T = reinterpret_cast<float*>(sA) + wave * 16 * 65;
-  const int c4 = (lane & 15) * 4;
-#pragma unroll
-  for (int jh = 0; jh < 2; ++jh) {
-    const int nb = n0 + jh * 64 + c4;
-    const float4 bv = bias ? *reinterpret_cast<const float4*>(bias + nb) : make_float4(0.f, 0.f, 0.f, 0.f);
-    float4 gv = make_float4(1.f, 1.f, 1.f, 1.f);
-    if (EPI == EPI_SCALE_RES) gv = *reinterpret_cast<const float4*>(gamma + nb);
-    double gs = 0.0, gss = 0.0;  // GNS: this lane's four columns over its 16 rows
-#pragma unroll
-    for (int ih = 0; ih < 4; ++ih) {
-      const int i = ih >> 1, h = ih & 1;
-#pragma unroll
-      for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int r = 0; r < 8; ++r)
-          T[((r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)) * 65 + j * 32 + (lane & 31)] = acc[i][jh * 2 + j][h * 8 + r];
-      __builtin_amdgcn_s_waitcnt(0xc07f);
-#pragma unroll
-      for (int rr = 0; rr < 4; ++rr) {
-        const int row = rr * 4 + (lane >> 4);
-        const float* t = T + row * 65 + c4;
-        float4 v = make_float4(t[0] + bv.x, t[1] + bv.y, t[2] + bv.z, t[3] + bv.w);
-        const int grow = m0 + wave * 64 + i * 32 + h * 16 + row;
-        if (grow >= M) continue;
-        const size_t off = (size_t)grow * N + nb;
-        if (GNS) {
-          gs += ((double)v.x + (double)v.y) + ((double)v.z + (double)v.w);
-          gss += ((double)v.x * v.x + (double)v.y * v.y) + ((double)v.z * v.z + (double)v.w * v.w);
-        }
-        if (EPI == EPI_GELU) { v.x = gelu_erf(v.x); v.y = gelu_erf(v.y); v.z = gelu_erf(v.z); v.w = gelu_erf(v.w); }
-        if (EPI == EPI_SCALE_RES) {
-          const float4 rs = *reinterpret_cast<const float4*>(resid + off);
-          v.x = rs.x + gv.x * v.x; v.y = rs.y + gv.y * v.y; v.z = rs.z + gv.z * v.z; v.w = rs.w + gv.w * v.w;
-        }
-        { const f32x4v t4 = {v.x, v.y, v.z, v.w}; __builtin_nontemporal_store(t4, reinterpret_cast<f32x4v*>(C + off)); }
-      }
-      __builtin_amdgcn_s_waitcnt(0xc07f);
-    }
-    if (GNS) {
-      // a group's 8 channels are the column quads of lanes 2k, 2k+1; its 64 rows sit in the four 16-lane row groups
-      gs += __shfl_xor(gs, 1, 64);   gss += __shfl_xor(gss, 1, 64);
-      gs += __shfl_xor(gs, 16, 64);  gss += __shfl_xor(gss, 16, 64);
-      gs += __shfl_xor(gs, 32, 64);  gss += __shfl_xor(gss, 32, 64);
-      if ((lane & 0x31) == 0) {
-        const int hw = cg.H * cg.W, img = m0 / hw, mt = (m0 - img * hw) >> 8;
-        const int g = ((n0 + jh * 64) >> 3) + (lane >> 1);
-        double* o = gn.part + (((size_t)img * (4 * gn.tiles_per_img) + 4 * mt + wave) * gn.G + g) * 2;
-        o[0] = gs;
-        o[1] = gss;
-      }
-    }
-  }
+#define EPI_TILES_M 2
+#define EPI_HALVES 2
+#define EPI_ACC(i, j) acc[i][j]
+#define EPI_ROW0 m0 + wave * 64
+#define EPI_COL0 n0
+#define EPI_BIAS bias
+#define EPI_STAGE sA
+#define EPI_STAGE_BYTES (2 * GA_SLOTS * sizeof(uint4))
+#define EPI_GN gn
+#include "split_epilogue_body.hpp"
 }
 
 }  // namespace
@@ -508,36 +410,39 @@ int launch_split_epi(const float* A, const uint4* Wp, const float* bias, const f
     const int rc = launch_split_pipe(A, Wp, bias, gamma, resid, C, M, N, K, EPI, CONV, cg, gdrnpp::option_split_gemm_pipe(), st, what);
     if (rc >= 0) return rc;
   }
-  if (big && gdrnpp::option_split_gemm_glds()) {   // LDS-DMA kernel: any M, any of the three A forms
-    if (CONV && fast3x3) hipLaunchKernelGGL((gemm_split_glds_kernel<EPI, CONV ? 1 : 0>), dim3((unsigned)tiles256), dim3(256), 0, st, A, Wp, bias, gamma, resid, C, M, N, K, cg, GnStats{nullptr, 0, 0});
-    else hipLaunchKernelGGL((gemm_split_glds_kernel<EPI, CONV ? 2 : 0>), dim3((unsigned)tiles256), dim3(256), 0, st, A, Wp, bias, gamma, resid, C, M, N, K, cg, GnStats{nullptr, 0, 0});
+  // the kernels' A form: linear, the 3x3 / stride 1 / pad 1 convolution, the general convolution
+  auto with_form = [&](auto&& launch) {
+    if (CONV && fast3x3) launch(std::integral_constant<int, CONV ? 1 : 0>{});
+    else launch(std::integral_constant<int, CONV ? 2 : 0>{});
     return gdrnpp::check_launch(what);
-  }
+  };
+  auto split_kernel = [&](auto mi, unsigned grid) {
+    return with_form([&](auto form) {
+      hipLaunchKernelGGL((gemm_split_kernel<EPI, decltype(form)::value, decltype(mi)::value>), dim3(grid), dim3(256), 0, st, A, Wp, bias, gamma, resid, C, M, N, K, cg);
+    });
+  };
+  if (big && gdrnpp::option_split_gemm_glds())   // LDS-DMA kernel: any M, any of the three A forms
+    return with_form([&](auto form) {
+      hipLaunchKernelGGL((gemm_split_glds_kernel<EPI, decltype(form)::value>), dim3((unsigned)tiles256), dim3(256), 0, st, A, Wp, bias, gamma, resid, C, M, N, K, cg, GnStats{nullptr, 0, 0});
+    });
   // (the general convolution form needs a few more registers than 256x128 tiles leave: it stays on 128x128 tiles)
-  if (M % 256 == 0 && big && !(CONV && !fast3x3)) {
-    if (CONV && fast3x3) hipLaunchKernelGGL((gemm_split_kernel<EPI, CONV ? 1 : 0, 4>), dim3((unsigned)tiles256), dim3(256), 0, st, A, Wp, bias, gamma, resid, C, M, N, K, cg);
-    else hipLaunchKernelGGL((gemm_split_kernel<EPI, CONV ? 2 : 0, 4>), dim3((unsigned)tiles256), dim3(256), 0, st, A, Wp, bias, gamma, resid, C, M, N, K, cg);
-    return gdrnpp::check_launch(what);
-  }
+  if (M % 256 == 0 && big && !(CONV && !fast3x3)) return split_kernel(std::integral_constant<int, 4>{}, (unsigned)tiles256);
   if (!CONV && !big && gdrnpp::option_split_gemm_pipe() && M >= 96) {   // few tiles: the 128-row form of the pipelined kernel
     const int rc = launch_split_pipe128(A, Wp, bias, gamma, resid, C, M, N, K, EPI, 0, st, what);
     if (rc >= 0) return rc;
   }
   const long blocks = (long)((M + BM - 1) / BM) * (N / BN);
   GDRNPP_REQUIRE(blocks < (1l << 31), GDRNPP_ELIMIT, "%s: grid too large", what);
-  if (CONV && fast3x3) hipLaunchKernelGGL((gemm_split_kernel<EPI, CONV ? 1 : 0, 2>), dim3((unsigned)blocks), dim3(256), 0, st, A, Wp, bias, gamma, resid, C, M, N, K, cg);
-  else hipLaunchKernelGGL((gemm_split_kernel<EPI, CONV ? 2 : 0, 2>), dim3((unsigned)blocks), dim3(256), 0, st, A, Wp, bias, gamma, resid, C, M, N, K, cg);
-  return gdrnpp::check_launch(what);
+  return split_kernel(std::integral_constant<int, 2>{}, (unsigned)blocks);
 }
 
 template <bool CONV>
 int launch_split(const float* A, const uint4* Wp, const float* bias, const float* gamma, const float* resid, float* C,
                  int M, int N, int K, int epilogue, ConvGeom cg, hipStream_t st, const char* what) {
-  if (epilogue == EPI_BIAS) return launch_split_epi<EPI_BIAS, CONV>(A, Wp, bias, gamma, resid, C, M, N, K, cg, st, what);
-  if (epilogue == EPI_GELU) return launch_split_epi<EPI_GELU, CONV>(A, Wp, bias, gamma, resid, C, M, N, K, cg, st, what);
-  return launch_split_epi<EPI_SCALE_RES, CONV>(A, Wp, bias, gamma, resid, C, M, N, K, cg, st, what);
+  return with_epilogue(epilogue, [&](auto epi) {
+    return launch_split_epi<decltype(epi)::value, CONV>(A, Wp, bias, gamma, resid, C, M, N, K, cg, st, what);
+  });
 }
-
 
 }  // namespace
 
@@ -571,6 +476,16 @@ __global__ void splitk_reduce_kernel(const float* __restrict__ part, const float
     acc.x = r.x + g.x * acc.x; acc.y = r.y + g.y * acc.y; acc.z = r.z + g.z * acc.z; acc.w = r.w + g.w * acc.w;
   }
   reinterpret_cast<float4*>(out)[i] = acc;
+}
+
+int launch_splitk_reduce(int epilogue, const float* part, const float* bias, const float* gamma, const float* resid, float* out, long mn,
+                         int N, int splits, hipStream_t st, const char* what) {
+  const long mn4 = mn / 4;
+  return with_epilogue(epilogue, [&](auto epi) {
+    hipLaunchKernelGGL(splitk_reduce_kernel<decltype(epi)::value>, dim3((unsigned)((mn4 + 255) / 256)), dim3(256), 0, st, part, bias, gamma,
+                       resid, out, mn4, N, splits);
+    return gdrnpp::check_launch(what);
+  });
 }
 
 // k-tiles (of 16) per split: halve the chunk (keeping it even) until every CU has about three workgroups
@@ -659,13 +574,7 @@ extern "C" int gdrnpp_linear_f32_splitk(const float* A, const void* W_packed, co
                        (const uint4*)W_packed, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr,
                        (float*)workspace, M, N, K, ConvGeom{0, 0, 0, 0, 0, 0, 0, 0, nkc});
   }
-  const long mn4 = (long)M * N / 4;
-  const dim3 grid((unsigned)((mn4 + 255) / 256));
-  const float* ws = (const float*)workspace;
-  if (epilogue == EPI_BIAS) hipLaunchKernelGGL(splitk_reduce_kernel<EPI_BIAS>, grid, dim3(256), 0, st, ws, bias, gamma, resid, C, mn4, N, splits);
-  else if (epilogue == EPI_GELU) hipLaunchKernelGGL(splitk_reduce_kernel<EPI_GELU>, grid, dim3(256), 0, st, ws, bias, gamma, resid, C, mn4, N, splits);
-  else hipLaunchKernelGGL(splitk_reduce_kernel<EPI_SCALE_RES>, grid, dim3(256), 0, st, ws, bias, gamma, resid, C, mn4, N, splits);
-  return gdrnpp::check_launch("gdrnpp_linear_f32_splitk");
+  return launch_splitk_reduce(epilogue, (const float*)workspace, bias, gamma, resid, C, (long)M * N, N, splits, st, "gdrnpp_linear_f32_splitk");
 }
 
 extern "C" int gdrnpp_linear_f32_split(const float* A, const void* W_packed, const float* bias, const float* gamma,
@@ -685,15 +594,10 @@ extern "C" int gdrnpp_conv2d_f32_split(const float* x_nhwc, const void* W_packed
                                        int n_img, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad,
                                        int epilogue, void* stream) {
   GDRNPP_REQUIRE(x_nhwc && W_packed && y_nhwc, GDRNPP_EINVAL, "gdrnpp_conv2d_f32_split: null pointer");
-  GDRNPP_REQUIRE(n_img > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && H < 32768 && W < 32768 && KH > 0 && KW > 0 &&
-                     stride > 0 && pad >= 0 && pad < KH && pad < KW,
-                 GDRNPP_EINVAL, "gdrnpp_conv2d_f32_split: bad shape");
-  const int OH = (H + 2 * pad - KH) / stride + 1, OW = (W + 2 * pad - KW) / stride + 1;
-  GDRNPP_REQUIRE(OH > 0 && OW > 0 && (OH - 1) * stride < H && (OW - 1) * stride < W, GDRNPP_EINVAL,
-                 "gdrnpp_conv2d_f32_split: empty output or anchor pixel outside the image");
-  const long M = (long)n_img * OH * OW;
-  GDRNPP_REQUIRE(M < (1l << 31) && Cout % BN == 0 && Cin % 32 == 0, GDRNPP_ELIMIT,
-                 "gdrnpp_conv2d_f32_split: Cout=%d Cin=%d must be multiples of %d/32 (pixels=%ld is free)", Cout, Cin, BN, M);
+  ConvShape sh;
+  if (const int rc = check_conv_shape("gdrnpp_conv2d_f32_split", n_img, H, W, Cin, Cout, KH, KW, stride, pad, 0, &sh)) return rc;
+  const int OH = sh.OH, OW = sh.OW;
+  const long M = sh.M;
   GDRNPP_REQUIRE(epilogue == EPI_BIAS || epilogue == EPI_GELU, GDRNPP_EINVAL, "gdrnpp_conv2d_f32_split: epilogue=%d", epilogue);
   return launch_split<true>(x_nhwc, (const uint4*)W_packed, bias, nullptr, nullptr, y_nhwc, (int)M, Cout, KH * KW * Cin, epilogue,
                             ConvGeom{H, W, Cin, OH, OW, KW, stride, pad, 0}, (hipStream_t)stream, "gdrnpp_conv2d_f32_split");
@@ -728,15 +632,10 @@ extern "C" int gdrnpp_conv2d_f32_splitk(const float* x_nhwc, const void* W_packe
                                         int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int epilogue,
                                         void* workspace, size_t workspace_bytes, void* stream) {
   GDRNPP_REQUIRE(x_nhwc && W_packed && y_nhwc, GDRNPP_EINVAL, "gdrnpp_conv2d_f32_splitk: null pointer");
-  GDRNPP_REQUIRE(n_img > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && H < 32768 && W < 32768 && KH > 0 && KW > 0 &&
-                     stride > 0 && pad >= 0 && pad < KH && pad < KW,
-                 GDRNPP_EINVAL, "gdrnpp_conv2d_f32_splitk: bad shape");
-  const int OH = (H + 2 * pad - KH) / stride + 1, OW = (W + 2 * pad - KW) / stride + 1;
-  GDRNPP_REQUIRE(OH > 0 && OW > 0 && (OH - 1) * stride < H && (OW - 1) * stride < W, GDRNPP_EINVAL,
-                 "gdrnpp_conv2d_f32_splitk: empty output or anchor pixel outside the image");
-  const long M = (long)n_img * OH * OW;
-  GDRNPP_REQUIRE(M < (1l << 31) && Cout % BN == 0 && Cin % 32 == 0, GDRNPP_ELIMIT,
-                 "gdrnpp_conv2d_f32_splitk: Cout=%d Cin=%d must be multiples of %d/32", Cout, Cin, BN);
+  ConvShape sh;
+  if (const int rc = check_conv_shape("gdrnpp_conv2d_f32_splitk", n_img, H, W, Cin, Cout, KH, KW, stride, pad, 0, &sh)) return rc;
+  const int OH = sh.OH, OW = sh.OW;
+  const long M = sh.M;
   GDRNPP_REQUIRE(epilogue == EPI_BIAS || epilogue == EPI_GELU, GDRNPP_EINVAL, "gdrnpp_conv2d_f32_splitk: epilogue=%d", epilogue);
   const int K = KH * KW * Cin, splits = conv_splitk_chunks(M, Cout, K);
   if (splits == 1)
@@ -755,11 +654,7 @@ extern "C" int gdrnpp_conv2d_f32_splitk(const float* x_nhwc, const void* W_packe
     hipLaunchKernelGGL((gemm_split_kernel<EPI_BIAS, 2, 2>), dim3((unsigned)tiles, (unsigned)splits), dim3(256), 0, st, x_nhwc,
                        (const uint4*)W_packed, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr,
                        (float*)workspace, (int)M, Cout, K, cg);
-  const long mn4 = M * Cout / 4;
-  const dim3 grid((unsigned)((mn4 + 255) / 256));
-  if (epilogue == EPI_BIAS) hipLaunchKernelGGL(splitk_reduce_kernel<EPI_BIAS>, grid, dim3(256), 0, st, (const float*)workspace, bias, (const float*)nullptr, (const float*)nullptr, y_nhwc, mn4, Cout, splits);
-  else hipLaunchKernelGGL(splitk_reduce_kernel<EPI_GELU>, grid, dim3(256), 0, st, (const float*)workspace, bias, (const float*)nullptr, (const float*)nullptr, y_nhwc, mn4, Cout, splits);
-  return gdrnpp::check_launch("gdrnpp_conv2d_f32_splitk");
+  return launch_splitk_reduce(epilogue, (const float*)workspace, bias, nullptr, nullptr, y_nhwc, M * Cout, Cout, splits, st, "gdrnpp_conv2d_f32_splitk");
 }
 
 extern "C" int gdrnpp_conv3x3_f32_split(const float* x_nhwc, const void* W_packed, const float* bias, float* y_nhwc,

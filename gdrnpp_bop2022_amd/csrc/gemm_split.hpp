@@ -2,6 +2,7 @@
 // the software-pipelined LDS-DMA form).  See gemm_split.hip for the numerical scheme (exact 3-way bf16 operand split, six
 // partial products on v_mfma_f32_32x32x16_bf16 with fp32 accumulation).
 #pragma once
+#include <type_traits>
 #include "common.hpp"
 
 namespace gdrnpp {
@@ -38,6 +39,32 @@ enum { EPI_BIAS = 0, EPI_GELU = 1, EPI_SCALE_RES = 2 };
 struct ConvGeom { int H, W, C, OH, OW, KW, stride, pad; int nk_split; };
 
 using gdrnpp::gelu_erf;  // common.hpp
+
+// the run-time `epilogue` of an entry point as the template argument of its kernels: f(std::integral_constant<int, EPI_*>{})
+template <class F>
+inline int with_epilogue(int epilogue, F&& f) {
+  if (epilogue == EPI_BIAS) return f(std::integral_constant<int, EPI_BIAS>{});
+  if (epilogue == EPI_GELU) return f(std::integral_constant<int, EPI_GELU>{});
+  return f(std::integral_constant<int, EPI_SCALE_RES>{});
+}
+
+// Shape checks of the convolution entry points (`what` = the entry point, for the message; max_taps: 0 = any number): 0 and
+// the output image / GEMM rows in *s, or the error code with the text set
+struct ConvShape { int OH, OW; long M; };
+inline int check_conv_shape(const char* what, int n_img, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad,
+                            int max_taps, ConvShape* s) {
+  GDRNPP_REQUIRE(n_img > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && H < 32768 && W < 32768 && KH > 0 && KW > 0 &&
+                     (max_taps == 0 || KH * KW <= max_taps) && stride > 0 && pad >= 0 && pad < KH && pad < KW,
+                 GDRNPP_EINVAL, max_taps ? "%s: bad shape (at most %d taps)" : "%s: bad shape", what, max_taps);
+  s->OH = (H + 2 * pad - KH) / stride + 1;
+  s->OW = (W + 2 * pad - KW) / stride + 1;
+  GDRNPP_REQUIRE(s->OH > 0 && s->OW > 0 && (s->OH - 1) * stride < H && (s->OW - 1) * stride < W, GDRNPP_EINVAL,
+                 "%s: empty output or anchor pixel outside the image", what);
+  s->M = (long)n_img * s->OH * s->OW;
+  GDRNPP_REQUIRE(s->M < (1l << 31) && Cout % BN == 0 && Cin % 32 == 0, GDRNPP_ELIMIT,
+                 "%s: Cout=%d Cin=%d must be multiples of %d/32 (pixels=%ld is free)", what, Cout, Cin, BN, s->M);
+  return 0;
+}
 
 // Software-pipelined LDS-DMA kernel (gemm_split_pipe.hip).  Handles the linear form and the 3x3/1/1 convolution with
 // M*K*4 (resp. the image bytes) below 4 GiB; returns -1 when the problem is outside its domain (the caller then uses the

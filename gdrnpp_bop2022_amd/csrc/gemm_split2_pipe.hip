@@ -40,8 +40,8 @@
 // v_fma_mix_f32 residual, cvt_pk: 32 VALU operations) spread over the MFMA slots of k-tile t, both weight fragment sets read
 // just in time (l behind the barrier of the previous k-tile, h in slots 1 and 3), one barrier per k-tile behind slot 19.
 // 80 KB of dynamic LDS (three A stages, four weight slots: one barrier per two k-tiles), two workgroups per CU.  Linear form, the 3x3 / stride 1 / pad 1 convolution and the general K x K /
-// stride / pad convolution (implicit im2col, k-tile order of gemm_split.hpp), optional GroupNorm statistics in the epilogue (as
-// gemm_split_glds_kernel<.., GNS>).  -DGDRNPP2_TIMING_NO_{BREAD,SPLIT,SYNC,DMA}: timing-only builds (results invalid) behind
+// stride / pad convolution (implicit im2col, k-tile order of gemm_split.hpp), optional GroupNorm statistics in the epilogue (GnStats,
+// split_gemm_device.hpp).  -DGDRNPP2_TIMING_NO_{BREAD,SPLIT,SYNC,DMA}: timing-only builds (results invalid) behind
 // profiles/r03y_split2_kloop_dissection.txt.
 #include "split2_common.hpp"
 
@@ -55,7 +55,6 @@ constexpr int W2_TILE_SLOTS = 2 * KB * BN;     // uint4 slots of one packed 128x
 constexpr int W2_TILE_B = W2_TILE_SLOTS * 16;  // 8 KB
 
 __device__ int g_split2_range_word;  // sticky range word (GDRNPP_SPLIT2_NONFINITE | GDRNPP_SPLIT2_SMALL_ROWS) of launches that pass no word of their own
-__device__ __attribute__((aligned(64))) float g_split2_zero_page[16];
 
 // One half of a wave's A tile for one k-tile: 32 rows x 16 k, 8 consecutive k of one row per lane.  x ~ h + l in 8 steps of two
 // VALU operations (the residual overwrites x).  APRE: A is an "f16x2 rows" tensor (split2_common.hpp) — the two 16-byte chunks the
@@ -149,8 +148,6 @@ __global__ void pack_weight2_kernel(const float* __restrict__ W, uint4* __restri
   img[(1 * KB + kb) * BN + row] = make_uint4(l[0], l[1], l[2], l[3]);
 }
 
-struct GnStats2 { double* part; int G; int tiles_per_img; };   // as GnStats of gemm_split.hip
-
 // CONV: 0 = linear (A row-major [M,K]), 1 = 3x3 / stride 1 / pad 1 convolution over an NHWC image (geometry folded at compile
 //       time), 2 = any KH x KW / stride / zero padding with at most 32 taps (ConvNeXt's 2x2/2 downsamples, Patch-PnP's 3x3/2)
 // GNS: GroupNorm (sum, sum of squares) partials of the stored result per wave (64 rows x 8-channel groups), CONV only
@@ -163,7 +160,7 @@ __global__ __launch_bounds__(256, NJ == 4 ? 2 : 1) void gemm_split2_pipe_kernel(
                                                                   const float* __restrict__ bias,
                                                                   const float* __restrict__ gamma,
                                                                   const float* __restrict__ resid, float* __restrict__ C,
-                                                                  int M, int N, int K, ConvGeom cg, int panel, GnStats2 gn, int* range_flag, int c_rows) {
+                                                                  int M, int N, int K, ConvGeom cg, int panel, GnStats gn, int* range_flag, int c_rows) {
   static_assert(!APRE || CONV == 0, "f16x2-rows A: linear form only");
   using HalfSplit2 = HalfSplit2T<APRE>;
   constexpr int BNB = NJ * 32;                     // block columns
@@ -184,22 +181,10 @@ __global__ __launch_bounds__(256, NJ == 4 ? 2 : 1) void gemm_split2_pipe_kernel(
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int ntn = N / BNB;
-  // XCD-aware tile order, as in gemm_split.hip
-  const int nwg = gridDim.x, xcd = blockIdx.x & 7, q8 = nwg >> 3, r8 = nwg & 7;
-  const int tile = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (blockIdx.x >> 3);
-  int tile_m, tile_n;
-  if (panel > 1) {  // panel order for wide layers, see launch_split_pipe (gemm_split_pipe.hip)
-    const int ntm = (M + 255) >> 8, per = panel * ntn, p = tile / per, w = tile - p * per;
-    const int rows = min(panel, ntm - p * panel);
-    tile_n = w / rows;
-    tile_m = p * panel + (w - tile_n * rows);
-  } else {
-    tile_m = tile / ntn;
-    tile_n = tile - tile_m * ntn;
-  }
-  const int m0 = tile_m * 256, n0 = tile_n * BNB;
+  const TileMN tile = tile_coords(xcd_tile_id(), ntn, panel, M);   // panel order for wide layers, see launch_split_pipe (gemm_split_pipe.hip)
+  const int tile_n = tile.n, m0 = tile.m * 256, n0 = tile_n * BNB;
   const int nk = K / BK;
-  const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) const char*)smem;
+  const unsigned lds0 = lds_addr(smem);
   const float wsc = reinterpret_cast<const float*>(Wp + (size_t)(N / BN) * nk * W2_TILE_SLOTS)[1];   // 2^-e of the weight scale (trailer)
 
   // ---- DMA lanes: piece c (0..3) of this wave fills A slots (wave*4 + c)*64 + lane = rows wave*64 + c*16 + lane/4, chunk
@@ -255,12 +240,12 @@ __global__ __launch_bounds__(256, NJ == 4 ? 2 : 1) void gemm_split2_pipe_kernel(
   auto dma_a = [&](int kt, unsigned sb, auto cc) {
     constexpr int c = decltype(cc)::value;
     if constexpr (CONV) {
-      const int cps = (cpt & 1) ? 1 : 2, sup = kt / (ntaps * cps), rem = kt - sup * (ntaps * cps), tap = rem / cps;  // gemm_split.hpp
-      const int c0 = (sup * cps + (rem - tap * cps)) * BK;
+      GDRNPP_CONV_KTILE(kt, cpt, ntaps);
+      const int c0 = chunk * BK;
       const int ky = tap / ckw, dy = ky - cpad, dx = tap - ky * ckw - cpad;
       const long off = ((long)dy * cg.W + dx) * cg.C + c0;
       const bool ok = (okmask[c] >> tap) & 1u;
-      dma_v(ok ? (const void*)(ap[c] + off) : (const void*)g_split2_zero_page, ldsA + sb + c * 1024u);
+      dma_v(ok ? (const void*)(ap[c] + off) : (const void*)g_zero_page, ldsA + sb + c * 1024u);
     } else {
       dma_s(aoff[c], reinterpret_cast<const char*>(A) + (size_t)kt * (BK * 4), ldsA + sb + c * 1024u);
     }
@@ -269,8 +254,8 @@ __global__ __launch_bounds__(256, NJ == 4 ? 2 : 1) void gemm_split2_pipe_kernel(
     constexpr int c = decltype(cc)::value;
     int wkt = kt;
     if constexpr (CONV) {
-      const int cps = (cpt & 1) ? 1 : 2, sup = kt / (ntaps * cps), rem = kt - sup * (ntaps * cps), tap = rem / cps;
-      wkt = tap * cpt + sup * cps + (rem - tap * cps);
+      GDRNPP_CONV_KTILE(kt, cpt, ntaps);
+      wkt = tap * cpt + chunk;
     }
     constexpr int t = c >> 1, sub = c & 1;   // piece c = half `sub` of this wave's 2 KB share of the packed 128-column tile t
     dma_s(boff, wbase + (((size_t)t * nk + wkt) * W2_TILE_B + sub * 1024), ldsB + sb + (unsigned)(t * W2_TILE_B + sub * 1024));
@@ -434,70 +419,19 @@ __global__ __launch_bounds__(256, NJ == 4 ? 2 : 1) void gemm_split2_pipe_kernel(
   __builtin_amdgcn_s_waitcnt(0xc07f);
   __builtin_amdgcn_s_barrier();  // every wave's stages are dead: the epilogue reuses them
 
-  // ---- epilogue: per wave one 16x64 slice at a time through LDS, written back row-wise as float4 (as in gemm_split.hip)
-  float* T = reinterpret_cast<float*>(smem) + wave * 16 * 65;
-  const int c4 = (lane & 15) * 4;
   bool bad = false;
-#pragma unroll
-  for (int jh = 0; jh < NJ / 2; ++jh) {
-    const int nb = n0 + jh * 64 + c4;
-    const float4 bv = bias ? *reinterpret_cast<const float4*>(bias + nb) : make_float4(0.f, 0.f, 0.f, 0.f);
-    float4 gv = make_float4(1.f, 1.f, 1.f, 1.f);
-    if (EPI == EPI_SCALE_RES) gv = *reinterpret_cast<const float4*>(gamma + nb);
-    double gs = 0.0, gss = 0.0;  // GNS: this lane's four columns over its 16 rows
-#pragma unroll
-    for (int ih = 0; ih < 4; ++ih) {
-      const int i = ih >> 1, h = ih & 1;
-#pragma unroll
-      for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int r = 0; r < 8; ++r)
-          T[((r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)) * 65 + j * 32 + (lane & 31)] = acc[i][jh * 2 + j][h * 8 + r];
-      __builtin_amdgcn_s_waitcnt(0xc07f);
-#pragma unroll
-      for (int rr = 0; rr < 4; ++rr) {
-        const int row = rr * 4 + (lane >> 4);
-        const float* t = T + row * 65 + c4;
-        float4 v = make_float4(t[0] * wsc + bv.x, t[1] * wsc + bv.y, t[2] * wsc + bv.z, t[3] * wsc + bv.w);
-        const int grow = m0 + wave * 64 + i * 32 + h * 16 + row;
-        if (grow >= M) continue;
-        const size_t off = (size_t)grow * N + nb;
-        if (GNS) {
-          gs += ((double)v.x + (double)v.y) + ((double)v.z + (double)v.w);
-          gss += ((double)v.x * v.x + (double)v.y * v.y) + ((double)v.z * v.z + (double)v.w * v.w);
-        }
-        if (EPI == EPI_GELU) { v.x = gelu_erf(v.x); v.y = gelu_erf(v.y); v.z = gelu_erf(v.z); v.w = gelu_erf(v.w); }
-        if (EPI == EPI_SCALE_RES) {
-          const float4 rs = *reinterpret_cast<const float4*>(resid + off);
-          v.x = rs.x + gv.x * v.x; v.y = rs.y + gv.y * v.y; v.z = rs.z + gv.z * v.z; v.w = rs.w + gv.w * v.w;
-        }
-        constexpr unsigned kInfNan = 0x203u;   // v_cmp_class_f32: signalling / quiet NaN, -inf, +inf
-        bad |= __builtin_amdgcn_class(v.x, kInfNan) | __builtin_amdgcn_class(v.y, kInfNan) |
-               __builtin_amdgcn_class(v.z, kInfNan) | __builtin_amdgcn_class(v.w, kInfNan);
-        if (EPI != EPI_SCALE_RES && c_rows) {   // lanes 2k / 2k + 1 hold columns 8k .. 8k + 3 / 8k + 4 .. 8k + 7 of the same row
-          const uint4 o = f16x2_rows_quad(v.x, v.y, v.z, v.w, lane & 1);
-          const f32x4v t4 = {__uint_as_float(o.x), __uint_as_float(o.y), __uint_as_float(o.z), __uint_as_float(o.w)};
-          __builtin_nontemporal_store(t4, reinterpret_cast<f32x4v*>(C + off));
-        } else {
-          const f32x4v t4 = {v.x, v.y, v.z, v.w}; __builtin_nontemporal_store(t4, reinterpret_cast<f32x4v*>(C + off));
-        }
-      }
-      __builtin_amdgcn_s_waitcnt(0xc07f);
-    }
-    if (GNS) {
-      // a group's 8 channels are the column quads of lanes 2k, 2k+1; its 64 rows sit in the four 16-lane row groups
-      gs += __shfl_xor(gs, 1, 64);   gss += __shfl_xor(gss, 1, 64);
-      gs += __shfl_xor(gs, 16, 64);  gss += __shfl_xor(gss, 16, 64);
-      gs += __shfl_xor(gs, 32, 64);  gss += __shfl_xor(gss, 32, 64);
-      if ((lane & 0x31) == 0) {
-        const int hw = cg.H * cg.W, img = m0 / hw, mt = (m0 - img * hw) >> 8;
-        const int g = ((n0 + jh * 64) >> 3) + (lane >> 1);
-        double* o = gn.part + (((size_t)img * (4 * gn.tiles_per_img) + 4 * mt + wave) * gn.G + g) * 2;
-        o[0] = gs;
-        o[1] = gss;
-      }
-    }
-  }
+#define EPI_TILES_M 2
+#define EPI_HALVES (NJ / 2)
+#define EPI_ACC(i, j) acc[i][j]
+#define EPI_ROW0 m0 + wave * 64
+#define EPI_COL0 n0
+#define EPI_BIAS bias
+#define EPI_STAGE smem
+#define EPI_STAGE_BYTES (NA * A_STAGE_B)
+#define EPI_SCALE wsc
+#define EPI_GN gn
+#define EPI_RANGE_BAD bad
+#include "split_epilogue_body.hpp"
   // range verdict of the wave's 64 A rows: lanes l and l ^ 32 hold the two k-block halves of rows frow and frow + 32
   bool small = false;
 #ifndef GDRNPP2_NO_RANGE_CHECK
@@ -517,7 +451,7 @@ __global__ __launch_bounds__(256, NJ == 4 ? 2 : 1) void gemm_split2_pipe_kernel(
 
 template <int EPI, int CONV, bool GNS, int NJ, bool APRE = false>
 int launch_nj(const float* A, const uint4* Wp, const float* bias, const float* gamma, const float* resid, float* C, int M, int N,
-              int K, ConvGeom cg, int panel, GnStats2 gn, int* range_flag, hipStream_t st, const char* what, int c_rows = 0) {
+              int K, ConvGeom cg, int panel, GnStats gn, int* range_flag, hipStream_t st, const char* what, int c_rows = 0) {
 #ifndef GDRNPP2_SINGLE_BARRIER
   constexpr int lds_bytes = NA * A_STAGE_B + (NJ == 4 ? 4 : 2) * (NJ / 4) * W2_TILE_B;   // NJ = 4: 80 KB, two workgroups fill the CU's 160 KB
 #else
@@ -537,7 +471,7 @@ int launch_nj(const float* A, const uint4* Wp, const float* bias, const float* g
 // 189 us, stage-0 fc1 623 vs 533 us: one wave per SIMD has nobody to hide its LDS / DMA latencies behind)
 template <int EPI, int CONV, bool GNS>
 int launch_one(const float* A, const uint4* Wp, const float* bias, const float* gamma, const float* resid, float* C, int M, int N,
-               int K, ConvGeom cg, int panel, GnStats2 gn, int* range_flag, hipStream_t st, const char* what, int a_rows = 0, int c_rows = 0) {
+               int K, ConvGeom cg, int panel, GnStats gn, int* range_flag, hipStream_t st, const char* what, int a_rows = 0, int c_rows = 0) {
   if constexpr (CONV == 0 && EPI != EPI_BIAS) {   // the f16x2-rows forms exist for the two MLP layers (GELU / scale + residual)
     if (a_rows) return launch_nj<EPI, CONV, GNS, 4, true>(A, Wp, bias, gamma, resid, C, M, N, K, cg, panel, gn, range_flag, st, what, c_rows);
   }
@@ -587,14 +521,14 @@ extern "C" int gdrnpp_linear_f32_split2_rows(const float* A, const void* W_packe
   // wide layers walk the tiles in panels (gemm_split_pipe.hip: launch_split_pipe); the fp16x2 image is 4 bytes per weight
   const int panel = (N / BN >= 8 && (long)N * K * 4 > (2l << 20)) ? gdrnpp::option_split_gemm_panel() : 0;
   const ConvGeom cg{0, 0, 0, 0, 0, 0, 0, 0, 0};
-  const GnStats2 gn{nullptr, 0, 0};
+  const GnStats gn{nullptr, 0, 0};
   hipStream_t st = (hipStream_t)stream;
   const uint4* Wp = (const uint4*)W_packed;
   const char* what = "gdrnpp_linear_f32_split2";
   const int ar = rows & GDRNPP_A_F16X2_ROWS, cr = (rows & GDRNPP_C_F16X2_ROWS) ? 1 : 0;
-  if (epilogue == EPI_BIAS) return launch_one<EPI_BIAS, 0, false>(A, Wp, bias, gamma, resid, C, M, N, K, cg, panel, gn, range_flag, st, what, 0, cr);
-  if (epilogue == EPI_GELU) return launch_one<EPI_GELU, 0, false>(A, Wp, bias, gamma, resid, C, M, N, K, cg, panel, gn, range_flag, st, what, ar, cr);
-  return launch_one<EPI_SCALE_RES, 0, false>(A, Wp, bias, gamma, resid, C, M, N, K, cg, panel, gn, range_flag, st, what, ar, 0);
+  return with_epilogue(epilogue, [&](auto epi) {   // (the checks above leave ar = 0 with EPI_BIAS and cr = 0 with EPI_SCALE_RES)
+    return launch_one<decltype(epi)::value, 0, false>(A, Wp, bias, gamma, resid, C, M, N, K, cg, panel, gn, range_flag, st, what, ar, cr);
+  });
 }
 
 extern "C" int gdrnpp_linear_f32_split2(const float* A, const void* W_packed, const float* bias, const float* gamma,
@@ -622,9 +556,9 @@ extern "C" int gdrnpp_conv3x3_f32_split2(const float* x_nhwc, const void* W_pack
                    "gdrnpp_conv3x3_f32_split2: GroupNorm statistics need the plain epilogue, H*W %% 256 == 0 and 8 channels per group "
                    "(H*W=%d Cout=%d groups=%d)", H * W, Cout, groups);
     return launch_one<EPI_BIAS, 1, true>(x_nhwc, Wp, bias, nullptr, nullptr, y_nhwc, (int)M, Cout, 9 * Cin, cg, 0,
-                                         GnStats2{gn_partials, groups, (H * W) / 256}, range_flag, st, what);
+                                         GnStats{gn_partials, groups, (H * W) / 256}, range_flag, st, what);
   }
-  const GnStats2 gn{nullptr, 0, 0};
+  const GnStats gn{nullptr, 0, 0};
   if (epilogue == EPI_GELU)
     return launch_one<EPI_GELU, 1, false>(x_nhwc, Wp, bias, nullptr, nullptr, y_nhwc, (int)M, Cout, 9 * Cin, cg, 0, gn, range_flag, st, what);
   return launch_one<EPI_BIAS, 1, false>(x_nhwc, Wp, bias, nullptr, nullptr, y_nhwc, (int)M, Cout, 9 * Cin, cg, 0, gn, range_flag, st, what);
@@ -634,20 +568,15 @@ extern "C" int gdrnpp_conv2d_f32_split2(const float* x_nhwc, const void* W_packe
                                         int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int epilogue,
                                         int* range_flag, void* stream) {
   GDRNPP_REQUIRE(x_nhwc && W_packed && y_nhwc, GDRNPP_EINVAL, "gdrnpp_conv2d_f32_split2: null pointer");
-  GDRNPP_REQUIRE(n_img > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && H < 32768 && W < 32768 && KH > 0 && KW > 0 && KH * KW <= 32 &&
-                     stride > 0 && pad >= 0 && pad < KH && pad < KW,
-                 GDRNPP_EINVAL, "gdrnpp_conv2d_f32_split2: bad shape (at most 32 taps)");
+  ConvShape sh;
+  if (const int rc = check_conv_shape("gdrnpp_conv2d_f32_split2", n_img, H, W, Cin, Cout, KH, KW, stride, pad, 32, &sh)) return rc;
   if (KH == 3 && KW == 3 && stride == 1 && pad == 1)
     return gdrnpp_conv3x3_f32_split2(x_nhwc, W_packed, bias, y_nhwc, nullptr, n_img, H, W, Cin, Cout, 0, epilogue, range_flag, stream);
-  const int OH = (H + 2 * pad - KH) / stride + 1, OW = (W + 2 * pad - KW) / stride + 1;
-  GDRNPP_REQUIRE(OH > 0 && OW > 0 && (OH - 1) * stride < H && (OW - 1) * stride < W, GDRNPP_EINVAL,
-                 "gdrnpp_conv2d_f32_split2: empty output or anchor pixel outside the image");
-  const long M = (long)n_img * OH * OW;
-  GDRNPP_REQUIRE(M < (1l << 31) && Cout % BN == 0 && Cin % 32 == 0, GDRNPP_ELIMIT,
-                 "gdrnpp_conv2d_f32_split2: Cout=%d Cin=%d must be multiples of %d/32", Cout, Cin, BN);
+  const int OH = sh.OH, OW = sh.OW;
+  const long M = sh.M;
   GDRNPP_REQUIRE(epilogue == EPI_BIAS || epilogue == EPI_GELU, GDRNPP_EINVAL, "gdrnpp_conv2d_f32_split2: epilogue=%d", epilogue);
   const ConvGeom cg{H, W, Cin, OH, OW, KW, stride, pad, 0};
-  const GnStats2 gn{nullptr, 0, 0};
+  const GnStats gn{nullptr, 0, 0};
   hipStream_t st = (hipStream_t)stream;
   const uint4* Wp = (const uint4*)W_packed;
   const char* what = "gdrnpp_conv2d_f32_split2";

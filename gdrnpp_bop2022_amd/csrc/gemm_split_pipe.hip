@@ -19,7 +19,7 @@
 //
 // LDS: NA x 16 KB (A, fp32) + 2 x 12 KB (weights) = 56 / 72 KB dynamic, two workgroups per CU.
 // Results are bitwise equal to the other split-GEMM kernels (same products, same order per accumulator).
-#include "gemm_split.hpp"
+#include "split_gemm_device.hpp"
 
 namespace {
 
@@ -27,31 +27,6 @@ using namespace gdrnpp::splitgemm;
 
 constexpr int A_STAGE_B = 256 * BK * 4;       // fp32 A image of one k-tile: 16 KB
 constexpr int B_STAGE_B = W_TILE_SLOTS * 16;  // packed weight tile image: 12 KB
-
-__device__ __attribute__((aligned(64))) float g_pipe_zero_page[16];
-
-// LDS-DMA pieces (1 KiB per wave): M0 = LDS destination, written in the statement that uses it (cdna_hip_programming.md
-// §5.7).  hipcc does not count these loads: the kernel waits for them itself with counted vmcnt.
-// (No instruction offset: on an LDS-DMA load the immediate moves the LDS destination as well as the source address.)
-__device__ __forceinline__ void dma_s(unsigned voff, const void* sbase, unsigned lds_dst) {
-  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(sbase), "s"(lds_dst)
-               : "memory");
-}
-__device__ __forceinline__ void dma_v(const void* gsrc, unsigned lds_dst) {
-  asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(gsrc), "s"(lds_dst) : "memory");
-}
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
-template <int I, int E, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-  if constexpr (I < E) {
-    f(std::integral_constant<int, I>{});
-    static_for<I + 1, E>(f);
-  }
-}
 
 __device__ __forceinline__ unsigned cvt_pk_bf16(float a, float b) {
   const f32x2 v = {a, b};
@@ -135,26 +110,14 @@ __global__ __launch_bounds__(256, 2) void gemm_split_pipe_kernel(const float* __
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int ntn = N / BN;
-  // XCD-aware tile order, as in gemm_split.hip
-  const int nwg = gridDim.x, xcd = blockIdx.x & 7, q8 = nwg >> 3, r8 = nwg & 7;
-  const int tile = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (blockIdx.x >> 3);
-  int tile_m, tile_n;
-  if (grp.panel > 1) {  // panel order for wide layers, see launch_split_pipe
-    const int ntm = (M + 255) >> 8, per = grp.panel * ntn, p = tile / per, w = tile - p * per;
-    const int rows = min(grp.panel, ntm - p * grp.panel);
-    tile_n = w / rows;
-    tile_m = p * grp.panel + (w - tile_n * rows);
-  } else {
-    tile_m = tile / ntn;
-    tile_n = tile - tile_m * ntn;
-  }
-  const int m0 = tile_m * 256, n0 = tile_n * BN;
+  const TileMN tile = tile_coords(xcd_tile_id(), ntn, grp.panel, M);   // panel order for wide layers, see launch_split_pipe
+  const int tile_n = tile.n, m0 = tile.m * 256, n0 = tile_n * BN;
   // split-K (linear form, cg.nk_split > 0): workgroup (x, y) multiplies k-tiles [y * nk_split, (y + 1) * nk_split) and writes
   // the partial result C + y*M*N; gdrnpp_linear_f32_splitk sums the partials in fixed order and applies bias / epilogue
   const int kt0 = (!CONV && cg.nk_split > 0) ? (int)blockIdx.y * cg.nk_split : 0;
   const int nk = (!CONV && cg.nk_split > 0) ? cg.nk_split : K / BK;
   if (!CONV && cg.nk_split > 0) C += (size_t)blockIdx.y * (size_t)M * (size_t)N;
-  const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) const char*)smem;
+  const unsigned lds0 = lds_addr(smem);
 
   // ---- DMA lanes: piece c (0..3) of this wave fills A slots (wave*4 + c)*64 + lane = rows wave*64 + c*16 + lane/4, chunk
   // q = (lane & 3) ^ ((row >> 2) & 3) of the row's 64-byte k segment (the swizzle is on the source address)
@@ -207,12 +170,12 @@ __global__ __launch_bounds__(256, 2) void gemm_split_pipe_kernel(const float* __
   auto dma_a = [&](int kt, unsigned sb, auto cc) {
     constexpr int c = decltype(cc)::value;
     if constexpr (CONV) {
-      const int cps = (cpt & 1) ? 1 : 2, sup = kt / (9 * cps), rem = kt - sup * (9 * cps), tap = rem / cps;  // gemm_split.hpp
-      const int c0 = (sup * cps + (rem - tap * cps)) * BK;
+      GDRNPP_CONV_KTILE(kt, cpt, 9);
+      const int c0 = chunk * BK;
       const int ky = tap / 3, dy = ky - 1, dx = tap - ky * 3 - 1;
       const long off = ((long)dy * cg.W + dx) * cg.C + c0;
       const bool ok = (okmask[c] >> tap) & 1u;
-      dma_v(ok ? (const void*)(ap[c] + off) : (const void*)g_pipe_zero_page, ldsA + sb + c * 1024u);
+      dma_v(ok ? (const void*)(ap[c] + off) : (const void*)g_zero_page, ldsA + sb + c * 1024u);
     } else {
       dma_s(aoff[c], reinterpret_cast<const char*>(A) + (size_t)(kt0 + kt) * (BK * 4), ldsA + sb + c * 1024u);
     }
@@ -221,8 +184,8 @@ __global__ __launch_bounds__(256, 2) void gemm_split_pipe_kernel(const float* __
     constexpr int c = decltype(cc)::value;
     int wkt = kt0 + kt;
     if constexpr (CONV) {
-      const int cps = (cpt & 1) ? 1 : 2, sup = kt / (9 * cps), rem = kt - sup * (9 * cps), tap = rem / cps;
-      wkt = tap * cpt + sup * cps + (rem - tap * cps);
+      GDRNPP_CONV_KTILE(kt, cpt, 9);
+      wkt = tap * cpt + chunk;
     }
     dma_s(boff, wbase + ((size_t)wkt * B_STAGE_B + c * 1024), ldsB + sb + c * 1024u);
   };
@@ -342,46 +305,16 @@ __global__ __launch_bounds__(256, 2) void gemm_split_pipe_kernel(const float* __
   __builtin_amdgcn_s_waitcnt(0xc07f);
   __builtin_amdgcn_s_barrier();  // every wave's stages are dead: the epilogue reuses them
 
-  // ---- epilogue: per wave one 16x64 slice at a time through LDS, written back row-wise as float4 (as in gemm_split.hip)
-  float* T = reinterpret_cast<float*>(smem) + wave * 16 * 65;
-  const int c4 = (lane & 15) * 4;
-#pragma unroll
-  for (int jh = 0; jh < 2; ++jh) {
-    const int nb = n0 + jh * 64 + c4;
-    const float4 bv = bias_t ? *reinterpret_cast<const float4*>(bias_t + nb) : make_float4(0.f, 0.f, 0.f, 0.f);
-    float4 gv = make_float4(1.f, 1.f, 1.f, 1.f);
-    if (EPI == EPI_SCALE_RES) gv = *reinterpret_cast<const float4*>(gamma + nb);
-#pragma unroll
-    for (int ih = 0; ih < 4; ++ih) {
-      const int i = ih >> 1, h = ih & 1;
-#pragma unroll
-      for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int r = 0; r < 8; ++r)
-          T[((r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)) * 65 + j * 32 + (lane & 31)] = acc[i][jh * 2 + j][h * 8 + r];
-      __builtin_amdgcn_s_waitcnt(0xc07f);
-#pragma unroll
-      for (int rr = 0; rr < 4; ++rr) {
-        const int row = rr * 4 + (lane >> 4);
-        const float* t = T + row * 65 + c4;
-        float4 v = make_float4(t[0] + bv.x, t[1] + bv.y, t[2] + bv.z, t[3] + bv.w);
-        const int grow = m0 + wave * 64 + i * 32 + h * 16 + row;
-        if (grow >= M || nb >= grp.n_store) continue;
-        const size_t off = (size_t)grow * N + nb;
-        if (EPI == EPI_GELU) { v.x = gelu_erf(v.x); v.y = gelu_erf(v.y); v.z = gelu_erf(v.z); v.w = gelu_erf(v.w); }
-        if (EPI == EPI_SCALE_RES) {
-          const float4 rs = *reinterpret_cast<const float4*>(resid + off);
-          v.x = rs.x + gv.x * v.x; v.y = rs.y + gv.y * v.y; v.z = rs.z + gv.z * v.z; v.w = rs.w + gv.w * v.w;
-        }
-#ifdef GDRNPP_TIMING_NO_STORE   // timing-only build (results invalid): the epilogue without its global stores
-        if (v.x == 1.2345e38f) C[off] = v.y;
-#else
-        { const f32x4v t4 = {v.x, v.y, v.z, v.w}; __builtin_nontemporal_store(t4, reinterpret_cast<f32x4v*>(C + off)); }
-#endif
-      }
-      __builtin_amdgcn_s_waitcnt(0xc07f);
-    }
-  }
+#define EPI_TILES_M 2
+#define EPI_HALVES 2
+#define EPI_ACC(i, j) acc[i][j]
+#define EPI_ROW0 m0 + wave * 64
+#define EPI_COL0 n0
+#define EPI_BIAS bias_t
+#define EPI_STAGE smem
+#define EPI_STAGE_BYTES (NA * A_STAGE_B)
+#define EPI_N_STORE grp.n_store
+#include "split_epilogue_body.hpp"
 }
 
 // --------------------------------------------------------------------------------------------------------------------
@@ -410,14 +343,12 @@ __global__ __launch_bounds__(256, 2) void gemm_split_pipe128_kernel(const float*
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int ntn = N / BN;
-  const int nwg = gridDim.x, xcd = blockIdx.x & 7, q8 = nwg >> 3, r8 = nwg & 7;
-  const int tile = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (blockIdx.x >> 3);
-  const int tile_m = tile / ntn, tile_n = tile - tile_m * ntn;
-  const int m0 = tile_m * 128, n0 = tile_n * BN;
+  const TileMN tile = tile_coords(xcd_tile_id(), ntn);
+  const int tile_n = tile.n, m0 = tile.m * 128, n0 = tile_n * BN;
   const int kt0 = nk_split > 0 ? (int)blockIdx.y * nk_split : 0;
   const int nk = nk_split > 0 ? nk_split : K / BK;
   if (nk_split > 0) C += (size_t)blockIdx.y * (size_t)M * (size_t)N;
-  const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) const char*)smem;
+  const unsigned lds0 = lds_addr(smem);
 
   const int prow = lane >> 2, pq = lane & 3;
   unsigned aoff[2];
@@ -540,41 +471,15 @@ __global__ __launch_bounds__(256, 2) void gemm_split_pipe128_kernel(const float*
   __builtin_amdgcn_s_waitcnt(0xc07f);
   __builtin_amdgcn_s_barrier();  // every wave's stages are dead: the epilogue reuses them
 
-  // ---- epilogue: per wave one 16x64 slice at a time through LDS, written back row-wise as float4
-  float* T = reinterpret_cast<float*>(smem) + wave * 16 * 65;
-  const int c4 = (lane & 15) * 4;
-#pragma unroll
-  for (int jh = 0; jh < 2; ++jh) {
-    const int nb = n0 + jh * 64 + c4;
-    const float4 bv = bias ? *reinterpret_cast<const float4*>(bias + nb) : make_float4(0.f, 0.f, 0.f, 0.f);
-    float4 gv = make_float4(1.f, 1.f, 1.f, 1.f);
-    if (EPI == EPI_SCALE_RES) gv = *reinterpret_cast<const float4*>(gamma + nb);
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-#pragma unroll
-      for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int r = 0; r < 8; ++r)
-          T[((r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)) * 65 + j * 32 + (lane & 31)] = acc[jh * 2 + j][h * 8 + r];
-      __builtin_amdgcn_s_waitcnt(0xc07f);
-#pragma unroll
-      for (int rr = 0; rr < 4; ++rr) {
-        const int row = rr * 4 + (lane >> 4);
-        const float* t = T + row * 65 + c4;
-        float4 v = make_float4(t[0] + bv.x, t[1] + bv.y, t[2] + bv.z, t[3] + bv.w);
-        const int grow = m0 + wave * 32 + h * 16 + row;
-        if (grow >= M) continue;
-        const size_t off = (size_t)grow * N + nb;
-        if (EPI == EPI_GELU) { v.x = gelu_erf(v.x); v.y = gelu_erf(v.y); v.z = gelu_erf(v.z); v.w = gelu_erf(v.w); }
-        if (EPI == EPI_SCALE_RES) {
-          const float4 rs = *reinterpret_cast<const float4*>(resid + off);
-          v.x = rs.x + gv.x * v.x; v.y = rs.y + gv.y * v.y; v.z = rs.z + gv.z * v.z; v.w = rs.w + gv.w * v.w;
-        }
-        { const f32x4v t4 = {v.x, v.y, v.z, v.w}; __builtin_nontemporal_store(t4, reinterpret_cast<f32x4v*>(C + off)); }
-      }
-      __builtin_amdgcn_s_waitcnt(0xc07f);
-    }
-  }
+#define EPI_TILES_M 1
+#define EPI_HALVES 2
+#define EPI_ACC(i, j) acc[j]
+#define EPI_ROW0 m0 + wave * 32
+#define EPI_COL0 n0
+#define EPI_BIAS bias
+#define EPI_STAGE smem
+#define EPI_STAGE_BYTES (NA * A128_STAGE_B)
+#include "split_epilogue_body.hpp"
 }
 
 template <int EPI>
@@ -625,9 +530,9 @@ int launch_na(int a_stages, const float* A, const uint4* Wp, const float* bias, 
 template <int CONV>
 int launch_epi(int epilogue, int a_stages, const float* A, const uint4* Wp, const float* bias, const float* gamma,
                const float* resid, float* C, int M, int N, int K, ConvGeom cg, Grouped grp, hipStream_t st, const char* what) {
-  if (epilogue == EPI_BIAS) return launch_na<EPI_BIAS, CONV>(a_stages, A, Wp, bias, gamma, resid, C, M, N, K, cg, grp, st, what);
-  if (epilogue == EPI_GELU) return launch_na<EPI_GELU, CONV>(a_stages, A, Wp, bias, gamma, resid, C, M, N, K, cg, grp, st, what);
-  return launch_na<EPI_SCALE_RES, CONV>(a_stages, A, Wp, bias, gamma, resid, C, M, N, K, cg, grp, st, what);
+  return with_epilogue(epilogue, [&](auto epi) {
+    return launch_na<decltype(epi)::value, CONV>(a_stages, A, Wp, bias, gamma, resid, C, M, N, K, cg, grp, st, what);
+  });
 }
 
 }  // namespace
@@ -663,9 +568,7 @@ int launch_split_pipe128(const float* A, const uint4* Wp, const float* bias, con
   if ((unsigned long long)M * (unsigned long long)K * 4ull >= (1ull << 32)) return -1;  // 32-bit lane offsets
   if ((long)((M + 127) / 128) * (N / BN) >= (1l << 30)) return -1;
   if (nk_split > 0) return launch_pipe128<EPI_BIAS>(A, Wp, nullptr, nullptr, nullptr, C, M, N, K, nk_split, st, what);
-  if (epilogue == EPI_BIAS) return launch_pipe128<EPI_BIAS>(A, Wp, bias, gamma, resid, C, M, N, K, 0, st, what);
-  if (epilogue == EPI_GELU) return launch_pipe128<EPI_GELU>(A, Wp, bias, gamma, resid, C, M, N, K, 0, st, what);
-  return launch_pipe128<EPI_SCALE_RES>(A, Wp, bias, gamma, resid, C, M, N, K, 0, st, what);
+  return with_epilogue(epilogue, [&](auto epi) { return launch_pipe128<decltype(epi)::value>(A, Wp, bias, gamma, resid, C, M, N, K, 0, st, what); });
 }
 
 // Split-K launch of the pipelined kernel: partials[y][M][N] for the (K/16) / nk_split chunks of nk_split (even) k-tiles.

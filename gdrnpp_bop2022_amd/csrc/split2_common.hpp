@@ -1,6 +1,7 @@
-// Device helpers shared by the three-product (fp16x2) GEMM kernels: gemm_split2_pipe.hip and gemm_mlp_fused.hip.
+// Device helpers of the three-product (fp16x2) GEMM kernels alone: gemm_split2_pipe.hip and gemm_mlp_fused.hip (what they share
+// with the six-product kernels is in split_gemm_device.hpp).
 #pragma once
-#include "gemm_split.hpp"
+#include "split_gemm_device.hpp"
 
 namespace gdrnpp {
 namespace split2 {
@@ -8,25 +9,6 @@ namespace split2 {
 using namespace gdrnpp::splitgemm;
 using f16x2 = __attribute__((ext_vector_type(2))) _Float16;
 using f16x8 = __attribute__((ext_vector_type(8))) _Float16;
-
-__device__ __forceinline__ void dma_s(unsigned voff, const void* sbase, unsigned lds_dst) {
-  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(sbase), "s"(lds_dst)
-               : "memory");
-}
-__device__ __forceinline__ void dma_v(const void* gsrc, unsigned lds_dst) {
-  asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(gsrc), "s"(lds_dst) : "memory");
-}
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-template <int I, int E, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-  if constexpr (I < E) {
-    f(std::integral_constant<int, I>{});
-    static_for<I + 1, E>(f);
-  }
-}
 
 __device__ __forceinline__ unsigned cvt_pk_f16(float a, float b) {
   const f32x2 v = {a, b};

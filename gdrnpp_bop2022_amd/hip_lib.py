@@ -885,6 +885,26 @@ def _count_x3():
 X3 = "_x3"   # LaunchTimer kind suffix of the three-product (fp16x2) kernels: 3 instead of 6 MFMA flops per fp32-equivalent flop
 
 
+_EPILOGUES = {"none": 0, "gelu": 1, "scale_res": 2}
+
+
+def _packed_weight(weight_packed, k: int, what: str, contiguous: bool = False):
+    """Validate a packed split-GEMM weight with GEMM depth ``k`` (``contiguous``: and that it is contiguous); returns
+    (N, True for the three-product fp16x2 format).  ``what`` is the caller's message."""
+    fp16x2 = weight_packed.dtype == torch.float16     # pack_weight_f16x2: the three-product kernel
+    if weight_packed.dtype not in (torch.bfloat16, torch.float16) or weight_packed.dim() != 6 \
+            or (contiguous and not weight_packed.is_contiguous()) \
+            or weight_packed.shape[1] * 16 != k or weight_packed.shape[2] != (2 if fp16x2 else 3):
+        raise ValueError(what)
+    return weight_packed.shape[0] * 128, fp16x2
+
+
+def _channels_last_f32(x_cl, what: str):
+    if not x_cl.is_contiguous(memory_format=torch.channels_last) or x_cl.dtype != torch.float32 or not x_cl.is_cuda:
+        raise ValueError("%s expects a float32 channels_last device tensor" % what)
+    return x_cl.shape
+
+
 def linear_f32_split(x2d, weight_packed, bias, epilogue: str = "none", gamma=None, resid=None, _kind: str = "linear", x3_slot: int = 0,
                      a_rows: bool = False, c_rows: bool = False):
     """out = epilogue(x2d @ W^T + bias) with the weight given as pack_weight_bf16x3(weight); runs on the bf16 matrix cores
@@ -892,17 +912,14 @@ def linear_f32_split(x2d, weight_packed, bias, epilogue: str = "none", gamma=Non
     three-product kernel; there ``a_rows`` = x2d is an "f16x2 rows" tensor (epilogues gelu / scale_res), ``c_rows`` = write the
     result as one (epilogues none / gelu) — gdrnpp_linear_f32_split2_rows, bit-identical to the fp32 hand-over."""
     m, k = x2d.shape
-    fp16x2 = weight_packed.dtype == torch.float16     # pack_weight_f16x2: the three-product kernel
-    if weight_packed.dtype not in (torch.bfloat16, torch.float16) or weight_packed.dim() != 6 or not weight_packed.is_contiguous() \
-            or weight_packed.shape[1] * 16 != k or weight_packed.shape[2] != (2 if fp16x2 else 3):
-        raise ValueError("weight_packed must be the contiguous tensor from pack_weight_bf16x3 / pack_weight_f16x2 with matching K")
-    n = weight_packed.shape[0] * 128
+    n, fp16x2 = _packed_weight(weight_packed, k, "weight_packed must be the contiguous tensor from pack_weight_bf16x3 / pack_weight_f16x2 with matching K",
+                               contiguous=True)
     out = torch.empty((m, n), dtype=torch.float32, device=x2d.device)
     args = (_dev(x2d, torch.float32, "x"), weight_packed.data_ptr(),
             _dev(bias, torch.float32, "bias") if bias is not None else None,
             _dev(gamma, torch.float32, "gamma") if gamma is not None else None,
             _dev(resid, torch.float32, "resid") if resid is not None else None, out.data_ptr(), m, n, k,
-            {"none": 0, "gelu": 1, "scale_res": 2}[epilogue]) + \
+            _EPILOGUES[epilogue]) + \
         (((A_F16X2_ROWS if a_rows else 0) | (C_F16X2_ROWS if c_rows else 0), _x3_flag_ptr(x3_slot)) if fp16x2 else ()) + (_stream(),)
     if (a_rows or c_rows) and not fp16x2:
         raise ValueError("f16x2-rows tensors exist for the three-product kernel (pack_weight_f16x2) only")
@@ -966,7 +983,7 @@ def linear_f32_splitk(x2d, weight_packed, bias, epilogue: str = "none", gamma=No
     """Same contract as linear_f32_split for problems with few output tiles: split-K with a deterministic reduction that
     also applies bias and epilogue."""
     m, k = x2d.shape
-    if weight_packed.dtype != torch.bfloat16 or weight_packed.dim() != 6 or weight_packed.shape[1] * 16 != k:
+    if weight_packed.dtype != torch.bfloat16 or weight_packed.dim() != 6 or weight_packed.shape[1] * 16 != k:   # six-product only
         raise ValueError("weight_packed must be the contiguous bf16 tensor from pack_weight_bf16x3 with matching K")
     n = weight_packed.shape[0] * 128
     out = torch.empty((m, n), dtype=torch.float32, device=x2d.device)
@@ -975,7 +992,7 @@ def linear_f32_splitk(x2d, weight_packed, bias, epilogue: str = "none", gamma=No
     args = (_dev(x2d, torch.float32, "x"), weight_packed.data_ptr(), _dev(bias, torch.float32, "bias") if bias is not None else None,
             _dev(gamma, torch.float32, "gamma") if gamma is not None else None,
             _dev(resid, torch.float32, "resid") if resid is not None else None, out.data_ptr(), m, n, k,
-            {"none": 0, "gelu": 1, "scale_res": 2}[epilogue], ws.data_ptr(), nbytes, _stream())
+            _EPILOGUES[epilogue], ws.data_ptr(), nbytes, _stream())
     nb = 4.0 * m * k + 6.0 * n * k + 4.0 * m * n * (2 if epilogue == "scale_res" else 1)
     _check(_timed("linear_splitk", 2.0 * m * n * k, lambda: load().gdrnpp_linear_f32_splitk(*args), nb), "gdrnpp_linear_f32_splitk")
     return out
@@ -1008,14 +1025,8 @@ def conv2d_f32_split(x_cl, weight_packed, bias, kh: int, kw: int, stride: int, p
                      x3_slot: int = 0):
     """KHxKW / stride / zero-pad convolution of a channels_last tensor [N,Cin,H,W] on the bf16 matrix cores (fp32-accurate
     split GEMM, implicit im2col) -> channels_last [N,Cout,OH,OW]."""
-    n, cin, h, w = x_cl.shape
-    if not x_cl.is_contiguous(memory_format=torch.channels_last) or x_cl.dtype != torch.float32 or not x_cl.is_cuda:
-        raise ValueError("conv2d_f32_split expects a float32 channels_last device tensor")
-    fp16x2 = weight_packed.dtype == torch.float16
-    if weight_packed.dtype not in (torch.bfloat16, torch.float16) or weight_packed.dim() != 6 \
-            or weight_packed.shape[1] * 16 != kh * kw * cin or weight_packed.shape[2] != (2 if fp16x2 else 3):
-        raise ValueError("weight_packed must come from pack_conv_weight_bf16x3 / pack_conv_weight_f16x2 with matching Cin and kernel size")
-    cout = weight_packed.shape[0] * 128
+    n, cin, h, w = _channels_last_f32(x_cl, "conv2d_f32_split")
+    cout, fp16x2 = _packed_weight(weight_packed, kh * kw * cin, "weight_packed must come from pack_conv_weight_bf16x3 / pack_conv_weight_f16x2 with matching Cin and kernel size")
     oh, ow = (h + 2 * pad - kh) // stride + 1, (w + 2 * pad - kw) // stride + 1
     out = torch.empty((n, cout, oh, ow), dtype=torch.float32, device=x_cl.device, memory_format=torch.channels_last)
     if fp16x2:
@@ -1049,9 +1060,7 @@ def conv3x3_f32_split(x_cl, weight_packed, bias, gelu: bool = False, x3_slot: in
 
 def bias_act_nhwc_(x_cl, bias, resid=None, relu: bool = True):
     """In place: x = act(x + bias[c] (+ resid)) on a channels_last float32 tensor [N,C,H,W] (C % 4 == 0)."""
-    n, c, h, w = x_cl.shape
-    if not x_cl.is_contiguous(memory_format=torch.channels_last) or x_cl.dtype != torch.float32 or not x_cl.is_cuda:
-        raise ValueError("bias_act_nhwc_ expects a float32 channels_last device tensor")
+    n, c, h, w = _channels_last_f32(x_cl, "bias_act_nhwc_")
     if resid is not None and (resid.shape != x_cl.shape or not resid.is_contiguous(memory_format=torch.channels_last)
                               or resid.dtype != torch.float32 or resid.device != x_cl.device):
         raise ValueError("resid must match x (float32, channels_last, same device)")
@@ -1073,16 +1082,22 @@ def pack_deconv_weight_f16x2(weight):
     return pack_weight_f16x2(weight.detach().permute(2, 3, 1, 0).reshape(kh * kw * cout, cin).contiguous())
 
 
-def conv_transpose2d_f32_split(x_cl, weight_packed, bias, ks: int, stride: int, pad: int, out_pad: int, x3_slot: int = 0):
-    """nn.ConvTranspose2d of a channels_last tensor [N,Cin,H,W] as split GEMM + col2im gather -> channels_last
-    [N,Cout,OH,OW] (``weight_packed`` from pack_deconv_weight_bf16x3)."""
-    n, cin, h, w = x_cl.shape
-    if not x_cl.is_contiguous(memory_format=torch.channels_last) or x_cl.dtype != torch.float32 or not x_cl.is_cuda:
-        raise ValueError("conv_transpose2d_f32_split expects a float32 channels_last device tensor")
+def _deconv_cols(x_cl, weight_packed, ks: int, stride: int, pad: int, out_pad: int, x3_slot: int, what: str):
+    """First half of a transposed convolution: the GEMM into ``cols`` [N*H*W, KS*KS*Cout] and the empty channels_last result
+    the col2im gather fills; returns (cols, y, cout, oh, ow)."""
+    n, cin, h, w = _channels_last_f32(x_cl, what)
     cout = weight_packed.shape[0] * 128 // (ks * ks)
     cols = linear_f32_split(x_cl.permute(0, 2, 3, 1).reshape(n * h * w, cin), weight_packed, None, _kind="deconv", x3_slot=x3_slot)
     oh, ow = (h - 1) * stride - 2 * pad + ks + out_pad, (w - 1) * stride - 2 * pad + ks + out_pad
     y = torch.empty((n, cout, oh, ow), dtype=torch.float32, device=x_cl.device, memory_format=torch.channels_last)
+    return cols, y, cout, oh, ow
+
+
+def conv_transpose2d_f32_split(x_cl, weight_packed, bias, ks: int, stride: int, pad: int, out_pad: int, x3_slot: int = 0):
+    """nn.ConvTranspose2d of a channels_last tensor [N,Cin,H,W] as split GEMM + col2im gather -> channels_last
+    [N,Cout,OH,OW] (``weight_packed`` from pack_deconv_weight_bf16x3)."""
+    n, _, h, w = x_cl.shape
+    cols, y, cout, _, _ = _deconv_cols(x_cl, weight_packed, ks, stride, pad, out_pad, x3_slot, "conv_transpose2d_f32_split")
     _check(load().gdrnpp_deconv_col2im_nhwc(cols.data_ptr(), _dev(bias, torch.float32, "bias") if bias is not None else None,
                                             y.data_ptr(), n, h, w, cout, ks, stride, pad, out_pad, _stream()),
            "gdrnpp_deconv_col2im_nhwc")
@@ -1094,13 +1109,8 @@ def conv_transpose2d_groupnorm_act(x_cl, weight_packed, bias, ks: int, stride: i
     """nn.ConvTranspose2d -> GroupNorm(groups) [-> GELU] of a channels_last tensor: split GEMM, then the col2im gather leaves the
     GroupNorm partial sums (``gdrnpp_deconv_col2im_gn_nhwc``) and the norm is one more pass (``gdrnpp_groupnorm_apply_nhwc``) —
     bitwise the result of conv_transpose2d_f32_split + groupnorm_act, one launch fewer."""
-    n, cin, h, w = x_cl.shape
-    if not x_cl.is_contiguous(memory_format=torch.channels_last) or x_cl.dtype != torch.float32 or not x_cl.is_cuda:
-        raise ValueError("conv_transpose2d_groupnorm_act expects a float32 channels_last device tensor")
-    cout = weight_packed.shape[0] * 128 // (ks * ks)
-    cols = linear_f32_split(x_cl.permute(0, 2, 3, 1).reshape(n * h * w, cin), weight_packed, None, _kind="deconv", x3_slot=x3_slot)
-    oh, ow = (h - 1) * stride - 2 * pad + ks + out_pad, (w - 1) * stride - 2 * pad + ks + out_pad
-    y = torch.empty((n, cout, oh, ow), dtype=torch.float32, device=x_cl.device, memory_format=torch.channels_last)
+    n, _, h, w = x_cl.shape
+    cols, y, cout, oh, ow = _deconv_cols(x_cl, weight_packed, ks, stride, pad, out_pad, x3_slot, "conv_transpose2d_groupnorm_act")
     nbytes = load().gdrnpp_groupnorm_workspace_bytes(n, oh * ow, groups)
     P = nbytes // (16 * n * groups)
     part = torch.empty((n, P, groups, 2), dtype=torch.float64, device=x_cl.device)
@@ -1197,14 +1207,8 @@ def conv3x3_groupnorm_act(x_cl, weight_packed, bias, gamma, beta, groups: int, e
     leaves the GroupNorm partial sums, the norm is one more pass (``gdrnpp_conv3x3_f32_split_gnstats`` +
     ``gdrnpp_groupnorm_apply_nhwc``).  Returns None when the shape is outside the fused form (H*W % 256, 8 channels
     per group): the caller then runs the two layers separately."""
-    n, cin, h, w = x_cl.shape
-    if not x_cl.is_contiguous(memory_format=torch.channels_last) or x_cl.dtype != torch.float32 or not x_cl.is_cuda:
-        raise ValueError("conv3x3_groupnorm_act expects a float32 channels_last device tensor")
-    fp16x2 = weight_packed.dtype == torch.float16
-    if weight_packed.dtype not in (torch.bfloat16, torch.float16) or weight_packed.dim() != 6 \
-            or weight_packed.shape[1] * 16 != 9 * cin or weight_packed.shape[2] != (2 if fp16x2 else 3):
-        raise ValueError("weight_packed must come from pack_conv_weight_bf16x3 / pack_conv_weight_f16x2 with matching Cin")
-    cout = weight_packed.shape[0] * 128
+    n, cin, h, w = _channels_last_f32(x_cl, "conv3x3_groupnorm_act")
+    cout, fp16x2 = _packed_weight(weight_packed, 9 * cin, "weight_packed must come from pack_conv_weight_bf16x3 / pack_conv_weight_f16x2 with matching Cin")
     P = load().gdrnpp_conv3x3_gnstats_partials(h, w)
     if P <= 0 or cout != 8 * groups or (n * h * w // 256) * (cout // 128) < 256:   # below: the 128x128-tile kernels are faster
         return None
