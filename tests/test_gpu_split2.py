@@ -255,16 +255,16 @@ def test_overflow_raises_the_nonfinite_bit(hip):
 
 @pytest.fixture()
 def three_products(hip):
-    from gdrnpp_bop2022_amd.gdrn_modeling import engine, hip_layers
+    from gdrnpp_bop2022_amd.gdrn_modeling import engine, hip_layers, range_check
     old_products, old_tiles = hip_layers.gemm_products(), hip.SPLIT2_MIN_TILES
     hip_layers.set_gemm_products(3)
     hip_layers.reset_x3_demotions()
-    engine._X3_OVERFLOW_STEPS = 0
+    range_check._X3_OVERFLOW_STEPS = 0
     yield hip_layers
     hip_layers.set_gemm_products(old_products)          # what the session ran before (the library default: 3)
     hip.SPLIT2_MIN_TILES = old_tiles
     hip_layers.reset_x3_demotions()
-    engine._X3_OVERFLOW_STEPS = 0
+    range_check._X3_OVERFLOW_STEPS = 0
 
 
 @pytest.mark.parametrize("ds", ["ycbv", "ycbvso"])
@@ -334,7 +334,7 @@ def test_headline_batch_three_vs_six_products_and_overflow_retry(hip, three_prod
     """128 ROIs (the shapes bench.py times): maps / poses of the two modes agree far inside the 1e-4 tolerance and no layer leaves
     the range; with an fc1 bias that pushes the hidden tensor beyond the fp16 range the consuming fc2 raises NONFINITE,
     engine.inference_step returns the six-product result and from then on runs THAT layer on six products (no second repeat)."""
-    from gdrnpp_bop2022_amd.gdrn_modeling import engine
+    from gdrnpp_bop2022_amd.gdrn_modeling import engine, range_check
 
     hip_layers = three_products
     model, post, batch, x, kw = _headline_model_and_batch(hip)
@@ -358,14 +358,14 @@ def test_headline_batch_three_vs_six_products_and_overflow_retry(hip, three_prod
         got = engine.inference_step(model, post, batch)  # ... and the step repeats itself with six products
     assert hip_layers.gemm_products() == 3 and hip.split2_range_words() == {} and engine.range_reruns() == reruns + 1
     assert torch.isfinite(got).all() and torch.equal(got, want)
-    assert list(hip_layers.x3_demoted()) == [min(words)] and engine._X3_OVERFLOW_STEPS == 1     # the first layer that saw the inf
+    assert list(hip_layers.x3_demoted()) == [min(words)] and range_check._X3_OVERFLOW_STEPS == 1     # the first layer that saw the inf
     with torch.no_grad():
         again = engine.inference_step(model, post, batch)               # that fc2 now runs on six products: nothing to repeat
     assert engine.range_reruns() == reruns + 1 and torch.isfinite(again).all()
     assert (again[:, :12] - want[:, :12]).abs().max().item() <= 1e-3     # (a 9e4 outlier in front of a LayerNorm: sane, not parity)
     # the same through a captured hipGraph built from scratch: the eager warm-up step trips, demotes, and the capture holds the mix
     hip_layers.reset_x3_demotions()
-    engine._X3_OVERFLOW_STEPS = 0
+    range_check._X3_OVERFLOW_STEPS = 0
     with torch.no_grad():
         g = engine.GraphedInference(model, post, batch, warmup=1)
         assert g.uses_x3 and g.captures == 1 and len(hip_layers.x3_demoted()) == 1

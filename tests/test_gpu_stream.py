@@ -8,7 +8,7 @@ import pytest
 import torch
 
 from gdrnpp_bop2022_amd import hip_lib, synthetic as S
-from gdrnpp_bop2022_amd.gdrn_modeling import engine
+from gdrnpp_bop2022_amd.gdrn_modeling import engine, range_check
 from gdrnpp_bop2022_amd.gdrn_modeling.config import get_cfg
 from gdrnpp_bop2022_amd.gdrn_modeling.GDRN_double_mask import build_model_optimizer
 
@@ -171,4 +171,4 @@ def test_a_flagged_step_inside_the_scheduler_is_repeated_with_six_products(setup
             blk.norm.bias.copy_(b_ok)
         hip_layers.set_gemm_products(old)
         hip_layers.reset_x3_demotions()
-        engine._X3_OVERFLOW_STEPS = 0
+        range_check._X3_OVERFLOW_STEPS = 0

@@ -8,7 +8,7 @@ import pytest
 import torch
 
 from gdrnpp_bop2022_amd import hip_lib, synthetic as S
-from gdrnpp_bop2022_amd.gdrn_modeling import engine, hip_layers
+from gdrnpp_bop2022_amd.gdrn_modeling import engine, hip_layers, range_check, streams
 from gdrnpp_bop2022_amd.gdrn_modeling.config import get_cfg
 from gdrnpp_bop2022_amd.gdrn_modeling.GDRN_double_mask import build_model_optimizer
 
@@ -115,7 +115,7 @@ def test_handles_belong_to_their_stream_and_a_flagged_step_is_repeated_there(set
         want = engine.inference_step(model, post, batches[0]).clone()
     dealer = engine.StepStreams(2)
     reruns0 = engine.range_reruns()
-    step = torch.no_grad()(engine._step_closure(model, post, batches[0], batches[0]["roi_id"]))
+    step = torch.no_grad()(streams._step_closure(model, post, batches[0], batches[0]["roi_id"]))
     calls = []
 
     def flagged_step():
@@ -145,7 +145,7 @@ def test_handles_belong_to_their_stream_and_a_flagged_step_is_repeated_there(set
         assert torch.equal(h.result(), one[1]) and not h.reran
     finally:
         hip_layers.reset_x3_demotions()
-        engine._X3_OVERFLOW_STEPS = 0
+        range_check._X3_OVERFLOW_STEPS = 0
 
 
 @pytest.mark.parametrize("host_fed", [False, True])
@@ -319,7 +319,7 @@ def test_a_graph_on_its_own_stream_that_leaves_the_range_is_repeated_there_and_c
             blk.norm.weight.copy_(w_ok)
             blk.norm.bias.copy_(b_ok)
         hip_layers.reset_x3_demotions()
-        engine._X3_OVERFLOW_STEPS = 0
+        range_check._X3_OVERFLOW_STEPS = 0
 
 
 def test_host_fed_images_report_when_their_pinned_source_may_be_overwritten(setup):
