@@ -14,11 +14,16 @@ S = L.NhwcSlice
 _MAX_PLANS = 4
 
 
-def supported(model, x) -> bool:
-    """[B,3,H,W] with H, W multiples of the coarsest stride (what the module path's concatenations need as well), three levels."""
+def supported_size(model, H: int, W: int) -> bool:
+    """H, W multiples of the coarsest stride (what the module path's concatenations need as well), three levels."""
     head = model.head
-    return (x.dim() == 4 and x.shape[1] == 3 and x.shape[2] % 32 == 0 and x.shape[3] % 32 == 0 and x.shape[2] > 0 and x.shape[3] > 0
+    return (H % 32 == 0 and W % 32 == 0 and H > 0 and W > 0
             and list(head.strides) == [8, 16, 32] and len(head.stems) == 3 and hasattr(model.backbone, "C3_n4"))
+
+
+def supported(model, x) -> bool:
+    """[B,3,H,W] of a ``supported_size``."""
+    return x.dim() == 4 and x.shape[1] == 3 and supported_size(model, x.shape[2], x.shape[3])
 
 
 class _Buffers:
@@ -49,22 +54,43 @@ def _csp(layer, src, dst, buf, name, h, w):
     return _conv(layer.conv3, S(cat), dst)
 
 
-def forward(model, x):
-    b, _, H, W = x.shape
+def _plan(model, b, H, W, device) -> _Buffers:
     plans = model.__dict__.setdefault("_gdrnpp_yolox_buffers", {})
-    key = (b, H, W, x.device, hip_lib._stream())
+    key = (b, H, W, device, hip_lib._stream())
     buf = plans.get(key)
     if buf is None:
         if len(plans) >= _MAX_PLANS:
             plans.clear()
-        buf = plans[key] = _Buffers(b, x.device)
+        buf = plans[key] = _Buffers(b, device)
+    return buf
+
+
+def focus_buffer(model, b: int, H: int, W: int, device) -> torch.Tensor:
+    """The Focus stem's input f32[b,H/2,W/2,12] of the plan for a [b,3,H,W] image on the current stream: a producer that writes
+    the Focus layout itself (``hip_lib.yolox_letterbox(..., focus=True)``) fills it and calls ``forward(model, None, focus=...)``."""
+    return _plan(model, b, H, W, device)("focus", H // 2, W // 2, 12)
+
+
+def forward(model, x, focus=None):
+    """``x`` f32[B,3,H,W] — or ``x=None`` and ``focus`` = the filled ``focus_buffer``: the space-to-depth launch is skipped (one
+    write and one read of the image less)."""
+    if focus is not None:
+        b, h2, w2, _ = focus.shape
+        H, W, device = 2 * h2, 2 * w2, focus.device
+        buf = _plan(model, b, H, W, device)
+        if x is not None or focus is not buf("focus", h2, w2, 12):
+            raise RuntimeError("hip_forward.forward: focus must be the plan's own focus_buffer (same stream), with x=None")
+    else:
+        b, _, H, W = x.shape
+        device = x.device
+        buf = _plan(model, b, H, W, device)
     fpn, head = model.backbone, model.head
     bb = fpn.backbone
     h2, w2, h4, w4, h8, w8, h16, w16, h32, w32 = H // 2, W // 2, H // 4, W // 4, H // 8, W // 8, H // 16, W // 16, H // 32, W // 32
     c3, c4, c5 = (m.conv.in_channels for m in head.stems)
 
     # CSPDarknet; dark3 / dark4 land in the second halves of the top-down concatenations
-    foc = L.focus_slice(x, S(buf("focus", h2, w2, 12)))
+    foc = S(focus) if focus is not None else L.focus_slice(x, S(buf("focus", h2, w2, 12)))
     stem = _conv(bb.stem.conv, foc, S(buf("stem", h2, w2, bb.stem.conv.conv.out_channels)))
     d2a = _conv(bb.dark2[0], stem, S(buf("d2a", h4, w4, bb.dark2[0].conv.out_channels)))
     d2 = _csp(bb.dark2[1], d2a, S(buf("d2", h4, w4, d2a.c)), buf, "d2", h4, w4)
@@ -104,7 +130,7 @@ def forward(model, x):
     head.hw = [(h, w) for _, h, w in levels]
     A = sum(h * w for _, h, w in levels)
     nc = head.num_classes
-    det = torch.empty((b, A, 5 + nc), dtype=torch.float32, device=x.device)
+    det = torch.empty((b, A, 5 + nc), dtype=torch.float32, device=device)
     row0 = 0
     for k, (feat, h, w) in enumerate(levels):
         ch = head.stems[k].conv.out_channels

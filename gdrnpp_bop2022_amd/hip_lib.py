@@ -97,6 +97,10 @@ SIGNATURES = {
                                          c_int, c_int, c_int, c_int, c_int, c_int, c_float, _P]),
     "gdrnpp_yolox_focus": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
     "gdrnpp_spp_maxpool_5_9_13": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
+    "gdrnpp_yolox_letterbox": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, c_int, c_int, c_int, c_int, c_int, _P]),
+    "gdrnpp_rois_from_dets_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "gdrnpp_rois_from_dets": (c_int, [_P, _P, c_int, c_int, c_int, c_float, c_int, c_int, c_double, c_int, _P, c_int, _P, c_double, c_int,
+                                      c_int, _P, _P, _P, _P, c_size_t, _P]),
     "gdrnpp_upsample_nearest2x_slice": (c_int, [_P, c_int, c_int, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
     "gdrnpp_paste_masks_rle": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_float, _P, _P, c_int, _P]),
     "gdrnpp_flow_forward": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, _P]),
@@ -1326,6 +1330,92 @@ def upsample_nearest2x_slice(x, x_off: int, y, y_off: int, c: int):
     _check(load().gdrnpp_upsample_nearest2x_slice(_nhwc_buf(x, "x"), ldx, x_off, _nhwc_buf(y, "y"), y.shape[-1], y_off, b, h, w, c,
                                                   _stream()), "gdrnpp_upsample_nearest2x_slice")
     return y
+
+
+# ---- the detector's two ends (csrc/yolox_pre.hip) -----------------------------------------------------------------------------
+def letterbox_sizes(H: int, W: int, test_size) -> tuple:
+    """``preproc``'s size arithmetic (det/yolox/data/data_augment.py:167-173) with Python floats, as the reference does it:
+    -> (r, rh, rw) = (min(Ht / H, Wt / W), int(H * r), int(W * r))."""
+    r = min(test_size[0] / H, test_size[1] / W)
+    return r, int(H * r), int(W * r)
+
+
+def yolox_letterbox(images_u8, test_size=(640, 640), out=None, y_off: int = 0, focus: bool = False, legacy: bool = False):
+    """``gdrnpp_yolox_letterbox``: images u8[B,H,W,3] (BGR, device) -> (the letterboxed float image, r).  ``focus=False``:
+    f32[B,3,Ht,Wt], what ``YOLOX.forward`` takes.  ``focus=True``: the Focus stem's 12 channels at ``y_off`` of
+    f32[B,Ht/2,Wt/2,ld] (``out``, or a fresh 12-channel buffer).  ``ValTransform(legacy=True)`` is not implemented."""
+    if legacy:
+        raise NotImplementedError("yolox_letterbox: legacy=True (RGB flip and ImageNet normalisation) is not implemented")
+    if images_u8.dim() != 4 or images_u8.shape[-1] != 3:
+        raise RuntimeError(f"yolox_letterbox: images must be u8[B,H,W,3], got {tuple(images_u8.shape)}")
+    b, H, W, _ = images_u8.shape
+    ht, wt = int(test_size[0]), int(test_size[1])
+    r, rh, rw = letterbox_sizes(H, W, (ht, wt))
+    if out is None:
+        shape = (b, ht // 2, wt // 2, 12) if focus else (b, 3, ht, wt)
+        out = torch.empty(shape, dtype=torch.float32, device=images_u8.device)
+    want = (b, ht // 2, wt // 2) if focus else (b, 3, ht, wt)
+    if tuple(out.shape[:3] if focus else out.shape) != want:
+        raise RuntimeError(f"yolox_letterbox: out must be {want + (('ld',) if focus else ())}, got {tuple(out.shape)}")
+    _check(load().gdrnpp_yolox_letterbox(_dev(images_u8, torch.uint8, "images"), b, H, W, rh, rw, _nhwc_buf(out, "out"), ht, wt,
+                                         1 if focus else 0, out.shape[-1] if focus else 0, int(y_off) if focus else 0, _stream()),
+           "gdrnpp_yolox_letterbox")
+    return out, r
+
+
+class gdrnpp_roi_table(ctypes.Structure):
+    _fields_ = [(k, c_void_p) for k in ("center64", "scale64", "im_idx", "roi_cls", "roi_cam", "roi_center", "roi_wh", "scale",
+                                        "resize_ratio", "roi_extent", "score", "roi_id")]
+
+
+# column -> (torch dtype, trailing shape): the keys and dtypes of roi_stream.roi_host_arrays, in its order
+ROI_TABLE_COLUMNS = {
+    "center64": (torch.float64, (2,)), "scale64": (torch.float64, ()), "im_idx": (torch.int32, ()), "roi_cls": (torch.int64, ()),
+    "roi_cam": (torch.float32, (3, 3)), "roi_center": (torch.float32, (2,)), "roi_wh": (torch.float32, (2,)),
+    "scale": (torch.float32, ()), "resize_ratio": (torch.float32, ()), "roi_extent": (torch.float32, (3,)),
+    "score": (torch.float32, ()), "roi_id": (torch.int32, ()),
+}
+
+
+def roi_table(cap: int, device) -> dict:
+    """An empty ROI table of ``cap`` rows: one device allocation, every column a 16-byte aligned typed view of it."""
+    sizes, total = {}, 0
+    for k, (dt, tail) in ROI_TABLE_COLUMNS.items():
+        n = cap * torch.empty((), dtype=dt).element_size()
+        for t in tail:
+            n *= t
+        total = (total + 15) & ~15
+        sizes[k] = (total, n)
+        total += n
+    raw = torch.zeros((total,), dtype=torch.uint8, device=device)
+    return {k: raw[off:off + n].view(ROI_TABLE_COLUMNS[k][0]).reshape((cap,) + ROI_TABLE_COLUMNS[k][1]) for k, (off, n) in sizes.items()}
+
+
+def rois_from_dets(dets, count, ratio: float, H: int, W: int, cam, extents, dzi_pad_scale: float = 1.5, out_res: int = 64,
+                   score_thr: float = 0.0, top_k_per_obj: int = 0, cap: int = 256, table: dict | None = None, counts=None):
+    """``gdrnpp_rois_from_dets``: ``yolox_postprocess`` output -> (table, counts).  ``table`` = {column: tensor of ``cap`` rows}
+    (``roi_table``; the keys and dtypes of ``roi_stream.roi_host_arrays``), ``counts`` i32[1 + B] = (n_rois, per-image counts);
+    rows from n_rois on are not written.  cam f32[3,3] or f32[B,3,3], extents f32[C,3], all on the device."""
+    b, max_det, seven = dets.shape
+    if seven != 7 or count.numel() != b:
+        raise RuntimeError(f"rois_from_dets: dets f32[B,max_det,7] and count i32[B], got {tuple(dets.shape)} and {tuple(count.shape)}")
+    if cam.numel() not in (9, 9 * b) or extents.dim() != 2 or extents.shape[1] != 3:
+        raise RuntimeError(f"rois_from_dets: cam f32[3,3] or f32[B,3,3], extents f32[C,3], got {tuple(cam.shape)} and {tuple(extents.shape)}")
+    table = table if table is not None else roi_table(cap, dets.device)
+    if any(table[k].shape[0] != cap for k in ROI_TABLE_COLUMNS):
+        raise RuntimeError(f"rois_from_dets: every table column must hold cap = {cap} rows")
+    counts = counts if counts is not None else torch.zeros((1 + b,), dtype=torch.int32, device=dets.device)
+    lib = load()
+    nbytes = lib.gdrnpp_rois_from_dets_workspace_bytes(b, max_det)
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=dets.device)
+    ctab = gdrnpp_roi_table(**{k: _dev(table[k], ROI_TABLE_COLUMNS[k][0], k) for k in ROI_TABLE_COLUMNS})
+    cnt = _dev(counts, torch.int32, "counts")
+    _check(lib.gdrnpp_rois_from_dets(
+        _dev(dets, torch.float32, "dets"), _dev(count, torch.int32, "count"), b, max_det, extents.shape[0], float(ratio), int(H), int(W),
+        float(dzi_pad_scale), int(out_res), _dev(cam, torch.float32, "cam"), 1 if cam.dim() == 3 else 0,
+        _dev(extents, torch.float32, "extents"), float(score_thr), int(top_k_per_obj), int(cap), ctypes.byref(ctab), cnt, cnt + 4,
+        ws.data_ptr(), nbytes, _stream()), "gdrnpp_rois_from_dets")
+    return table, counts
 
 
 def paste_masks_rle(mask_probs, boxes_xyxy, im_h: int, im_w: int, threshold: float = 0.5, max_runs: int = 4096):

@@ -612,6 +612,47 @@ int gdrnpp_spp_maxpool_5_9_13(float* buf, int ld, int off, int C, int B, int H, 
 int gdrnpp_upsample_nearest2x_slice(const float* x, int ldx, int x_off, float* y, int ldy, int y_off, int B, int h, int w, int C,
                                     void* stream);
 
+/* ---- the detector's two ends (csrc/yolox_pre.hip) ----
+ * gdrnpp_yolox_letterbox: `preproc` of det/yolox/data/data_augment.py:161-177 as ValTransform(legacy=False) uses it.
+ * images_u8 u8[B,H,W,3] (BGR, rows of 3 W bytes, no alignment assumed) -> cv2.resize(INTER_LINEAR) to rh x rw placed top-left
+ * on a canvas of 114, as float.  rh = int(H r), rw = int(W r) with r = min(Ht / H, Wt / W) are the CALLER's arithmetic (Python
+ * floats in the reference); the kernel derives no size.  The resize restates OpenCV's 8-bit path (11-bit coefficients, int
+ * horizontal pass, the vertical pass's shifts and rounding, border clamps; rh x rw == H x W is a copy, an exact 2:1 reduction in
+ * both axes the area mean).  focus = 0: out f32[B,3,Ht,Wt] (ldy, y_off ignored).  focus = 1: out f32[B,Ht/2,Wt/2,ldy], the 12
+ * channels from y_off on exactly as gdrnpp_yolox_focus of the NCHW form writes them (y_off, ldy multiples of 4).
+ * Ht, Wt positive multiples of 32, or GDRNPP_EINVAL and no launch. */
+int gdrnpp_yolox_letterbox(const unsigned char* images_u8, int B, int H, int W, int rh, int rw, float* out, int Ht, int Wt, int focus,
+                           int ldy, int y_off, void* stream);
+
+/* gdrnpp_rois_from_dets: gdrnpp_yolox_postprocess output -> the per-ROI table of the pose path, compacted over the batch.
+ * dets f32[B,max_det,7], count i32[B] (values above max_det are clamped), max_det <= 1024.  A detection is dropped when
+ * obj_conf * class_conf < score_thr or its class lies outside [0, num_classes); with top_k_per_obj > 0 only the top_k_per_obj
+ * highest scores per (image, class) stay (ties: the earlier row) and an image's ROIs come in class order, then descending
+ * score; with 0 they keep their order.  Boxes are divided by `ratio` in float, then centre, (bw, bh) clamped to >= 1,
+ * scale = min(max(bw, bh) * dzi_pad_scale, max(H, W)) and resize_ratio = out_res / scale in double.  cam f32[3,3]
+ * (cam_per_image = 0) or f32[B,3,3]; extents f32[num_classes,3].  Every column of `table` holds `cap` rows; ROIs beyond cap are
+ * dropped from the tail.  n_rois i32[1] = rows written, per_image i32[B] = rows of every image; roi_id = the row's index.
+ * The struct itself is host memory, its members are device pointers. */
+typedef struct gdrnpp_roi_table {
+  double* center64;    /* [cap,2] */
+  double* scale64;     /* [cap] */
+  int* im_idx;         /* [cap] */
+  long long* roi_cls;  /* [cap] */
+  float* roi_cam;      /* [cap,3,3] */
+  float* roi_center;   /* [cap,2] */
+  float* roi_wh;       /* [cap,2] */
+  float* scale;        /* [cap] */
+  float* resize_ratio; /* [cap] */
+  float* roi_extent;   /* [cap,3] */
+  float* score;        /* [cap] */
+  int* roi_id;         /* [cap] */
+} gdrnpp_roi_table;
+size_t gdrnpp_rois_from_dets_workspace_bytes(int B, int max_det);
+int gdrnpp_rois_from_dets(const float* dets, const int* count, int B, int max_det, int num_classes, float ratio, int H, int W,
+                          double dzi_pad_scale, int out_res, const float* cam, int cam_per_image, const float* extents,
+                          double score_thr, int top_k_per_obj, int cap, const gdrnpp_roi_table* table, int* n_rois, int* per_image,
+                          void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- instance masks for SAVE_RESULTS_ONLY — gdrn_evaluator.py:914-945:
  * detectron2 paste_masks_in_image(mask_probs, boxes, (im_H, im_W), threshold) + the uncompressed COCO run-length
  * encoding of lib/utils/mask_utils.py:96-109, fused: the full-size masks are never materialised.
