@@ -32,7 +32,7 @@
 //   On either bit the host side re-runs the step in the six-product form and keeps the flagged layer there
 //   (engine.run_with_range_check) — never silently wrong, on either side of the range, on every launch;
 //   * weights: gdrnpp_pack_weight_f16x2 applies the same per-row test to the scaled weight rows (trailer word 3); such a layer
-//     is not eligible for this form (hip_layers._packed_weight).
+//     is not eligible for this form (x3_policy.six_product_weight).
 //
 // Kernel: the software-pipelined LDS-DMA kernel of gemm_split_pipe.hip with 24 instead of 48 MFMA slots per k-tile: block tile
 // 256x128x16, 4 waves stacked along M (2 x 4 MFMA tiles each), fp32 A by LDS-DMA into three 16 KB stages private to the waves,

@@ -7,7 +7,7 @@ Activation buffers are allocated once per (input shape, device, stream) and reus
 import torch
 
 from .... import hip_lib
-from ....gdrn_modeling import hip_layers as L
+from ....gdrn_modeling import slice_layers as L
 from .network_blocks import BaseConv
 
 S = L.NhwcSlice

@@ -23,7 +23,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .. import hip_lib
-from . import hip_layers
+from . import hip_layers, weight_cache, x3_policy
 from .backbones import create_backbone
 from .heads import HEADS
 
@@ -83,19 +83,19 @@ class GDRN_DoubleMask(nn.Module):
         if self.slice_classes is not None and self.xyz_out_dim == 3:
             self.register_buffer("_cls_rows", geo_head_net.class_channel_index(self.slice_classes), persistent=False)
         self._sliced_w = None  # cache of (weight[C,70,256], bias[C,70]) for eval
-        self._sliced_pk = {}    # cache of the packed, 128-row padded slices for the grouped split GEMM (hip_layers.cached)
+        self._sliced_pk = {}    # cache of the packed, 128-row padded slices for the grouped split GEMM (weight_cache.cached)
         self.fused_head_tail = True   # all-NHWC head tail on the HIP path (False: baddbmm + torch ops, for A/B)
 
     def load_state_dict(self, *args, **kwargs):
         res = super().load_state_dict(*args, **kwargs)
-        hip_layers.reset_x3_calibration()     # new weights, new activation scales: the layers look at their inputs again
+        x3_policy.reset()     # new weights, new activation scales: the layers look at their inputs again
         return res
 
     # ------------------------------------------------------------------------------------------
     def _sliced_out_layer(self, feat, roi_classes):
         """Per-ROI 70-channel output layer = the class-aware gather folded into the weights."""
         ol = self.geo_head_net.out_layer
-        tag = hip_layers.weight_tag(ol.weight, ol.bias)
+        tag = weight_cache.weight_tag(ol.weight, ol.bias)
         if self._sliced_w is None or self.training or self._sliced_w[0] != tag:
             w = ol.weight.view(ol.out_channels, -1)[self._cls_rows]  # [C,70,256]
             b = ol.bias[self._cls_rows]                               # [C,70]
@@ -142,8 +142,8 @@ class GDRN_DoubleMask(nn.Module):
             b128[:, :n70] = b
             return hip_lib.pack_weight_bf16x3(w128.view(C * 128, k).contiguous()), b128.contiguous(), n70
 
-        # (built with torch operators on the filling stream: hip_layers.cached drains it before another stream may hit the entry)
-        _, w_pk, b128, n70 = hip_layers.cached(self._sliced_pk, "pk", hip_layers.weight_tag(ol.weight, ol.bias), build, ol.weight)
+        # (built with torch operators on the filling stream: weight_cache.cached drains it before another stream may hit the entry)
+        _, w_pk, b128, n70 = weight_cache.cached(self._sliced_pk, "pk", weight_cache.weight_tag(ol.weight, ol.bias), build, ol.weight)
         bs, ch, h, wd = feat.shape
         feat = feat.contiguous(memory_format=torch.channels_last)
         x2d = feat.permute(0, 2, 3, 1).reshape(bs * h * wd, ch)     # a view of the NHWC memory

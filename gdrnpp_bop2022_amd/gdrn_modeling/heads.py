@@ -14,7 +14,7 @@ from __future__ import annotations
 import torch
 import torch.nn as nn
 
-from . import hip_layers
+from . import hip_layers, weight_cache, x3_policy
 from .. import hip_lib
 
 
@@ -303,7 +303,7 @@ class ConvPnPNet(nn.Module):
         """``x96_cl``: [B, 96, H, W] channels_last, channels 69..95 zero.  First convolution with its weight zero-padded to 96
         input channels on the implicit-GEMM split kernel, the rest as ``forward``."""
         c0 = self.features[0]
-        cache = c0.__dict__.setdefault("_gdrnpp_cache", {})
+        cache = weight_cache.module_cache(c0)
         def w96(w):
             out = torch.zeros((w.shape[0], 96, 3, 3), dtype=w.dtype, device=w.device)
             out[:, :69] = w
@@ -311,7 +311,7 @@ class ConvPnPNet(nn.Module):
 
         # always the six-product kernel: the input (metres, [0, 1) coordinates, softmax weights) is not a normalised tensor and sits
         # below the range of the three-product form at most pixels (its range word would say so on the first step)
-        w_pk = hip_layers._packed_weight(cache, "w96_pk", c0.weight, lambda w: hip_lib.pack_conv_weight_bf16x3(w96(w)))
+        w_pk = x3_policy.six_product_weight(cache, "w96_pk", c0.weight, lambda w: hip_lib.pack_conv_weight_bf16x3(w96(w)))
         x = hip_lib.conv2d_f32_split(x96_cl, w_pk, None, 3, 3, 2, 1)
         x = run_features(self.features[1:], x)
         return self._fc_tail(x, pose)

@@ -3,13 +3,18 @@
 or ``set_enabled(False)`` for A/B measurements).  Same math as the PyTorch operators, different summation order."""
 from __future__ import annotations
 
-import threading
-
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
 from .. import hip_lib
+# the names below are the owners' own objects: this module stays the namespace the package, the tests and the tools import.
+# Functions and classes only — an int or a dict re-exported here would be a stale copy the moment somebody assigns it.
+from .weight_cache import cache_fills, cached, module_cache, weight_tag  # noqa: F401
+from .x3_policy import (forced_gemm_products, gemm_products, is_demoted, note_launch, set_gemm_products, six_product_weight,  # noqa: F401
+                        split_weight)
+from .x3_policy import (demote as demote_x3, demoted as x3_demoted, launch_order as x3_launch_order,  # noqa: F401
+                        reset as reset_x3_demotions, slot as x3_slot, weight_for as x3_for)
 
 _ENABLED = True
 
@@ -25,43 +30,6 @@ def is_enabled() -> bool:
 
 def enabled_for(x: torch.Tensor) -> bool:
     return _ENABLED and x.is_cuda and x.dtype == torch.float32 and not torch.is_grad_enabled()
-
-
-def weight_tag(*tensors):
-    """Identity of parameter values for the eval-time derived-weight caches: storage, in-place version counter (bumped by
-    load_state_dict / optimiser steps) and device of every tensor the cached form is derived from."""
-    return tuple((t.data_ptr(), t._version, t.device) for t in tensors if t is not None)
-
-
-_CACHE_FILLS = 0
-
-
-def cache_fills() -> int:
-    """Derived-weight cache entries built so far by this process (tests: a warm model fills none)."""
-    return _CACHE_FILLS
-
-
-def cached(cache: dict, key: str, tag, build, on: torch.Tensor | None = None):
-    """``cache[key]`` = (tag, *build()) — rebuilt when ``tag`` (weight_tag of the parameters it derives from) changed.
-
-    Consecutive steps run on DIFFERENT compute streams (engine.StepStreams) and share these per-module entries, so a fill is
-    made safe for every stream, not just the one that happens to touch the layer first: the device is drained before the old
-    entry is dropped (its memory goes back to the filling stream's pool while another stream's step might still read it) and the
-    filling stream is drained before the new entry becomes visible (the pack kernels are complete when the next step, on the
-    other stream, hits the cache).  Two host waits per weight per process lifetime (+ one per load_state_dict); never inside a
-    hipGraph capture (engine.GraphedInference fills the caches with eager passes first; a fill under capture is captured as is)."""
-    global _CACHE_FILLS
-    hit = cache.get(key)
-    if hit is not None and hit[0] == tag:
-        return hit
-    gpu = on is not None and on.is_cuda and not torch.cuda.is_current_stream_capturing()
-    if gpu:
-        torch.cuda.synchronize(on.device)
-    hit = cache[key] = (tag,) + tuple(build())
-    if gpu:
-        torch.cuda.current_stream(on.device).synchronize()
-    _CACHE_FILLS += 1
-    return hit
 
 
 # ---- launches that are NOT this library's ------------------------------------------------------------------------------------
@@ -114,10 +82,13 @@ def _gn_ok(gn: nn.GroupNorm, x) -> bool:
             and x.shape[0] <= 65535 and gn.affine)
 
 
+def _exact_gelu_or_none(act: nn.Module | None) -> bool:
+    return act is None or (isinstance(act, nn.GELU) and getattr(act, "approximate", "none") == "none")
+
+
 def groupnorm_act(gn: nn.GroupNorm, act: nn.Module | None, x: torch.Tensor) -> torch.Tensor:
     """GroupNorm followed by ``act`` (fused when act is the exact GELU or None)."""
-    fusable_act = act is None or (isinstance(act, nn.GELU) and getattr(act, "approximate", "none") == "none")
-    if isinstance(gn, nn.GroupNorm) and _gn_ok(gn, x) and fusable_act:
+    if isinstance(gn, nn.GroupNorm) and _gn_ok(gn, x) and _exact_gelu_or_none(act):
         return hip_lib.groupnorm_act(_cl(x), gn.weight, gn.bias, gn.num_groups, gn.eps, gelu=act is not None)
     _fallback("groupnorm_act: " + type(gn).__name__ + " / activation outside the HIP kernel", x)
     x = gn(x)
@@ -143,7 +114,7 @@ def stem(conv: nn.Conv2d, ln: nn.LayerNorm, x: torch.Tensor) -> torch.Tensor:
             and conv.in_channels == 3 and conv.out_channels == 128 and conv.kernel_size == (4, 4) and conv.stride == (4, 4)
             and conv.padding == (0, 0) and conv.dilation == (1, 1) and conv.groups == 1 and ln.elementwise_affine
             and x.shape[2] % 4 == 0 and x.shape[3] % 16 == 0 and x.shape[3] <= 1024):
-        cache = conv.__dict__.setdefault("_gdrnpp_cache", {})
+        cache = module_cache(conv)
         # the kernel reads [co][ci][ky][kx]; the module may hold the weight channels_last
         hit = cached(cache, "w_oihw", weight_tag(conv.weight),
                      lambda: (conv.weight.detach().contiguous(memory_format=torch.contiguous_format).clone(),), conv.weight)
@@ -186,145 +157,6 @@ _LIBRARY_BELOW_TILES = 0    # A/B switch: blocks whose fc2 has fewer 128x128 out
                             # with a modelled number of K chunks and no block leaves this library
 
 
-# Partial products per fp32 product in the split GEMMs.
-#   3 (default): fp16x2 operand split, 22 significant operand bits, csrc/gemm_split2_pipe.hip — where the three-product kernels
-#      exist and pay: ConvNeXt MLPs, 3x3/1/1 convolutions and the transposed-convolution GEMM from 256 tiles of 256 x 128 on
-#      (batches of ~64 ROIs and more); every other layer and every smaller launch runs the six-product kernels.  Against fp64 the
-#      result is as close as the six-product form and closer than hipBLASLt's fp32 GEMM on the same operands (the fp32
-#      accumulation chain dominates all three; tools/split2_error_probe.py, profiles/r03y_split2_accuracy.txt), and the
-#      network outputs sit at the same 6e-6 from the reference's recorded forward as with six products or the vendor fp32
-#      kernels — for half the matrix-pipe work.  The form has a RANGE: every launch checks both sides of it on the device and
-#      reports in the range word of its layer (hip_lib.split2_range_words) — an activation beyond 65504, or an A row whose rms is
-#      below 2^-4 (low halves in the fp16 subnormals).  engine.run_with_range_check then repeats the step with 6 and keeps the
-#      flagged layers on 6 (demote_x3), so the outputs are fp32-level on EVERY batch, not on the ones somebody looked at.
-#   6: bf16x3 operand split, exact to 2^-26, everywhere.
-_GEMM_PRODUCTS = 3
-_TLS = threading.local()     # .forced: products forced for the calling host thread (the six-product repeat of a flagged step)
-
-
-def set_gemm_products(n: int) -> None:
-    global _GEMM_PRODUCTS
-    if n not in (3, 6):
-        raise ValueError(f"gemm products must be 6 (bf16x3) or 3 (fp16x2), got {n!r}")
-    _GEMM_PRODUCTS = int(n)
-
-
-def gemm_products() -> int:
-    forced = getattr(_TLS, "forced", None)
-    return _GEMM_PRODUCTS if forced is None else forced
-
-
-class forced_gemm_products:
-    """``with forced_gemm_products(6):`` — the calling host thread runs every split GEMM with that many products, other threads
-    (streams) keep the process setting."""
-
-    def __init__(self, n: int):
-        if n not in (3, 6):
-            raise ValueError(f"gemm products must be 6 or 3, got {n!r}")
-        self.n = n
-
-    def __enter__(self):
-        self.prev = getattr(_TLS, "forced", None)
-        _TLS.forced = self.n
-        return self
-
-    def __exit__(self, *exc):
-        _TLS.forced = self.prev
-        return False
-
-
-# ---- which layers run the three-product kernels ----------------------------------------------------------------------------
-# A layer = (the module's cache dict, a key).  It gets a range-word slot at its first three-product launch (slots follow launch
-# order within a model) and loses the three-product form for good — until the weights change — when a launch of it reported
-# rows below the range, or when it was the first layer of a step to overflow.
-_X3_NEXT_SLOT = 1            # slot 0: launches that name no layer
-_X3_DEMOTED = {}             # slot -> range word that demoted it
-_X3_EPOCH = 0                # bumped by reset_x3_demotions: slots handed out before it are forgotten
-_X3_LAUNCH_SEQ = {}          # slot -> sequence number of its latest three-product launch (process-wide monotonic counter)
-_X3_LAUNCH_COUNTER = 0
-
-
-def _note_x3_launch(*slots: int) -> None:
-    """Slots are handed out lazily (first eligible launch, any model, any batch size), so slot order is NOT launch order in
-    general; the order a step launched its layers in is what decides which of several overflowing layers was the first."""
-    global _X3_LAUNCH_COUNTER
-    for s_ in slots:
-        _X3_LAUNCH_COUNTER += 1
-        _X3_LAUNCH_SEQ[s_] = _X3_LAUNCH_COUNTER
-
-
-def x3_launch_order(slots) -> list:
-    """``slots`` sorted by the position of their latest three-product launch (slots never launched sort last, by number)."""
-    big = _X3_LAUNCH_COUNTER + 1
-    return sorted(slots, key=lambda s_: (_X3_LAUNCH_SEQ.get(s_, big), s_))
-
-
-def x3_slot(cache: dict, key: str) -> int:
-    global _X3_NEXT_SLOT
-    st = cache.get("x3_slot_" + key)
-    if st is None or st[0] != _X3_EPOCH:
-        st = cache["x3_slot_" + key] = (_X3_EPOCH, min(_X3_NEXT_SLOT, hip_lib.X3_SLOTS - 1))   # beyond the buffer: layers share the last slot
-        _X3_NEXT_SLOT += 1
-    return st[1]
-
-
-def demote_x3(words: dict) -> None:
-    """Keep the layers of ``words`` ({slot: range word}) on the six-product kernels from now on."""
-    for slot, word in words.items():
-        if slot > 0:
-            _X3_DEMOTED[int(slot)] = _X3_DEMOTED.get(int(slot), 0) | int(word)
-
-
-def x3_demoted() -> dict:
-    return dict(_X3_DEMOTED)
-
-
-def reset_x3_demotions() -> None:
-    """Forget the demotions and the slot numbering (new weights: new activation scales)."""
-    global _X3_EPOCH, _X3_NEXT_SLOT
-    _X3_EPOCH += 1
-    _X3_NEXT_SLOT = 1
-    _X3_DEMOTED.clear()
-    _X3_LAUNCH_SEQ.clear()
-
-
-reset_x3_calibration = reset_x3_demotions    # the name GDRN_DoubleMask.load_state_dict has always called
-
-
-def _use_x3(m: int, n: int, k_linear: int = 0) -> bool:
-    """Three-product kernel for an [m, n] result?  ``k_linear`` = K of a linear-form launch: its A operand is addressed with
-    32-bit lane offsets (m * K * 4 bytes < 4 GiB, ~480 ROIs at stage 0); beyond that the six-product kernels take over."""
-    return gemm_products() == 3 and hip_lib.split2_tiles_ok(m, n) and m * k_linear * 4 < (1 << 32)
-
-
-def x3_for(cache: dict, key: str, weight: torch.Tensor, pack3, m: int, n: int, k_linear: int = 0):
-    """-> (packed three-product weight or None, range-word slot).  None = this launch runs the six-product kernel: the shape is
-    outside the three-product kernels, the layer was demoted, or its weight has rows below the range (checked once per weight
-    by the pack kernel)."""
-    if not _use_x3(m, n, k_linear):
-        return None, 0
-    slot = x3_slot(cache, key)
-    if slot in _X3_DEMOTED:
-        return None, slot
-    def build():
-        packed = pack3(weight.detach())
-        return packed, hip_lib.packed_rows_in_range(packed)
-
-    hit = cached(cache, key + "_pk_x3", weight_tag(weight), build, weight)
-    if hit[2]:
-        _note_x3_launch(slot)
-    return (hit[1] if hit[2] else None), slot
-
-
-def _packed_weight(cache: dict, key: str, weight: torch.Tensor, pack6) -> torch.Tensor:
-    """Packed six-product split image of ``weight``, rebuilt when the weight changes."""
-    return cached(cache, key, weight_tag(weight), lambda: (pack6(weight.detach()),), weight)[1]
-
-
-def mlp_gemm() -> str:
-    return _MLP_GEMM
-
-
 def set_mlp_gemm(mode: str) -> None:
     global _MLP_GEMM
     if mode not in ("split", "torch"):
@@ -342,15 +174,6 @@ def set_library_below_tiles(n: int) -> None:
     of the split GEMM (one image's worth of ROIs leaves the deep stages with a handful of tiles)."""
     global _LIBRARY_BELOW_TILES
     _LIBRARY_BELOW_TILES = int(n)
-
-
-def set_fused_mlp(flag: bool) -> None:
-    """Backward-compatible switch: False = hipBLASLt + separate elementwise kernels."""
-    set_mlp_gemm("split" if flag else "torch")
-
-
-def _packed(linear: nn.Linear, cache: dict, key: str) -> torch.Tensor:
-    return _packed_weight(cache, key, linear.weight, hip_lib.pack_weight_bf16x3)
 
 
 _FUSED_MLP = True
@@ -375,7 +198,7 @@ def _fused_mlp_weights(mlp, cache: dict, m: int, c: int):
             and m * c * 4 < (1 << 32)):
         return None
     s1, s2 = x3_slot(cache, "fc1"), x3_slot(cache, "fc2")
-    if s1 in _X3_DEMOTED or s2 in _X3_DEMOTED:
+    if is_demoted(s1) or is_demoted(s2):
         return None
     def build():
         packed = hip_lib.pack_mlp_fused_f16x2(mlp.fc1.weight.detach().contiguous(), mlp.fc2.weight.detach().contiguous())
@@ -383,7 +206,7 @@ def _fused_mlp_weights(mlp, cache: dict, m: int, c: int):
 
     hit = cached(cache, "mlp_fused_pk", weight_tag(mlp.fc1.weight, mlp.fc2.weight), build, mlp.fc1.weight)
     if hit[2]:
-        _note_x3_launch(s1, s2)
+        note_launch(s1, s2)
     return (hit[1], s1, s2) if hit[2] else None
 
 
@@ -439,12 +262,12 @@ def convnext_mlp(mlp, gamma: torch.Tensor, x_nhwc: torch.Tensor, shortcut_nhwc: 
         else:
             # fewer than two output tiles per CU (small ROI counts at the deep stages): split K as well, or most of the chip idles
             f1 = hip_lib.linear_f32_splitk if hip_lib.split_gemm_tiles(m, 4 * c) < _SPLITK_BELOW_TILES else hip_lib.linear_f32_split
-            h = f1(x_nhwc.view(m, c), _packed(mlp.fc1, cache, "fc1_pk"), mlp.fc1.bias, "gelu")
+            h = f1(x_nhwc.view(m, c), six_product_weight(cache, "fc1_pk", mlp.fc1.weight, hip_lib.pack_weight_bf16x3), mlp.fc1.bias, "gelu")
         if w32 is not None:
             y = hip_lib.linear_f32_split(h, w32, mlp.fc2.bias, "scale_res", gamma, shortcut_nhwc.view(m, c), x3_slot=slot2, a_rows=h_rows)
         else:
             f2 = hip_lib.linear_f32_splitk if hip_lib.split_gemm_tiles(m, c) < _SPLITK_BELOW_TILES else hip_lib.linear_f32_split
-            y = f2(h, _packed(mlp.fc2, cache, "fc2_pk"), mlp.fc2.bias, "scale_res", gamma, shortcut_nhwc.view(m, c))
+            y = f2(h, six_product_weight(cache, "fc2_pk", mlp.fc2.weight, hip_lib.pack_weight_bf16x3), mlp.fc2.bias, "scale_res", gamma, shortcut_nhwc.view(m, c))
         return y.view(x_nhwc.shape)
     if a_rows:
         raise RuntimeError("convnext_mlp: f16x2-rows input outside the split-GEMM path")
@@ -476,14 +299,12 @@ def conv2d(conv: nn.Conv2d, x: torch.Tensor) -> torch.Tensor:
     head's 3x3/1, ConvNeXt's 2x2/2 downsamples, Patch-PnP's 3x3/2) run as an implicit GEMM in ``gdrnpp_conv2d_f32_split``
     (bf16 matrix cores, fp32-accurate), everything else in MIOpen."""
     if _conv_split_ok(conv, x):
-        cache = conv.__dict__.setdefault("_gdrnpp_cache", {})
+        cache = module_cache(conv)
         is3x3 = conv.kernel_size == (3, 3) and conv.stride == (1, 1) and conv.padding == (1, 1)
         ks, st, pd = conv.kernel_size[0], conv.stride[0], conv.padding[0]
         oh, ow = (x.shape[2] + 2 * pd - ks) // st + 1, (x.shape[3] + 2 * pd - ks) // st + 1
-        w_pk, slot = (x3_for(cache, "conv", conv.weight, hip_lib.pack_conv_weight_f16x2, x.shape[0] * oh * ow, conv.out_channels)
-                      if ks * ks <= 32 else (None, 0))
-        if w_pk is None:
-            w_pk = _packed_weight(cache, "w_pk", conv.weight, hip_lib.pack_conv_weight_bf16x3)
+        w_pk, slot = split_weight(cache, "conv", "w_pk", conv.weight, hip_lib.pack_conv_weight_f16x2, hip_lib.pack_conv_weight_bf16x3,
+                                  x.shape[0] * oh * ow, conv.out_channels, allow3=ks * ks <= 32)
         if is3x3:
             return hip_lib.conv3x3_f32_split(_cl(x), w_pk, conv.bias, x3_slot=slot)
         return hip_lib.conv2d_f32_split(_cl(x), w_pk, conv.bias, conv.kernel_size[0], conv.kernel_size[1], conv.stride[0],
@@ -496,7 +317,7 @@ def folded_conv_bn(conv: nn.Conv2d, bn: nn.BatchNorm2d):
     """(weight, bias) of the convolution that equals ``bn(conv(x))`` in inference mode: w * s and beta - mean * s with
     s = gamma / sqrt(var + eps) per output channel, formed in float64, cached on the conv module until a parameter or a
     running statistic changes."""
-    cache = conv.__dict__.setdefault("_gdrnpp_cache", {})
+    cache = module_cache(conv)
     def build():
         with torch.no_grad():
             s = bn.weight.double() / torch.sqrt(bn.running_var.double() + bn.eps)
@@ -562,12 +383,9 @@ def _deconv_split_ok(deconv, x) -> bool:
 def _deconv_weight(deconv, x):
     """-> (packed GEMM weight of the transposed convolution in the three- or six-product format, range-word slot)."""
     ks = deconv.kernel_size[0]
-    cache = deconv.__dict__.setdefault("_gdrnpp_cache", {})
-    w_pk, slot = x3_for(cache, "deconv", deconv.weight, hip_lib.pack_deconv_weight_f16x2, x.shape[0] * x.shape[2] * x.shape[3],
-                        ks * ks * deconv.out_channels, deconv.in_channels)
-    if w_pk is None:
-        w_pk = _packed_weight(cache, "w_pk", deconv.weight, hip_lib.pack_deconv_weight_bf16x3)
-    return w_pk, slot
+    return split_weight(module_cache(deconv), "deconv", "w_pk", deconv.weight, hip_lib.pack_deconv_weight_f16x2,
+                        hip_lib.pack_deconv_weight_bf16x3, x.shape[0] * x.shape[2] * x.shape[3], ks * ks * deconv.out_channels,
+                        deconv.in_channels)
 
 
 def conv_transpose2d(deconv: nn.ConvTranspose2d, x: torch.Tensor) -> torch.Tensor:
@@ -586,7 +404,7 @@ def conv_transpose2d_groupnorm_act(deconv: nn.ConvTranspose2d, gn: nn.GroupNorm,
     (``hip_lib.conv_transpose2d_groupnorm_act``).  Returns None when the layers are outside that form; the caller then runs them
     one by one."""
     if not (_CONV_GN_FUSED and _deconv_split_ok(deconv, x) and isinstance(gn, nn.GroupNorm) and gn.num_channels == deconv.out_channels
-            and _gn_ok(gn, x) and (act is None or (isinstance(act, nn.GELU) and getattr(act, "approximate", "none") == "none"))):
+            and _gn_ok(gn, x) and _exact_gelu_or_none(act)):
         return None
     w_pk, slot = _deconv_weight(deconv, x)
     return hip_lib.conv_transpose2d_groupnorm_act(_cl(x), w_pk, deconv.bias, deconv.kernel_size[0], deconv.stride[0], deconv.padding[0],
@@ -611,12 +429,11 @@ def conv3x3_groupnorm_act(conv: nn.Conv2d, gn: nn.GroupNorm, act: nn.Module | No
             and conv.padding == (1, 1) and conv.dilation == (1, 1) and conv.groups == 1 and conv.padding_mode == "zeros"
             and conv.in_channels % 32 == 0 and conv.out_channels % 128 == 0 and gn.affine
             and gn.num_channels == conv.out_channels and conv.out_channels == 8 * gn.num_groups
-            and (act is None or (isinstance(act, nn.GELU) and getattr(act, "approximate", "none") == "none"))):
+            and _exact_gelu_or_none(act)):
         return None
-    cache = conv.__dict__.setdefault("_gdrnpp_cache", {})
-    w_pk, slot = x3_for(cache, "conv", conv.weight, hip_lib.pack_conv_weight_f16x2, x.shape[0] * x.shape[2] * x.shape[3], conv.out_channels)
-    if w_pk is None:
-        w_pk = _packed_weight(cache, "w_pk", conv.weight, hip_lib.pack_conv_weight_bf16x3)
+    cache = module_cache(conv)
+    w_pk, slot = split_weight(cache, "conv", "w_pk", conv.weight, hip_lib.pack_conv_weight_f16x2, hip_lib.pack_conv_weight_bf16x3,
+                              x.shape[0] * x.shape[2] * x.shape[3], conv.out_channels)
     return hip_lib.conv3x3_groupnorm_act(_cl(x), w_pk, conv.bias, gn.weight, gn.bias, gn.num_groups, gn.eps,
                                          gelu=act is not None, x3_slot=slot)
 
@@ -627,10 +444,21 @@ def linear(fc: nn.Linear, x: torch.Tensor, gelu: bool = False) -> torch.Tensor:
     form of the split GEMM spreads K over 64 workgroups per output tile."""
     if (_MLP_GEMM == "split" and enabled_for(x) and x.dim() == 2 and x.is_contiguous() and fc.out_features % 128 == 0
             and fc.in_features % 32 == 0 and fc.in_features >= 1024 and x.shape[0] <= 1024):
-        cache = fc.__dict__.setdefault("_gdrnpp_cache", {})
-        return hip_lib.linear_f32_splitk(x, _packed(fc, cache, "w_pk"), fc.bias, "gelu" if gelu else "none")
+        cache = module_cache(fc)
+        return hip_lib.linear_f32_splitk(x, six_product_weight(cache, "w_pk", fc.weight, hip_lib.pack_weight_bf16x3), fc.bias, "gelu" if gelu else "none")
     _fallback("linear: nn.Linear outside the split-K form (hipBLASLt)", x)
     return F.gelu(fc(x)) if gelu else fc(x)
+
+
+def _heads_with_pose(feat, w_r, b_r, w_t, b_t, pose: dict | None):
+    """The two pose heads in one launch; with ``pose`` and a rotation head of that mode's width the same launch also leaves
+    ``pose["result"] = (R_ego, trans)``."""
+    if pose is not None and w_r.shape[0] == hip_lib.ROT_DIMS[pose["rot_mode"]]:
+        kw = {k: v for k, v in pose.items() if k != "result"}
+        rot_, t_, R, trans = hip_lib.pnp_fc_heads_pose(feat, w_r, b_r, w_t, b_t, **kw)
+        pose["result"] = (R, trans)
+        return rot_, t_
+    return hip_lib.pnp_fc_heads(feat, w_r, b_r, w_t, b_t)
 
 
 def pnp_fc_heads(fc_r: nn.Linear, fc_t: nn.Linear, x: torch.Tensor, pose: dict | None = None):
@@ -640,12 +468,7 @@ def pnp_fc_heads(fc_r: nn.Linear, fc_t: nn.Linear, x: torch.Tensor, pose: dict |
     if (enabled_for(x) and _MLP_GEMM == "split" and x.dim() == 2 and x.is_contiguous() and fc_r.in_features == fc_t.in_features <= 1024
             and fc_r.out_features <= 9 and fc_t.out_features == 3):
         w_r, w_t = fc_r.weight.detach().contiguous(), fc_t.weight.detach().contiguous()
-        if pose is not None and fc_r.out_features == {"rot6d": 6, "quat": 4, "mat": 9, "log_quat": 3, "lie_vec": 3}[pose["rot_mode"]]:
-            kw = {k: v for k, v in pose.items() if k != "result"}
-            rot_, t_, R, trans = hip_lib.pnp_fc_heads_pose(x, w_r, fc_r.bias, w_t, fc_t.bias, **kw)
-            pose["result"] = (R, trans)
-            return rot_, t_
-        return hip_lib.pnp_fc_heads(x, w_r, fc_r.bias, w_t, fc_t.bias)
+        return _heads_with_pose(x, w_r, fc_r.bias, w_t, fc_t.bias, pose)
     _fallback("pnp_fc_heads: pose heads outside the one-launch kernel (hipBLASLt)", x)
     return fc_r(x), fc_t(x)
 
@@ -667,92 +490,6 @@ def point_pnp(head: nn.Module, x2d: torch.Tensor, b: int, hw: int, pose: dict | 
         rd = head.rot_dim
         w, bias = head.fc_pose.weight.detach(), head.fc_pose.bias.detach()      # row slices of a contiguous matrix are contiguous
         w_r, w_t, b_r, b_t = w[:rd], w[rd:rd + 3], bias[:rd], bias[rd:rd + 3]
-        if pose is not None and rd == {"rot6d": 6, "quat": 4, "mat": 9, "log_quat": 3, "lie_vec": 3}[pose["rot_mode"]]:
-            kw = {k: v for k, v in pose.items() if k != "result"}
-            rot_, t_, R, trans = hip_lib.pnp_fc_heads_pose(feat, w_r, b_r, w_t, b_t, **kw)
-            pose["result"] = (R, trans)
-            return rot_, t_
-        return hip_lib.pnp_fc_heads(feat, w_r, b_r, w_t, b_t)
+        return _heads_with_pose(feat, w_r, b_r, w_t, b_t, pose)
     _fallback("point_pnp: SimplePointPnPNet outside the fused point-MLP kernel (PyTorch operators)", x2d)
     return head.mlp_tail(x2d.view(b, hw, x2d.shape[1])[:, :, :cin].transpose(1, 2))
-
-
-# ---- layers of the YOLOX detector on channel slices (csrc/yolox_net.hip) -----------------------------------------------------
-class NhwcSlice:
-    """Channels [off, off + c) of a contiguous NHWC buffer f32[B,H,W,ld]: where a layer reads its input and writes its result,
-    so a concatenation is a buffer its producers fill side by side."""
-    __slots__ = ("buf", "off", "c")
-
-    def __init__(self, buf: torch.Tensor, off: int = 0, c: int | None = None):
-        self.buf, self.off, self.c = buf, off, buf.shape[-1] - off if c is None else c
-
-    def view(self) -> torch.Tensor:
-        return self.buf[..., self.off:self.off + self.c]
-
-    def nchw(self) -> torch.Tensor:
-        return self.view().permute(0, 3, 1, 2)
-
-
-def _conv_slice_ok(conv: nn.Conv2d, src: NhwcSlice) -> bool:
-    """Shapes ``gdrnpp_conv_bias_act_f32`` takes: dense 1x1 / 3x3, stride 1 / 2, padding (k - 1) / 2, Cin and the slice's
-    placement multiples of 4."""
-    k, s = conv.kernel_size, conv.stride
-    return (k[0] == k[1] and k[0] in (1, 3) and s[0] == s[1] and s[0] in (1, 2) and conv.padding == ((k[0] - 1) // 2,) * 2
-            and conv.dilation == (1, 1) and conv.groups == 1 and conv.padding_mode == "zeros" and conv.in_channels % 4 == 0
-            and src.off % 4 == 0 and src.buf.shape[-1] % 4 == 0 and src.c == conv.in_channels)
-
-
-def conv_bn_act_slice(conv: nn.Conv2d, bn: nn.BatchNorm2d | None, act: str, src: NhwcSlice, dst: NhwcSlice, resid: NhwcSlice | None = None,
-                      img_rows: int = 0, row0: int = 0, dec_stride: float = 0.0) -> NhwcSlice:
-    """dst = act(bn(conv(src))) + resid in ONE launch of ``gdrnpp_conv_bias_act_f32``: BatchNorm (inference) folded into weight
-    and bias in float64 (``folded_conv_bn``), the k-major weight cached on the conv module until a parameter or statistic
-    changes.  ``act`` in none / silu / sigmoid / yolox_box; ``img_rows`` / ``row0``: dst.buf is f32[B,img_rows,ld] and the layer
-    writes from row ``row0`` of every image (the head's prediction layers).  Shapes outside the kernel run as PyTorch operators
-    into the same slice, counted as a fallback."""
-    x = src.buf
-    if not enabled_for(x):
-        raise RuntimeError("conv_bn_act_slice: the slice layers exist on the GPU with the HIP layers enabled only")
-    if bn is not None and (bn.training or not bn.affine or not bn.track_running_stats):
-        raise RuntimeError("conv_bn_act_slice: BatchNorm must be in inference mode with affine parameters and running statistics")
-    w, b = folded_conv_bn(conv, bn) if bn is not None else (conv.weight.detach(), None if conv.bias is None else conv.bias.detach())
-    if _conv_slice_ok(conv, src):
-        cache = conv.__dict__.setdefault("_gdrnpp_cache", {})
-        hit = cached(cache, "w_kmajor", weight_tag(w), lambda: (hip_lib.pack_conv_weight_kmajor(w),), w)
-        hip_lib.conv_bias_act_f32(x, src.off, src.c, hit[1], b, dst.buf, dst.off, dst.c, conv.kernel_size[0], conv.stride[0], act,
-                                  None if resid is None else resid.buf, 0 if resid is None else resid.off, img_rows, row0, dec_stride)
-        return dst
-    _fallback("conv_bn_act_slice: convolution outside gdrnpp_conv_bias_act_f32 (PyTorch operators)", x)
-    y = F.conv2d(src.nchw(), w, b, conv.stride, conv.padding, conv.dilation, conv.groups).permute(0, 2, 3, 1)
-    if act == "silu":
-        y = F.silu(y)
-    elif act == "sigmoid":
-        y = torch.sigmoid(y)
-    elif act == "yolox_box":
-        oh, ow = y.shape[1:3]
-        g = torch.stack(torch.meshgrid(torch.arange(ow, device=y.device), torch.arange(oh, device=y.device), indexing="xy"), -1).to(y.dtype)
-        y = torch.cat([(y[..., :2] + g) * dec_stride, torch.exp(y[..., 2:4]) * dec_stride], -1)
-    if resid is not None:
-        y = y + resid.view()
-    if img_rows:
-        dst.buf[:, row0:row0 + y.shape[1] * y.shape[2], dst.off:dst.off + dst.c] = y.reshape(y.shape[0], -1, y.shape[3])
-    else:
-        dst.view().copy_(y)
-    return dst
-
-
-def focus_slice(x_nchw: torch.Tensor, dst: NhwcSlice) -> NhwcSlice:
-    """The Focus stem's 2x2 space-to-depth from the NCHW image into a 12-channel NHWC slice (``gdrnpp_yolox_focus``)."""
-    hip_lib.yolox_focus(x_nchw.contiguous(), dst.buf, dst.off)
-    return dst
-
-
-def spp_slice(cat: NhwcSlice, c: int) -> NhwcSlice:
-    """The 5 / 9 / 13 max pools of the first ``c`` channels of ``cat`` into its next three groups of ``c`` channels, one launch."""
-    hip_lib.spp_maxpool_5_9_13(cat.buf, cat.off, c)
-    return cat
-
-
-def upsample2x_slice(src: NhwcSlice, dst: NhwcSlice) -> NhwcSlice:
-    """Nearest x2 of a slice into a slice (``gdrnpp_upsample_nearest2x_slice``)."""
-    hip_lib.upsample_nearest2x_slice(src.buf, src.off, dst.buf, dst.off, src.c)
-    return dst

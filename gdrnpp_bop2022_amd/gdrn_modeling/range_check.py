@@ -6,7 +6,7 @@ from __future__ import annotations
 import torch
 
 from .. import hip_lib
-from . import hip_layers
+from . import x3_policy
 
 
 _X3_OVERFLOW_STEPS = 0          # steps of this process whose three-product kernels overflowed the fp16 range
@@ -20,31 +20,31 @@ def range_reruns() -> int:
 
 def _note_range_words(words: dict) -> None:
     """What a step's non-zero range words ({slot: word}, hip_lib.split2_range_words) change for the steps to come:
-      * every layer with rows below the range stays on the six-product kernels (hip_layers.demote_x3);
+      * every layer with rows below the range stays on the six-product kernels (x3_policy.demote);
       * of the layers reporting non-finite values the FIRST in launch order does (the others saw its inf / NaN pass through);
       * a model whose activations overflow step after step is not paid for twice for ever: after X3_OVERFLOW_STEPS_TO_GIVE_UP
         such steps the process stays on six products (with a warning)."""
     global _X3_OVERFLOW_STEPS
-    hip_layers.demote_x3({s_: w for s_, w in words.items() if w & hip_lib.X3_SMALL_ROWS})
-    over = hip_layers.x3_launch_order(s_ for s_, w in words.items() if w & hip_lib.X3_NONFINITE)   # slot order is not launch order
+    x3_policy.demote({s_: w for s_, w in words.items() if w & hip_lib.X3_SMALL_ROWS})
+    over = x3_policy.launch_order(s_ for s_, w in words.items() if w & hip_lib.X3_NONFINITE)   # slot order is not launch order
     if over:
         _X3_OVERFLOW_STEPS += 1
         first = [s_ for s_ in over if s_ > 0][:1]
-        hip_layers.demote_x3({s_: hip_lib.X3_NONFINITE for s_ in first})
-        if _X3_OVERFLOW_STEPS >= X3_OVERFLOW_STEPS_TO_GIVE_UP and hip_layers.gemm_products() == 3:
+        x3_policy.demote({s_: hip_lib.X3_NONFINITE for s_ in first})
+        if _X3_OVERFLOW_STEPS >= X3_OVERFLOW_STEPS_TO_GIVE_UP and x3_policy.gemm_products() == 3:
             import warnings
-            hip_layers.set_gemm_products(6)
+            x3_policy.set_gemm_products(6)
             warnings.warn(f"{_X3_OVERFLOW_STEPS} steps overflowed the fp16 range of the three-product GEMM kernels: staying on the "
-                          "six-product kernels (hip_layers.set_gemm_products(3) switches back)")
+                          "six-product kernels (x3_policy.set_gemm_products(3) switches back)")
 
 
 def _six_product_rerun(run, words: dict):
     """Repeat a step with the six-product kernels after its three-product launches reported ``words``; the calling host thread
-    only (hip_layers.forced_gemm_products), other threads / streams keep their setting."""
+    only (x3_policy.forced_gemm_products), other threads / streams keep their setting."""
     global _RANGE_RERUNS
     _RANGE_RERUNS += 1
     _note_range_words(words)
-    with hip_layers.forced_gemm_products(6):
+    with x3_policy.forced_gemm_products(6):
         return run()
 
 
@@ -114,7 +114,7 @@ def launch_with_range_check(run) -> StepHandle:
         done = torch.cuda.Event()
         done.record()
         return StepHandle(None, out, stream=st, done=done)
-    words = hip_lib._x3_flags()              # this stream's words: steps in flight on other streams have their own
+    words = hip_lib.x3_flags()              # this stream's words: steps in flight on other streams have their own
     host = torch.empty(words.shape, dtype=words.dtype, pin_memory=True)
     host.copy_(words, non_blocking=True)
     words.zero_()

@@ -203,6 +203,22 @@ def _dev(t: torch.Tensor, dtype: torch.dtype, name: str) -> int:
     return t.data_ptr()
 
 
+def _f32(t: torch.Tensor, name: str) -> int:
+    """``_dev(t, torch.float32, name)`` with the checks in one test: one Python call per argument, as ``_dev`` itself."""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous():
+        _dev(t, torch.float32, name)    # raises, saying which
+    return t.data_ptr()
+
+
+def _opt_f32(t: torch.Tensor | None, name: str):
+    """``_f32`` of an optional argument: None = NULL."""
+    if t is None:
+        return None
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous():
+        _dev(t, torch.float32, name)
+    return t.data_ptr()
+
+
 # ------------------------------------------------------------------------------------------
 class MeshSet:
     """All object models of a dataset, flat and resident in HBM (``gdrnpp_meshes``)."""
@@ -245,8 +261,7 @@ def fps(pts: torch.Tensor, sn: int, init_center: bool = True, start_idx: torch.T
     ws_bytes = lib.gdrnpp_fps_workspace_bytes(b, pn)
     ws = torch.empty((max(ws_bytes, 4),), dtype=torch.uint8, device=pts.device)
     sp = _dev(start_idx, torch.int32, "start_idx") if start_idx is not None else None
-    _check(lib.gdrnpp_fps(_dev(pts, torch.float32, "pts"), idxs.data_ptr(), sp, b, pn, sn, 1 if init_center else 0,
-                          ws.data_ptr(), _stream()), "gdrnpp_fps")
+    _check(lib.gdrnpp_fps(_f32(pts, "pts"), idxs.data_ptr(), sp, b, pn, sn, 1 if init_center else 0, ws.data_ptr(), _stream()), "gdrnpp_fps")
     return idxs
 
 
@@ -254,8 +269,7 @@ def nnd_forward(xyz1, xyz2, dist1, dist2, idx1, idx2) -> int:
     lib = load()
     b, n, _ = xyz1.shape
     m = xyz2.shape[1]
-    _check(lib.gdrnpp_nnd_forward(_dev(xyz1, torch.float32, "xyz1"), _dev(xyz2, torch.float32, "xyz2"),
-                                  _dev(dist1, torch.float32, "dist1"), _dev(dist2, torch.float32, "dist2"),
+    _check(lib.gdrnpp_nnd_forward(_f32(xyz1, "xyz1"), _f32(xyz2, "xyz2"), _f32(dist1, "dist1"), _f32(dist2, "dist2"),
                                   _dev(idx1, torch.int32, "idx1"), _dev(idx2, torch.int32, "idx2"), b, n, m,
                                   _stream()), "gdrnpp_nnd_forward")
     return 1
@@ -265,11 +279,8 @@ def nnd_backward(xyz1, xyz2, gradxyz1, gradxyz2, graddist1, graddist2, idx1, idx
     lib = load()
     b, n, _ = xyz1.shape
     m = xyz2.shape[1]
-    _check(lib.gdrnpp_nnd_backward(_dev(xyz1, torch.float32, "xyz1"), _dev(xyz2, torch.float32, "xyz2"),
-                                   _dev(gradxyz1, torch.float32, "gradxyz1"),
-                                   _dev(gradxyz2, torch.float32, "gradxyz2"),
-                                   _dev(graddist1, torch.float32, "graddist1"),
-                                   _dev(graddist2, torch.float32, "graddist2"), _dev(idx1, torch.int32, "idx1"),
+    _check(lib.gdrnpp_nnd_backward(_f32(xyz1, "xyz1"), _f32(xyz2, "xyz2"), _f32(gradxyz1, "gradxyz1"), _f32(gradxyz2, "gradxyz2"),
+                                   _f32(graddist1, "graddist1"), _f32(graddist2, "graddist2"), _dev(idx1, torch.int32, "idx1"),
                                    _dev(idx2, torch.int32, "idx2"), b, n, m, _stream()), "gdrnpp_nnd_backward")
     return 1
 
@@ -300,10 +311,8 @@ def decode_correspondences(coor_x, coor_y, coor_z, mask_raw, coord2d, extent, im
     mdl_pts = torch.empty((b, hw, 3), dtype=torch.float32, device=dev)
     out_mask = torch.empty_like(mask_raw) if want_mask else None
     _check(lib.gdrnpp_decode_correspondences(
-        _dev(coor_x, torch.float32, "coor_x"), _dev(coor_y, torch.float32, "coor_y"),
-        _dev(coor_z, torch.float32, "coor_z"), _dev(mask_raw, torch.float32, "mask"),
-        _dev(coord2d, torch.float32, "coord2d"), _dev(extent, torch.float32, "extent"),
-        _dev(im_wh, torch.float32, "im_wh"), out_mask.data_ptr() if want_mask else None, count.data_ptr(),
+        _f32(coor_x, "coor_x"), _f32(coor_y, "coor_y"), _f32(coor_z, "coor_z"), _f32(mask_raw, "mask"),
+        _f32(coord2d, "coord2d"), _f32(extent, "extent"), _f32(im_wh, "im_wh"), out_mask.data_ptr() if want_mask else None, count.data_ptr(),
         sel_idx.data_ptr(), img_pts.data_ptr(), mdl_pts.data_ptr(), b, hw, mask_type, float(mask_thr), _stream()),
         "gdrnpp_decode_correspondences")
     return count, sel_idx, img_pts, mdl_pts, out_mask
@@ -315,9 +324,8 @@ def pose_from_pred_centroid_z(rot6d, t_, cams, centers, whs, resize_ratios, z_ty
     rot = torch.empty((b, 3, 3), dtype=torch.float32, device=rot6d.device)
     trans = torch.empty((b, 3), dtype=torch.float32, device=rot6d.device)
     _check(lib.gdrnpp_pose_from_pred_centroid_z(
-        _dev(rot6d, torch.float32, "rot6d"), _dev(t_, torch.float32, "t_"), _dev(cams, torch.float32, "cams"),
-        _dev(centers, torch.float32, "centers"), _dev(whs, torch.float32, "whs"),
-        _dev(resize_ratios, torch.float32, "resize_ratios"), rot.data_ptr(), trans.data_ptr(), b,
+        _f32(rot6d, "rot6d"), _f32(t_, "t_"), _f32(cams, "cams"), _f32(centers, "centers"), _f32(whs, "whs"),
+        _f32(resize_ratios, "resize_ratios"), rot.data_ptr(), trans.data_ptr(), b,
         {"REL": 0, "ABS": 1}[z_type], 1 if is_allo else 0, _stream()), "gdrnpp_pose_from_pred_centroid_z")
     return rot, trans
 
@@ -329,12 +337,10 @@ def pose_from_pred(rot_in, t_, cams, centers=None, whs=None, resize_ratios=None,
     b = rot_in.shape[0]
     rot = torch.empty((b, 3, 3), dtype=torch.float32, device=rot_in.device)
     trans = torch.empty((b, 3), dtype=torch.float32, device=rot_in.device)
-    rm = {"rot6d": 0, "quat": 1, "mat": 2, "log_quat": 3, "lie_vec": 4}[rot_mode]
-    tm = {"centroid_z_rel": 0, "centroid_z_abs_z": 1, "centroid_z_abs": 2, "trans": 3}[t_mode]
-    opt = lambda x, n: _dev(x, torch.float32, n) if x is not None else None  # noqa: E731
-    _check(load().gdrnpp_pose_from_pred(_dev(rot_in, torch.float32, "rot_in"), rm, _dev(t_, torch.float32, "t_"), tm,
-                                        _dev(cams, torch.float32, "cams"), opt(centers, "centers"), opt(whs, "whs"),
-                                        opt(resize_ratios, "resize_ratios"), rot.data_ptr(), trans.data_ptr(), b,
+    rm, tm = ROT_MODES[rot_mode], T_MODES[t_mode]
+    _check(load().gdrnpp_pose_from_pred(_f32(rot_in, "rot_in"), rm, _f32(t_, "t_"), tm,
+                                        _f32(cams, "cams"), _opt_f32(centers, "centers"), _opt_f32(whs, "whs"),
+                                        _opt_f32(resize_ratios, "resize_ratios"), rot.data_ptr(), trans.data_ptr(), b,
                                         1 if is_allo else 0, _stream()), "gdrnpp_pose_from_pred")
     return rot, trans
 
@@ -343,8 +349,7 @@ def zoom_K(K, centers, scales, out_res: float):
     lib = load()
     b = K.shape[0]
     out = torch.empty_like(K)
-    _check(lib.gdrnpp_zoom_K(_dev(K, torch.float32, "K"), _dev(centers, torch.float32, "centers"),
-                             _dev(scales, torch.float32, "scales"), out.data_ptr(), b, float(out_res), _stream()),
+    _check(lib.gdrnpp_zoom_K(_f32(K, "K"), _f32(centers, "centers"), _f32(scales, "scales"), out.data_ptr(), b, float(out_res), _stream()),
            "gdrnpp_zoom_K")
     return out
 
@@ -355,8 +360,7 @@ def render_depth(meshes: MeshSet, obj, K, R, t, res: int, z_near: float = 0.1, z
     b = obj.shape[0]
     depth = torch.empty((b, res, res), dtype=torch.float32, device=obj.device)
     xyz = torch.empty((b, res, res, 3), dtype=torch.float32, device=obj.device) if want_xyz else None
-    _check(lib.gdrnpp_render_depth(meshes.c, _dev(obj, torch.int32, "obj"), _dev(K, torch.float32, "K"),
-                                   _dev(R, torch.float32, "R"), _dev(t, torch.float32, "t"), depth.data_ptr(),
+    _check(lib.gdrnpp_render_depth(meshes.c, _dev(obj, torch.int32, "obj"), _f32(K, "K"), _f32(R, "R"), _f32(t, "t"), depth.data_ptr(),
                                    xyz.data_ptr() if want_xyz else None, b, res, z_near, z_far, _stream()),
            "gdrnpp_render_depth")
     return (depth, xyz) if want_xyz else depth
@@ -384,10 +388,8 @@ def depth_refine(meshes: MeshSet, obj, coor_x, coor_y, coor_z, mask_raw, roi_dep
         ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
         ev[0].record()
     _check(lib.gdrnpp_depth_refine(
-        meshes.c, _dev(obj, torch.int32, "obj"), _dev(coor_x, torch.float32, "coor_x"),
-        _dev(coor_y, torch.float32, "coor_y"), _dev(coor_z, torch.float32, "coor_z"),
-        _dev(mask_raw, torch.float32, "mask"), _dev(roi_depth, torch.float32, "roi_depth"),
-        _dev(K_crop, torch.float32, "K_crop"), _dev(R, torch.float32, "R"), _dev(t, torch.float32, "t"),
+        meshes.c, _dev(obj, torch.int32, "obj"), _f32(coor_x, "coor_x"), _f32(coor_y, "coor_y"), _f32(coor_z, "coor_z"),
+        _f32(mask_raw, "mask"), _f32(roi_depth, "roi_depth"), _f32(K_crop, "K_crop"), _f32(R, "R"), _f32(t, "t"),
         _dev(t_out, torch.float64, "t_out"), dbg.data_ptr() if debug else None, b, res, int(roi_depth.shape[-1]), iters,
         float(threshold), mask_type, 1 if use_coor_z else 0, z_near, z_far, ws.data_ptr() if ws is not None else None, nbytes,
         _stream()), "gdrnpp_depth_refine")
@@ -413,10 +415,9 @@ def refine_to_records(meshes: MeshSet, obj, coor_x, coor_y, coor_z, mask_raw, ro
         ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
         ev[0].record()
     _check(lib.gdrnpp_refine_to_records(
-        meshes.c, _dev(obj, torch.int32, "obj"), _dev(coor_x, torch.float32, "coor_x"), _dev(coor_y, torch.float32, "coor_y"),
-        _dev(coor_z, torch.float32, "coor_z"), _dev(mask_raw, torch.float32, "mask"), _dev(roi_depth, torch.float32, "roi_depth"),
-        _dev(cam, torch.float32, "cam"), _dev(center, torch.float32, "center"), _dev(scale, torch.float32, "scale"),
-        _dev(R, torch.float32, "R"), _dev(t, torch.float32, "t"), _dev(score, torch.float32, "score") if score is not None else None,
+        meshes.c, _dev(obj, torch.int32, "obj"), _f32(coor_x, "coor_x"), _f32(coor_y, "coor_y"),
+        _f32(coor_z, "coor_z"), _f32(mask_raw, "mask"), _f32(roi_depth, "roi_depth"), _f32(cam, "cam"), _f32(center, "center"), _f32(scale, "scale"),
+        _f32(R, "R"), _f32(t, "t"), _opt_f32(score, "score"),
         _dev(roi_id, torch.int32, "roi_id") if roi_id is not None else None, rec.data_ptr(), b, res, int(roi_depth.shape[-1]),
         iters, float(threshold), mask_type, 1 if use_coor_z else 0, z_near, z_far, ws.data_ptr() if ws is not None else None,
         nbytes, _stream()), "gdrnpp_refine_to_records")
@@ -445,10 +446,8 @@ def pack_pose_records(R, t_refined, t_net, score, obj_id, roi_id):
     b = R.shape[0]
     rec = torch.empty((b, 16), dtype=torch.float32, device=R.device)
     _check(lib.gdrnpp_pack_pose_records(
-        _dev(R, torch.float32, "R"), _dev(t_refined, torch.float64, "t_refined") if t_refined is not None else None,
-        _dev(t_net, torch.float32, "t_net") if t_net is not None else None,
-        _dev(score, torch.float32, "score") if score is not None else None,
-        _dev(obj_id, torch.int32, "obj_id") if obj_id is not None else None,
+        _f32(R, "R"), _dev(t_refined, torch.float64, "t_refined") if t_refined is not None else None,
+        _opt_f32(t_net, "t_net"), _opt_f32(score, "score"), _dev(obj_id, torch.int32, "obj_id") if obj_id is not None else None,
         _dev(roi_id, torch.int32, "roi_id") if roi_id is not None else None, rec.data_ptr(), b, _stream()),
         "gdrnpp_pack_pose_records")
     return rec
@@ -471,9 +470,8 @@ def dwconv7x7_ln(x, w49c, bias, ln_w=None, ln_b=None, eps: float = 1e-6, y_rows:
     ``linear_f32_split(..., a_rows=True)`` — same shape and dtype, NOT readable as floats."""
     n, c, h, w = x.shape
     y = torch.empty_like(x, memory_format=torch.channels_last)
-    args = (_nhwc(x, "x"), _dev(w49c, torch.float32, "w49c"), _dev(bias, torch.float32, "bias"),
-            _dev(ln_w, torch.float32, "ln_w") if ln_w is not None else None,
-            _dev(ln_b, torch.float32, "ln_b") if ln_b is not None else None, y.data_ptr(), n, h, w, c, float(eps), int(bool(y_rows)), _stream())
+    args = (_nhwc(x, "x"), _f32(w49c, "w49c"), _f32(bias, "bias"),
+            _opt_f32(ln_w, "ln_w"), _opt_f32(ln_b, "ln_b"), y.data_ptr(), n, h, w, c, float(eps), int(bool(y_rows)), _stream())
     _check(_timed("hbm:dwconv7_ln", 0.0, lambda: load().gdrnpp_dwconv7x7_ln_nhwc_rows(*args), 8.0 * x.numel()),
            "gdrnpp_dwconv7x7_ln_nhwc")
     return y
@@ -493,8 +491,7 @@ def layernorm_nhwc(x, weight, bias, eps: float = 1e-6):
     """x (N,C,H,W) channels_last -> LayerNorm over C per pixel, same shape/format."""
     n, c, h, w = x.shape
     y = torch.empty_like(x, memory_format=torch.channels_last)
-    args = (_nhwc(x, "x"), _dev(weight, torch.float32, "weight"), _dev(bias, torch.float32, "bias"), y.data_ptr(), n * h * w, c,
-            float(eps), _stream())
+    args = (_nhwc(x, "x"), _f32(weight, "weight"), _f32(bias, "bias"), y.data_ptr(), n * h * w, c, float(eps), _stream())
     _check(_timed("hbm:layernorm", 0.0, lambda: load().gdrnpp_layernorm_nhwc(*args), 8.0 * x.numel()), "gdrnpp_layernorm_nhwc")
     return y
 
@@ -512,7 +509,7 @@ def groupnorm_act(x, gamma, beta, groups: int, eps: float = 1e-5, gelu: bool = F
     n, c, h, w = x.shape
     y = torch.empty_like(x, memory_format=torch.channels_last)
     ws = torch.empty((load().gdrnpp_groupnorm_workspace_bytes(n, h * w, groups),), dtype=torch.uint8, device=x.device)
-    args = (_nhwc(x, "x"), _dev(gamma, torch.float32, "gamma"), _dev(beta, torch.float32, "beta"), y.data_ptr(),
+    args = (_nhwc(x, "x"), _f32(gamma, "gamma"), _f32(beta, "beta"), y.data_ptr(),
             ws.data_ptr(), n, h * w, c, groups, float(eps), 1 if gelu else 0, _stream())
     _check(_timed("hbm:groupnorm", 0.0, lambda: load().gdrnpp_groupnorm_act_nhwc(*args), 12.0 * x.numel()),   # read twice, write once
            "gdrnpp_groupnorm_act_nhwc")
@@ -535,7 +532,7 @@ def crop_resize_roi(images, depths, im_idx, centers, scales, out_res: int = 256,
     mean = (ctypes.c_double * 3)(*[float(v) for v in pixel_mean])
     std = (ctypes.c_double * 3)(*[float(v) for v in pixel_std])
     _check(lib.gdrnpp_crop_resize_roi(
-        _dev(images, torch.uint8, "images"), _dev(depths, torch.float32, "depths") if depths is not None else None,
+        _dev(images, torch.uint8, "images"), _opt_f32(depths, "depths"),
         n_im, H, W, _dev(im_idx, torch.int32, "im_idx") if im_idx is not None else None,
         _dev(centers, torch.float64, "centers"), _dev(scales, torch.float64, "scales"),
         roi_img.data_ptr() if want_img else None, roi_depth.data_ptr() if roi_depth is not None else None,
@@ -551,7 +548,7 @@ def roi_align(x, rois, output_size, spatial_scale: float = 1.0, sampling_ratio: 
     bsz, c, h, w = x.shape
     n = rois.shape[0]
     out = torch.empty((n, c, oh, ow), dtype=torch.float32, device=x.device)
-    _check(load().gdrnpp_roi_align(_dev(x, torch.float32, "x"), _dev(rois, torch.float32, "rois"), out.data_ptr(), n, c,
+    _check(load().gdrnpp_roi_align(_f32(x, "x"), _f32(rois, "rois"), out.data_ptr(), n, c,
                                    h, w, oh, ow, float(spatial_scale), int(sampling_ratio), 1 if aligned else 0,
                                    _stream()), "gdrnpp_roi_align")
     return out
@@ -564,7 +561,7 @@ def roi_pool(x, rois, output_size, spatial_scale: float = 1.0):
     bsz, c, h, w = x.shape
     n = rois.shape[0]
     out = torch.empty((n, c, oh, ow), dtype=torch.float32, device=x.device)
-    _check(load().gdrnpp_roi_pool(_dev(x, torch.float32, "x"), _dev(rois, torch.float32, "rois"), out.data_ptr(), n, c, h, w,
+    _check(load().gdrnpp_roi_pool(_f32(x, "x"), _f32(rois, "rois"), out.data_ptr(), n, c, h, w,
                                   oh, ow, float(spatial_scale), _stream()), "gdrnpp_roi_pool")
     return out
 
@@ -576,8 +573,8 @@ def pnp_iter_from_correspondences(img_pts, mdl_pts, count, K, R_net, t_net, retu
     t_out = torch.empty((b, 3), dtype=torch.float32, device=img_pts.device)
     info = torch.zeros((b, 2), dtype=torch.int32, device=img_pts.device)
     _check(load().gdrnpp_pnp_iter_from_correspondences(
-        _dev(img_pts, torch.float32, "img_pts"), _dev(mdl_pts, torch.float32, "mdl_pts"), _dev(count, torch.int32, "count"),
-        stride, _dev(K, torch.float32, "K"), _dev(R_net, torch.float32, "R_net"), _dev(t_net, torch.float32, "t_net"),
+        _f32(img_pts, "img_pts"), _f32(mdl_pts, "mdl_pts"), _dev(count, torch.int32, "count"),
+        stride, _f32(K, "K"), _f32(R_net, "R_net"), _f32(t_net, "t_net"),
         R_out.data_ptr(), t_out.data_ptr(), info.data_ptr(), b, _stream()), "gdrnpp_pnp_iter_from_correspondences")
     return (R_out, t_out, info) if return_info else (R_out, t_out)
 
@@ -606,8 +603,8 @@ def epnp_ransac(img_pts, mdl_pts, count, K, iters: int = 100, reproj_err: float 
             raise RuntimeError("draws must be a contiguous 32-bit integer CUDA(HIP) tensor [b, n_words]")
         n_draws = int(draws.shape[1])
     _check(lib.gdrnpp_epnp_ransac(
-        _dev(img_pts, torch.float32, "img_pts"), _dev(mdl_pts, torch.float32, "mdl_pts"), _dev(count, torch.int32, "count"),
-        stride, _dev(K.reshape(b, 9), torch.float32, "K"), draws.data_ptr() if draws is not None else None, n_draws, int(iters),
+        _f32(img_pts, "img_pts"), _f32(mdl_pts, "mdl_pts"), _dev(count, torch.int32, "count"),
+        stride, _f32(K.reshape(b, 9), "K"), draws.data_ptr() if draws is not None else None, n_draws, int(iters),
         float(reproj_err), float(confidence), Rm.data_ptr(), t.data_ptr(), n_inl.data_ptr(), status.data_ptr(), mask.data_ptr(),
         b, ws.data_ptr(), nbytes, _stream()), "gdrnpp_epnp_ransac")
     return Rm, t, n_inl, status, mask
@@ -621,8 +618,8 @@ def epnp_batched(img_pts, mdl_pts, K):
     Rm = torch.empty((b, 3, 3), dtype=torch.float32, device=dev)
     t = torch.empty((b, 3), dtype=torch.float32, device=dev)
     status = torch.empty((b,), dtype=torch.int32, device=dev)
-    _check(load().gdrnpp_epnp_batched(_dev(img_pts, torch.float32, "img_pts"), _dev(mdl_pts, torch.float32, "mdl_pts"), n,
-                                      _dev(K.reshape(b, 9), torch.float32, "K"), Rm.data_ptr(), t.data_ptr(), status.data_ptr(),
+    _check(load().gdrnpp_epnp_batched(_f32(img_pts, "img_pts"), _f32(mdl_pts, "mdl_pts"), n,
+                                      _f32(K.reshape(b, 9), "K"), Rm.data_ptr(), t.data_ptr(), status.data_ptr(),
                                       b, _stream()), "gdrnpp_epnp_batched")
     return Rm, t, status
 
@@ -662,7 +659,7 @@ def pack_weight_bf16x3(weight):
     128x16 tile, laid out as gdrnpp_linear_f32_split stages it (split, k-block, row, 8 k)."""
     n, k = weight.shape
     packed = torch.empty((n // 128, k // 16, 3, 2, 128, 8), dtype=torch.bfloat16, device=weight.device)
-    _check(load().gdrnpp_pack_weight_bf16x3(_dev(weight, torch.float32, "weight"), packed.data_ptr(), n, k, _stream()),
+    _check(load().gdrnpp_pack_weight_bf16x3(_f32(weight, "weight"), packed.data_ptr(), n, k, _stream()),
            "gdrnpp_pack_weight_bf16x3")
     return packed
 
@@ -674,7 +671,7 @@ def pack_weight_f16x2(weight):
     n, k = weight.shape
     nbytes = load().gdrnpp_pack_weight_f16x2_bytes(n, k)
     buf = torch.empty((nbytes,), dtype=torch.uint8, device=weight.device)
-    _check(load().gdrnpp_pack_weight_f16x2(_dev(weight, torch.float32, "weight"), buf.data_ptr(), n, k, _stream()),
+    _check(load().gdrnpp_pack_weight_f16x2(_f32(weight, "weight"), buf.data_ptr(), n, k, _stream()),
            "gdrnpp_pack_weight_f16x2")
     packed = buf[:n * k * 4].view(torch.float16).view(n // 128, k // 16, 2, 2, 128, 8)
     packed._gdrnpp_base = buf
@@ -695,8 +692,7 @@ def pack_mlp_fused_f16x2(w1, w2):
     if nbytes == 0:
         raise ValueError(f"the fused MLP exists for C = 128, hidden = 512, not {c} / {hidden}")
     buf = torch.empty((nbytes,), dtype=torch.uint8, device=w1.device)
-    _check(load().gdrnpp_pack_mlp_fused_f16x2(_dev(w1, torch.float32, "w1"), _dev(w2, torch.float32, "w2"), buf.data_ptr(), c, hidden,
-                                              _stream()), "gdrnpp_pack_mlp_fused_f16x2")
+    _check(load().gdrnpp_pack_mlp_fused_f16x2(_f32(w1, "w1"), _f32(w2, "w2"), buf.data_ptr(), c, hidden, _stream()), "gdrnpp_pack_mlp_fused_f16x2")
     return buf
 
 
@@ -712,9 +708,8 @@ def convnext_mlp_f32_fused(x2d, packed_buf, b1, b2, gamma, resid, slot_fc1: int 
     hidden = b1.shape[0]
     y = torch.empty((m, c), dtype=torch.float32, device=x2d.device)
     _count_x3()
-    args = (_dev(x2d, torch.float32, "x"), packed_buf.data_ptr(), _dev(b1, torch.float32, "b1"), _dev(b2, torch.float32, "b2"),
-            _dev(gamma, torch.float32, "gamma"), _dev(resid, torch.float32, "resid"), y.data_ptr(), m, c, hidden,
-            _x3_flag_ptr(slot_fc1), _x3_flag_ptr(slot_fc2), _stream())
+    args = (_f32(x2d, "x"), packed_buf.data_ptr(), _f32(b1, "b1"), _f32(b2, "b2"),
+            _f32(gamma, "gamma"), _f32(resid, "resid"), y.data_ptr(), m, c, hidden, _x3_flag_ptr(slot_fc1), _x3_flag_ptr(slot_fc2), _stream())
     nbytes = 4.0 * m * c * 3 + 8.0 * c * hidden       # x + residual + y, both weights once
     _check(_timed("mlp_fused" + X3, 4.0 * m * c * hidden, lambda: load().gdrnpp_convnext_mlp_f32_fused(*args), nbytes),
            "gdrnpp_convnext_mlp_f32_fused")
@@ -723,7 +718,7 @@ def convnext_mlp_f32_fused(x2d, packed_buf, b1, b2, gamma, resid, slot_fc1: int 
 
 def packed_rows_in_range(packed) -> bool:
     """False when gdrnpp_pack_weight_f16x2 found a non-zero weight row whose scaled rms is below 2^-4 (trailer word 3): the layer
-    belongs on the six-product kernels.  One 16-byte read-back, done once per packed weight (hip_layers caches it)."""
+    belongs on the six-product kernels.  One 16-byte read-back, done once per packed weight (x3_policy caches it)."""
     trailer = packed._gdrnpp_base[packed.numel() * 2:].view(torch.int32)
     return int(trailer[3].item()) == 0
 
@@ -800,13 +795,13 @@ def split2_tiles_ok(m: int, n: int) -> bool:
 
 # Range words of the three-product launches (include/gdrnpp_hip.h: GDRNPP_SPLIT2_NONFINITE | GDRNPP_SPLIT2_SMALL_ROWS).  Every
 # (device, stream) owns one i32[X3_SLOTS] device buffer; a launch ORs its word into the entry of its LAYER (slot numbers are
-# handed out by hip_layers.x3_slot, slot 0 = launches that name no layer), so that the reader knows which layer left the range.
+# handed out by x3_policy.slot, slot 0 = launches that name no layer), so that the reader knows which layer left the range.
 X3_SLOTS = 1024
 X3_NONFINITE, X3_SMALL_ROWS = 1, 2
 _X3_FLAGS = {}   # (device index, stream handle) -> i32[X3_SLOTS]
 
 
-def _x3_flags():
+def x3_flags():
     """The range words of the current device + stream (or of the enclosing x3_flag_scope)."""
     if _X3_FLAG_OVERRIDE is not None:
         return _X3_FLAG_OVERRIDE
@@ -818,7 +813,7 @@ def _x3_flags():
 
 
 def _x3_flag_ptr(slot: int) -> int:
-    f = _x3_flags()
+    f = x3_flags()
     return f.data_ptr() + 4 * (slot if 0 <= slot < f.numel() else 0)
 
 
@@ -854,7 +849,7 @@ def range_words_of(host_words) -> dict:
 def split2_range_words(reset: bool = True) -> dict:
     """{slot: word} of the layers whose three-product launches on the current stream left the fp16x2 range since the last reset
     (empty dict: all inside).  Synchronises the current stream (one X3_SLOTS * 4 byte read-back)."""
-    f = _x3_flags()
+    f = x3_flags()
     words = range_words_of(f.cpu())
     if words and reset:
         f.zero_()
@@ -919,10 +914,8 @@ def linear_f32_split(x2d, weight_packed, bias, epilogue: str = "none", gamma=Non
     n, fp16x2 = _packed_weight(weight_packed, k, "weight_packed must be the contiguous tensor from pack_weight_bf16x3 / pack_weight_f16x2 with matching K",
                                contiguous=True)
     out = torch.empty((m, n), dtype=torch.float32, device=x2d.device)
-    args = (_dev(x2d, torch.float32, "x"), weight_packed.data_ptr(),
-            _dev(bias, torch.float32, "bias") if bias is not None else None,
-            _dev(gamma, torch.float32, "gamma") if gamma is not None else None,
-            _dev(resid, torch.float32, "resid") if resid is not None else None, out.data_ptr(), m, n, k,
+    args = (_f32(x2d, "x"), weight_packed.data_ptr(),
+            _opt_f32(bias, "bias"), _opt_f32(gamma, "gamma"), _opt_f32(resid, "resid"), out.data_ptr(), m, n, k,
             _EPILOGUES[epilogue]) + \
         (((A_F16X2_ROWS if a_rows else 0) | (C_F16X2_ROWS if c_rows else 0), _x3_flag_ptr(x3_slot)) if fp16x2 else ()) + (_stream(),)
     if (a_rows or c_rows) and not fp16x2:
@@ -947,7 +940,7 @@ def linear_f32_split_grouped(x2d, weight_packed_stack, bias_stack, group_sel, ro
             or (weight_packed_stack.shape[0] * 128) % n:
         raise ValueError("weight_packed_stack must come from pack_weight_bf16x3 of the stacked [groups*N, K] weight")
     out = torch.empty((m, n), dtype=torch.float32, device=x2d.device)
-    args = (_dev(x2d, torch.float32, "x"), weight_packed_stack.data_ptr(), _dev(bias_stack, torch.float32, "bias_stack"),
+    args = (_f32(x2d, "x"), weight_packed_stack.data_ptr(), _f32(bias_stack, "bias_stack"),
             _dev(group_sel, torch.int32, "group_sel"), int(bias_stack.shape[0]), int(rows_per_group), out.data_ptr(), m, n, k,
             int(n_store if n_store is not None else n), _stream())
     nbytes = 4.0 * m * k + 6.0 * n * k * group_sel.numel() + 4.0 * m * (n_store or n)
@@ -961,9 +954,8 @@ def stem_conv4x4_ln(x_nchw, weight, bias, ln_weight, ln_bias, eps: float):
     n, cin, h, w = x_nchw.shape
     cout = weight.shape[0]
     out = torch.empty((n, cout, h // 4, w // 4), dtype=torch.float32, device=x_nchw.device, memory_format=torch.channels_last)
-    _check(load().gdrnpp_stem_conv4x4_ln(_dev(x_nchw, torch.float32, "x"), _dev(weight, torch.float32, "weight"),
-                                         _dev(bias, torch.float32, "bias") if bias is not None else None,
-                                         _dev(ln_weight, torch.float32, "ln_weight"), _dev(ln_bias, torch.float32, "ln_bias"),
+    _check(load().gdrnpp_stem_conv4x4_ln(_f32(x_nchw, "x"), _f32(weight, "weight"),
+                                         _opt_f32(bias, "bias"), _f32(ln_weight, "ln_weight"), _f32(ln_bias, "ln_bias"),
                                          out.data_ptr(), n, h, w, cout, float(eps), _stream()), "gdrnpp_stem_conv4x4_ln")
     return out
 
@@ -977,8 +969,8 @@ def head_tail_nhwc(out_nhwc, coord2d, extents, double_mask: bool):
     n_planes = 5 if double_mask else 4
     pnp_in = torch.empty((b, hw, 96), dtype=torch.float32, device=out_nhwc.device)
     planes = torch.empty((n_planes, b, hw), dtype=torch.float32, device=out_nhwc.device)
-    _check(load().gdrnpp_head_tail_nhwc(_dev(out_nhwc, torch.float32, "out_nhwc"), pitch, _dev(coord2d, torch.float32, "coord2d"),
-                                        _dev(extents, torch.float32, "extents"), pnp_in.data_ptr(), planes.data_ptr(), b, hw,
+    _check(load().gdrnpp_head_tail_nhwc(_f32(out_nhwc, "out_nhwc"), pitch, _f32(coord2d, "coord2d"),
+                                        _f32(extents, "extents"), pnp_in.data_ptr(), planes.data_ptr(), b, hw,
                                         1 if double_mask else 0, _stream()), "gdrnpp_head_tail_nhwc")
     return pnp_in, planes
 
@@ -993,9 +985,8 @@ def linear_f32_splitk(x2d, weight_packed, bias, epilogue: str = "none", gamma=No
     out = torch.empty((m, n), dtype=torch.float32, device=x2d.device)
     nbytes = load().gdrnpp_linear_f32_splitk_workspace_bytes(m, n, k)
     ws = torch.empty((nbytes,), dtype=torch.uint8, device=x2d.device)
-    args = (_dev(x2d, torch.float32, "x"), weight_packed.data_ptr(), _dev(bias, torch.float32, "bias") if bias is not None else None,
-            _dev(gamma, torch.float32, "gamma") if gamma is not None else None,
-            _dev(resid, torch.float32, "resid") if resid is not None else None, out.data_ptr(), m, n, k,
+    args = (_f32(x2d, "x"), weight_packed.data_ptr(), _opt_f32(bias, "bias"), _opt_f32(gamma, "gamma"),
+            _opt_f32(resid, "resid"), out.data_ptr(), m, n, k,
             _EPILOGUES[epilogue], ws.data_ptr(), nbytes, _stream())
     nb = 4.0 * m * k + 6.0 * n * k + 4.0 * m * n * (2 if epilogue == "scale_res" else 1)
     _check(_timed("linear_splitk", 2.0 * m * n * k, lambda: load().gdrnpp_linear_f32_splitk(*args), nb), "gdrnpp_linear_f32_splitk")
@@ -1037,12 +1028,12 @@ def conv2d_f32_split(x_cl, weight_packed, bias, kh: int, kw: int, stride: int, p
         if kh * kw > 32:
             raise ValueError("the three-product convolution takes at most 32 taps")
         _count_x3()
-        a2 = (x_cl.data_ptr(), weight_packed.data_ptr(), _dev(bias, torch.float32, "bias") if bias is not None else None,
+        a2 = (x_cl.data_ptr(), weight_packed.data_ptr(), _opt_f32(bias, "bias"),
               out.data_ptr(), n, h, w, cin, cout, kh, kw, stride, pad, 1 if gelu else 0, _x3_flag_ptr(x3_slot), _stream())
         _check(_timed(_kind + X3, 2.0 * n * oh * ow * cout * kh * kw * cin, lambda: load().gdrnpp_conv2d_f32_split2(*a2),
                       4.0 * n * (h * w * cin + oh * ow * cout) + 4.0 * cout * kh * kw * cin), "gdrnpp_conv2d_f32_split2")
         return out
-    args = (x_cl.data_ptr(), weight_packed.data_ptr(), _dev(bias, torch.float32, "bias") if bias is not None else None,
+    args = (x_cl.data_ptr(), weight_packed.data_ptr(), _opt_f32(bias, "bias"),
             out.data_ptr(), n, h, w, cin, cout, kh, kw, stride, pad, 1 if gelu else 0)
     nbytes = 4.0 * n * (h * w * cin + oh * ow * cout) + 6.0 * cout * kh * kw * cin
     flops = 2.0 * n * oh * ow * cout * kh * kw * cin
@@ -1068,7 +1059,7 @@ def bias_act_nhwc_(x_cl, bias, resid=None, relu: bool = True):
     if resid is not None and (resid.shape != x_cl.shape or not resid.is_contiguous(memory_format=torch.channels_last)
                               or resid.dtype != torch.float32 or resid.device != x_cl.device):
         raise ValueError("resid must match x (float32, channels_last, same device)")
-    _check(load().gdrnpp_bias_act_nhwc(x_cl.data_ptr(), _dev(bias, torch.float32, "bias"),
+    _check(load().gdrnpp_bias_act_nhwc(x_cl.data_ptr(), _f32(bias, "bias"),
                                        resid.data_ptr() if resid is not None else None, x_cl.data_ptr(), n * h * w, c,
                                        1 if relu else 0, _stream()), "gdrnpp_bias_act_nhwc")
     return x_cl
@@ -1102,7 +1093,7 @@ def conv_transpose2d_f32_split(x_cl, weight_packed, bias, ks: int, stride: int, 
     [N,Cout,OH,OW] (``weight_packed`` from pack_deconv_weight_bf16x3)."""
     n, _, h, w = x_cl.shape
     cols, y, cout, _, _ = _deconv_cols(x_cl, weight_packed, ks, stride, pad, out_pad, x3_slot, "conv_transpose2d_f32_split")
-    _check(load().gdrnpp_deconv_col2im_nhwc(cols.data_ptr(), _dev(bias, torch.float32, "bias") if bias is not None else None,
+    _check(load().gdrnpp_deconv_col2im_nhwc(cols.data_ptr(), _opt_f32(bias, "bias"),
                                             y.data_ptr(), n, h, w, cout, ks, stride, pad, out_pad, _stream()),
            "gdrnpp_deconv_col2im_nhwc")
     return y
@@ -1118,11 +1109,11 @@ def conv_transpose2d_groupnorm_act(x_cl, weight_packed, bias, ks: int, stride: i
     nbytes = load().gdrnpp_groupnorm_workspace_bytes(n, oh * ow, groups)
     P = nbytes // (16 * n * groups)
     part = torch.empty((n, P, groups, 2), dtype=torch.float64, device=x_cl.device)
-    _check(load().gdrnpp_deconv_col2im_gn_nhwc(cols.data_ptr(), _dev(bias, torch.float32, "bias") if bias is not None else None,
+    _check(load().gdrnpp_deconv_col2im_gn_nhwc(cols.data_ptr(), _opt_f32(bias, "bias"),
                                                y.data_ptr(), part.data_ptr(), n, h, w, cout, ks, stride, pad, out_pad, groups, _stream()),
            "gdrnpp_deconv_col2im_gn_nhwc")
     out = torch.empty_like(y)
-    a2 = (y.data_ptr(), part.data_ptr(), P, _dev(gamma, torch.float32, "gamma"), _dev(beta, torch.float32, "beta"),
+    a2 = (y.data_ptr(), part.data_ptr(), P, _f32(gamma, "gamma"), _f32(beta, "beta"),
           out.data_ptr(), n, oh * ow, cout, groups, float(eps), 1 if gelu else 0, _stream())
     _check(_timed("hbm:groupnorm_apply", 0.0, lambda: load().gdrnpp_groupnorm_apply_nhwc(*a2), 8.0 * y.numel()),
            "gdrnpp_groupnorm_apply_nhwc")
@@ -1135,9 +1126,8 @@ def pnp_fc_heads(x, w_r, b_r, w_t, b_t):
     rot_dim = w_r.shape[0]
     rot_ = torch.empty((b, rot_dim), dtype=torch.float32, device=x.device)
     t_ = torch.empty((b, 3), dtype=torch.float32, device=x.device)
-    _check(load().gdrnpp_pnp_fc_heads(_dev(x, torch.float32, "x"), _dev(w_r, torch.float32, "w_r"),
-                                      _dev(b_r, torch.float32, "b_r") if b_r is not None else None, _dev(w_t, torch.float32, "w_t"),
-                                      _dev(b_t, torch.float32, "b_t") if b_t is not None else None, rot_.data_ptr(), t_.data_ptr(),
+    _check(load().gdrnpp_pnp_fc_heads(_f32(x, "x"), _f32(w_r, "w_r"), _opt_f32(b_r, "b_r"), _f32(w_t, "w_t"),
+                                      _opt_f32(b_t, "b_t"), rot_.data_ptr(), t_.data_ptr(),
                                       b, k, rot_dim, _stream()), "gdrnpp_pnp_fc_heads")
     return rot_, t_
 
@@ -1161,8 +1151,7 @@ def point_pnp_pool(x2d, cin: int, w1, b1, w2, b2, w3, b3, b: int, hw: int, want_
         raise RuntimeError(f"point_pnp_pool: b={b} hw={hw}: hw must be a positive multiple of {POINT_PNP_TILE}")
     ws = torch.empty((nbytes // 4,), dtype=torch.float32, device=x2d.device)
     pooled = torch.empty((b, 1024), dtype=torch.float32, device=x2d.device) if want_pooled else None
-    f = lambda v, n: _dev(v, torch.float32, n)  # noqa: E731
-    a = (f(x2d, "x"), x2d.shape[1], cin, f(w1, "w1"), f(b1, "b1"), f(w2, "w2"), f(b2, "b2"), f(w3, "w3"), f(b3, "b3"),
+    a = (_f32(x2d, "x"), x2d.shape[1], cin, _f32(w1, "w1"), _f32(b1, "b1"), _f32(w2, "w2"), _f32(b2, "b2"), _f32(w3, "w3"), _f32(b3, "b3"),
          pooled.data_ptr() if want_pooled else None, b, hw, ws.data_ptr(), nbytes, _stream())
     _check(_timed("mfma_f32:point_pnp_pool", 2.0 * b * hw * (128 * cin + 128 * 128 + 1024 * 128), lambda: lib.gdrnpp_point_pnp_pool(*a)),
            "gdrnpp_point_pnp_pool")
@@ -1174,14 +1163,14 @@ def point_pnp_fc(ws, w_fc1, b_fc1, w_fc2, b_fc2, b: int, hw: int):
     if tuple(w_fc1.shape) != (512, 1024) or tuple(w_fc2.shape) != (256, 512) or b_fc1.numel() != 512 or b_fc2.numel() != 256:
         raise RuntimeError("point_pnp_fc: weights must be Linear(1024,512) and Linear(512,256) with biases")
     feat = torch.empty((b, 256), dtype=torch.float32, device=ws.device)
-    f = lambda v, n: _dev(v, torch.float32, n)  # noqa: E731
-    _check(load().gdrnpp_point_pnp_fc(f(ws, "workspace"), ws.numel() * 4, f(w_fc1, "w_fc1"), f(b_fc1, "b_fc1"), f(w_fc2, "w_fc2"),
-                                      f(b_fc2, "b_fc2"), feat.data_ptr(), b, hw, _stream()), "gdrnpp_point_pnp_fc")
+    _check(load().gdrnpp_point_pnp_fc(_f32(ws, "workspace"), ws.numel() * 4, _f32(w_fc1, "w_fc1"), _f32(b_fc1, "b_fc1"), _f32(w_fc2, "w_fc2"),
+                                      _f32(b_fc2, "b_fc2"), feat.data_ptr(), b, hw, _stream()), "gdrnpp_point_pnp_fc")
     return feat
 
 
 ROT_MODES = {"rot6d": 0, "quat": 1, "mat": 2, "log_quat": 3, "lie_vec": 4}
 T_MODES = {"centroid_z_rel": 0, "centroid_z_abs_z": 1, "centroid_z_abs": 2, "trans": 3}
+ROT_DIMS = {"rot6d": 6, "quat": 4, "mat": 9, "log_quat": 3, "lie_vec": 3}     # outputs of the rotation head per mode
 
 
 def pnp_fc_heads_pose(x, w_r, b_r, w_t, b_t, cams, centers=None, whs=None, resize_ratios=None, rot_mode: str = "rot6d",
@@ -1190,18 +1179,17 @@ def pnp_fc_heads_pose(x, w_r, b_r, w_t, b_t, cams, centers=None, whs=None, resiz
     R_ego f32[b,3,3], trans f32[b,3])."""
     b, k = x.shape
     rot_dim = w_r.shape[0]
-    if rot_dim != {0: 6, 1: 4, 2: 9, 3: 3, 4: 3}[ROT_MODES[rot_mode]]:
+    if rot_dim != ROT_DIMS[rot_mode]:
         raise ValueError(f"fc_r has {rot_dim} outputs, rot_mode {rot_mode!r} needs another count")
     dev = x.device
     rot_ = torch.empty((b, rot_dim), dtype=torch.float32, device=dev)
     t_ = torch.empty((b, 3), dtype=torch.float32, device=dev)
     rot = torch.empty((b, 3, 3), dtype=torch.float32, device=dev)
     trans = torch.empty((b, 3), dtype=torch.float32, device=dev)
-    opt = lambda v, n: _dev(v, torch.float32, n) if v is not None else None  # noqa: E731
     _check(load().gdrnpp_pnp_fc_heads_pose(
-        _dev(x, torch.float32, "x"), _dev(w_r, torch.float32, "w_r"), opt(b_r, "b_r"), _dev(w_t, torch.float32, "w_t"), opt(b_t, "b_t"),
-        rot_.data_ptr(), t_.data_ptr(), b, k, ROT_MODES[rot_mode], T_MODES[t_mode], _dev(cams, torch.float32, "cams"), opt(centers, "centers"),
-        opt(whs, "whs"), opt(resize_ratios, "resize_ratios"), rot.data_ptr(), trans.data_ptr(), 1 if is_allo else 0, _stream()),
+        _f32(x, "x"), _f32(w_r, "w_r"), _opt_f32(b_r, "b_r"), _f32(w_t, "w_t"), _opt_f32(b_t, "b_t"),
+        rot_.data_ptr(), t_.data_ptr(), b, k, ROT_MODES[rot_mode], T_MODES[t_mode], _f32(cams, "cams"), _opt_f32(centers, "centers"),
+        _opt_f32(whs, "whs"), _opt_f32(resize_ratios, "resize_ratios"), rot.data_ptr(), trans.data_ptr(), 1 if is_allo else 0, _stream()),
         "gdrnpp_pnp_fc_heads_pose")
     return rot_, t_, rot, trans
 
@@ -1218,8 +1206,7 @@ def conv3x3_groupnorm_act(x_cl, weight_packed, bias, gamma, beta, groups: int, e
         return None
     y = torch.empty((n, cout, h, w), dtype=torch.float32, device=x_cl.device, memory_format=torch.channels_last)
     part = torch.empty((n, P, groups, 2), dtype=torch.float64, device=x_cl.device)
-    args = (x_cl.data_ptr(), weight_packed.data_ptr(), _dev(bias, torch.float32, "bias") if bias is not None else None,
-            y.data_ptr(), part.data_ptr(), n, h, w, cin, cout, groups, _stream())
+    args = (x_cl.data_ptr(), weight_packed.data_ptr(), _opt_f32(bias, "bias"), y.data_ptr(), part.data_ptr(), n, h, w, cin, cout, groups, _stream())
     nbytes = 4.0 * n * h * w * (cin + cout) + (4.0 if fp16x2 else 6.0) * cout * 9 * cin
     if fp16x2:
         _count_x3()
@@ -1230,7 +1217,7 @@ def conv3x3_groupnorm_act(x_cl, weight_packed, bias, gamma, beta, groups: int, e
         _check(_timed("conv3x3", 2.0 * n * h * w * cout * 9 * cin, lambda: load().gdrnpp_conv3x3_f32_split_gnstats(*args), nbytes),
                "gdrnpp_conv3x3_f32_split_gnstats")
     out = torch.empty_like(y)
-    a2 = (y.data_ptr(), part.data_ptr(), P, _dev(gamma, torch.float32, "gamma"), _dev(beta, torch.float32, "beta"),
+    a2 = (y.data_ptr(), part.data_ptr(), P, _f32(gamma, "gamma"), _f32(beta, "beta"),
           out.data_ptr(), n, h * w, cout, groups, float(eps), 1 if gelu else 0, _stream())
     _check(_timed("hbm:groupnorm_apply", 0.0, lambda: load().gdrnpp_groupnorm_apply_nhwc(*a2), 8.0 * y.numel()),
            "gdrnpp_groupnorm_apply_nhwc")
@@ -1249,7 +1236,7 @@ def yolox_postprocess(det_preds, num_classes: int, conf_thre: float = 0.7, nms_t
     count = torch.zeros((b,), dtype=torch.int32, device=det_preds.device)
     nbytes = load().gdrnpp_yolox_postprocess_workspace_bytes(b, a)
     ws = torch.empty((nbytes,), dtype=torch.uint8, device=det_preds.device)
-    _check(load().gdrnpp_yolox_postprocess(_dev(det_preds, torch.float32, "det_preds"), b, a, num_classes, float(conf_thre),
+    _check(load().gdrnpp_yolox_postprocess(_f32(det_preds, "det_preds"), b, a, num_classes, float(conf_thre),
                                            float(nms_thre), 1 if class_agnostic else 0, dets.data_ptr(), count.data_ptr(), max_det,
                                            ws.data_ptr(), nbytes, _stream()), "gdrnpp_yolox_postprocess")
     return dets, count
@@ -1296,7 +1283,7 @@ def conv_bias_act_f32(a, a_off: int, cin: int, w_kmajor, bias, c, c_off: int, co
     if bias is not None and bias.numel() != cout:
         raise RuntimeError(f"conv_bias_act_f32: bias must hold {cout} values")
     args = (_nhwc_buf(a, "a"), lda, a_off, _nhwc_buf(w_kmajor, "weight"), w_kmajor.shape[1],
-            None if bias is None else _dev(bias, torch.float32, "bias"), None if res is None else _nhwc_buf(res, "res"),
+            _opt_f32(bias, "bias"), None if res is None else _nhwc_buf(res, "res"),
             0 if res is None else res.shape[-1], r_off, _nhwc_buf(c, "c"), ldc, c_off, c_img_rows, c_row0, b, h, w, cin, cout, ks, stride,
             CONV_ACTS[act], float(dec_stride), _stream())
     _check(_timed("mfma_f32:conv_bias_act", 2.0 * b * oh * ow * cout * ks * ks * cin, lambda: load().gdrnpp_conv_bias_act_f32(*args),
@@ -1309,7 +1296,7 @@ def yolox_focus(x_nchw, y, y_off: int = 0):
     b, ch, h, w = x_nchw.shape
     if ch != 3 or tuple(y.shape[:3]) != (b, h // 2, w // 2):
         raise RuntimeError(f"yolox_focus: x [B,3,H,W] -> y [B,H/2,W/2,ldy], got {tuple(x_nchw.shape)} -> {tuple(y.shape)}")
-    _check(load().gdrnpp_yolox_focus(_dev(x_nchw, torch.float32, "x"), _nhwc_buf(y, "y"), y.shape[-1], y_off, b, h, w, _stream()),
+    _check(load().gdrnpp_yolox_focus(_f32(x_nchw, "x"), _nhwc_buf(y, "y"), y.shape[-1], y_off, b, h, w, _stream()),
            "gdrnpp_yolox_focus")
     return y
 
@@ -1411,9 +1398,9 @@ def rois_from_dets(dets, count, ratio: float, H: int, W: int, cam, extents, dzi_
     ctab = gdrnpp_roi_table(**{k: _dev(table[k], ROI_TABLE_COLUMNS[k][0], k) for k in ROI_TABLE_COLUMNS})
     cnt = _dev(counts, torch.int32, "counts")
     _check(lib.gdrnpp_rois_from_dets(
-        _dev(dets, torch.float32, "dets"), _dev(count, torch.int32, "count"), b, max_det, extents.shape[0], float(ratio), int(H), int(W),
-        float(dzi_pad_scale), int(out_res), _dev(cam, torch.float32, "cam"), 1 if cam.dim() == 3 else 0,
-        _dev(extents, torch.float32, "extents"), float(score_thr), int(top_k_per_obj), int(cap), ctypes.byref(ctab), cnt, cnt + 4,
+        _f32(dets, "dets"), _dev(count, torch.int32, "count"), b, max_det, extents.shape[0], float(ratio), int(H), int(W),
+        float(dzi_pad_scale), int(out_res), _f32(cam, "cam"), 1 if cam.dim() == 3 else 0,
+        _f32(extents, "extents"), float(score_thr), int(top_k_per_obj), int(cap), ctypes.byref(ctab), cnt, cnt + 4,
         ws.data_ptr(), nbytes, _stream()), "gdrnpp_rois_from_dets")
     return table, counts
 
@@ -1425,7 +1412,7 @@ def paste_masks_rle(mask_probs, boxes_xyxy, im_h: int, im_w: int, threshold: flo
     while True:
         counts = torch.empty((b, max_runs), dtype=torch.int32, device=mask_probs.device)
         n_runs = torch.empty((b,), dtype=torch.int32, device=mask_probs.device)
-        _check(load().gdrnpp_paste_masks_rle(_dev(mask_probs, torch.float32, "mask_probs"), _dev(boxes_xyxy, torch.float32, "boxes"),
+        _check(load().gdrnpp_paste_masks_rle(_f32(mask_probs, "mask_probs"), _f32(boxes_xyxy, "boxes"),
                                              b, hm, wm, im_h, im_w, float(threshold), counts.data_ptr(), n_runs.data_ptr(), max_runs,
                                              _stream()), "gdrnpp_paste_masks_rle")
         n = n_runs.tolist()
@@ -1440,7 +1427,6 @@ def flow_forward(depth_src, depth_tgt, KT, Kinv):
     b, _, h, w = depth_src.shape
     flow = torch.empty((b, 2, h, w), dtype=torch.float32, device=depth_src.device)
     valid = torch.empty((b, 1, h, w), dtype=torch.float32, device=depth_src.device)
-    _check(load().gdrnpp_flow_forward(_dev(depth_src, torch.float32, "depth_src"), _dev(depth_tgt, torch.float32, "depth_tgt"),
-                                      _dev(KT, torch.float32, "KT"), _dev(Kinv, torch.float32, "Kinv"), flow.data_ptr(),
+    _check(load().gdrnpp_flow_forward(_f32(depth_src, "depth_src"), _f32(depth_tgt, "depth_tgt"), _f32(KT, "KT"), _f32(Kinv, "Kinv"), flow.data_ptr(),
                                       valid.data_ptr(), b, h, w, _stream()), "gdrnpp_flow_forward")
     return flow, valid

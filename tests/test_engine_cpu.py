@@ -388,7 +388,7 @@ def test_gemm_product_switch_and_range_word_policy(monkeypatch):
     import pytest
 
     from gdrnpp_bop2022_amd import hip_lib
-    from gdrnpp_bop2022_amd.gdrn_modeling import engine, hip_layers
+    from gdrnpp_bop2022_amd.gdrn_modeling import engine, hip_layers, x3_policy
 
     assert hip_layers.gemm_products() == 3
     with pytest.raises(ValueError):
@@ -396,8 +396,8 @@ def test_gemm_product_switch_and_range_word_policy(monkeypatch):
     assert hip_lib.split2_tiles_ok(128 * 256, 256) and not hip_lib.split2_tiles_ok(127 * 256, 256)
     assert hip_lib.split2_tiles_ok(64 * 256 + 1, 512) and not hip_lib.split2_tiles_ok(1 << 20, 192)
     # linear form: the A operand must stay below 4 GiB (32-bit lane offsets) — 128 ROIs of stage-0 fc2 do, 600 do not
-    assert hip_layers._use_x3(128 * 4096, 128, 512) and not hip_layers._use_x3(600 * 4096, 128, 512)
-    assert hip_layers._use_x3(600 * 4096, 256)            # convolutions address per pixel: no such limit
+    assert x3_policy.eligible(128 * 4096, 128, 512) and not x3_policy.eligible(600 * 4096, 128, 512)
+    assert x3_policy.eligible(600 * 4096, 256)            # convolutions address per pixel: no such limit
     seen = []
 
     def run():

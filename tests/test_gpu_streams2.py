@@ -122,7 +122,7 @@ def test_handles_belong_to_their_stream_and_a_flagged_step_is_repeated_there(set
         out = step()
         calls.append(torch.cuda.current_stream())
         if len(calls) == 1:
-            hip_lib._x3_flags()[0:1].fill_(hip_lib.X3_SMALL_ROWS)       # slot 0 (names no layer: nothing gets demoted); the current stream's words, stream-ordered behind the kernels
+            hip_lib.x3_flags()[0:1].fill_(hip_lib.X3_SMALL_ROWS)       # slot 0 (names no layer: nothing gets demoted); the current stream's words, stream-ordered behind the kernels
         return out
 
     try:

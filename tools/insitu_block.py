@@ -4,7 +4,7 @@ import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from gdrnpp_bop2022_amd import hip_lib
-from gdrnpp_bop2022_amd.gdrn_modeling import hip_layers
+from gdrnpp_bop2022_amd.gdrn_modeling import hip_layers, x3_policy
 from gdrnpp_bop2022_amd.gdrn_modeling.config import get_cfg
 from gdrnpp_bop2022_amd.gdrn_modeling.GDRN_double_mask import build_model_optimizer
 torch.manual_seed(0)
@@ -27,7 +27,8 @@ b = blocks[3]
 with torch.no_grad():
     xin = hip_layers.dwconv_ln(b.conv_dw, b.norm, x, b._cache)
     m = xin.numel() // 512
-    p1 = hip_layers._packed(b.mlp.fc1, b._cache, "fc1_pk"); p2 = hip_layers._packed(b.mlp.fc2, b._cache, "fc2_pk")
+    p1 = x3_policy.six_product_weight(b._cache, "fc1_pk", b.mlp.fc1.weight, hip_lib.pack_weight_bf16x3)
+    p2 = x3_policy.six_product_weight(b._cache, "fc2_pk", b.mlp.fc2.weight, hip_lib.pack_weight_bf16x3)
     x2 = xin.reshape(m, 512)
     h = hip_lib.linear_f32_split(x2, p1, b.mlp.fc1.bias, "gelu")
     sc = x.permute(0, 2, 3, 1).reshape(m, 512)

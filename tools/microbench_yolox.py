@@ -22,7 +22,7 @@ sys.path.insert(0, ROOT)
 
 from gdrnpp_bop2022_amd import hip_lib  # noqa: E402
 from gdrnpp_bop2022_amd.det.yolox.models import build_yolox  # noqa: E402
-from gdrnpp_bop2022_amd.gdrn_modeling import hip_layers  # noqa: E402
+from gdrnpp_bop2022_amd.gdrn_modeling import hip_layers, slice_layers  # noqa: E402
 
 F32_MATRIX_TFLOPS = 157.0
 DEV = "cuda"
@@ -108,7 +108,7 @@ def main():
         oh, ow = (h + 2 * (k // 2) - k) // s + 1, (w + 2 * (k // 2) - k) // s + 1
         yb = torch.empty(b, oh, ow, cout, device=DEV)
         with torch.no_grad():
-            hip_ms = timed(lambda: hip_layers.conv_bn_act_slice(conv, bn, "silu", hip_layers.NhwcSlice(xb), hip_layers.NhwcSlice(yb)), args.iters, args.repeats)
+            hip_ms = timed(lambda: slice_layers.conv_bn_act_slice(conv, bn, "silu", slice_layers.NhwcSlice(xb), slice_layers.NhwcSlice(yb)), args.iters, args.repeats)
             op_ms = timed(lambda: F.silu(bn(conv(x_cl))), args.iters, args.repeats)
         fl = 2.0 * b * oh * ow * cout * cin * k * k
         out["conv_shapes"].append(dict(cin=cin, cout=cout, k=k, stride=s, h=h, w=w, batch=b, layers=count, hip_ms=hip_ms, operators_ms=op_ms,
