@@ -1194,15 +1194,17 @@ def pnp_fc_heads_pose(x, w_r, b_r, w_t, b_t, cams, centers=None, whs=None, resiz
     return rot_, t_, rot, trans
 
 
-def conv3x3_groupnorm_act(x_cl, weight_packed, bias, gamma, beta, groups: int, eps: float = 1e-5, gelu: bool = False, x3_slot: int = 0):
+def conv3x3_groupnorm_act(x_cl, weight_packed, bias, gamma, beta, groups: int, eps: float = 1e-5, gelu: bool = False, x3_slot: int = 0,
+                          _min_tiles: int = 256):
     """conv3x3 (stride 1, pad 1) -> GroupNorm(groups) [-> GELU] of a channels_last tensor: the convolution's epilogue
     leaves the GroupNorm partial sums, the norm is one more pass (``gdrnpp_conv3x3_f32_split_gnstats`` +
     ``gdrnpp_groupnorm_apply_nhwc``).  Returns None when the shape is outside the fused form (H*W % 256, 8 channels
-    per group): the caller then runs the two layers separately."""
+    per group) or the launch has fewer than 256 tiles of 256 x 128 (a dispatch rule, not a limit of the kernels; ``_min_tiles`` is a
+    test / A-B knob like ``_kind``, not a tuning parameter: tests lower it to reach the kernels' smallest shape): the caller then runs the two layers separately."""
     n, cin, h, w = _channels_last_f32(x_cl, "conv3x3_groupnorm_act")
     cout, fp16x2 = _packed_weight(weight_packed, 9 * cin, "weight_packed must come from pack_conv_weight_bf16x3 / pack_conv_weight_f16x2 with matching Cin")
     P = load().gdrnpp_conv3x3_gnstats_partials(h, w)
-    if P <= 0 or cout != 8 * groups or (n * h * w // 256) * (cout // 128) < 256:   # below: the 128x128-tile kernels are faster
+    if P <= 0 or cout != 8 * groups or (n * h * w // 256) * (cout // 128) < _min_tiles:   # below: the 128x128-tile kernels are faster
         return None
     y = torch.empty((n, cout, h, w), dtype=torch.float32, device=x_cl.device, memory_format=torch.channels_last)
     part = torch.empty((n, P, groups, 2), dtype=torch.float64, device=x_cl.device)
