@@ -7,7 +7,7 @@ from .... import hip_lib
 
 
 def _chk(x, dtype, name):
-    return hip_lib._dev(x, dtype, name)
+    return hip_lib.dev_ptr(x, dtype, name)
 
 
 def _dims(direct, coords, third, last):
@@ -19,37 +19,37 @@ def _dims(direct, coords, third, last):
 def generate_hypothesis(direct, coords, idxs):
     tn, vn, hn = _dims(direct, coords, idxs, 2)
     hypo_pts = torch.empty((hn, vn, 2), dtype=torch.float32, device=direct.device)
-    hip_lib._check(hip_lib.load().gdrnpp_generate_hypothesis(
+    hip_lib.check(hip_lib.load().gdrnpp_generate_hypothesis(
         _chk(direct, torch.float32, "direct"), _chk(coords, torch.float32, "coords"), _chk(idxs, torch.int32, "idxs"),
-        hypo_pts.data_ptr(), tn, vn, hn, hip_lib._stream()), "generate_hypothesis")
+        hypo_pts.data_ptr(), tn, vn, hn, hip_lib.current_stream()), "generate_hypothesis")
     return hypo_pts
 
 
 def voting_for_hypothesis(direct, coords, hypo_pts, inliers, inlier_thresh):
     tn, vn, hn = _dims(direct, coords, hypo_pts, 2)
     assert inliers.shape == (hn, vn, tn)
-    hip_lib._check(hip_lib.load().gdrnpp_voting_for_hypothesis(
+    hip_lib.check(hip_lib.load().gdrnpp_voting_for_hypothesis(
         _chk(direct, torch.float32, "direct"), _chk(coords, torch.float32, "coords"),
         _chk(hypo_pts, torch.float32, "hypo_pts"), _chk(inliers, torch.uint8, "inliers"), tn, vn, hn,
-        float(inlier_thresh), hip_lib._stream()), "voting_for_hypothesis")
+        float(inlier_thresh), hip_lib.current_stream()), "voting_for_hypothesis")
 
 
 def generate_hypothesis_vanishing_point(direct, coords, idxs):
     tn, vn, hn = _dims(direct, coords, idxs, 2)
     hypo_pts = torch.empty((hn, vn, 3), dtype=torch.float32, device=direct.device)
-    hip_lib._check(hip_lib.load().gdrnpp_generate_hypothesis_vanishing_point(
+    hip_lib.check(hip_lib.load().gdrnpp_generate_hypothesis_vanishing_point(
         _chk(direct, torch.float32, "direct"), _chk(coords, torch.float32, "coords"), _chk(idxs, torch.int32, "idxs"),
-        hypo_pts.data_ptr(), tn, vn, hn, hip_lib._stream()), "generate_hypothesis_vanishing_point")
+        hypo_pts.data_ptr(), tn, vn, hn, hip_lib.current_stream()), "generate_hypothesis_vanishing_point")
     return hypo_pts
 
 
 def voting_for_hypothesis_vanishing_point(direct, coords, hypo_pts, inliers, inlier_thresh):
     tn, vn, hn = _dims(direct, coords, hypo_pts, 3)
     assert inliers.shape == (hn, vn, tn)
-    hip_lib._check(hip_lib.load().gdrnpp_voting_for_hypothesis_vanishing_point(
+    hip_lib.check(hip_lib.load().gdrnpp_voting_for_hypothesis_vanishing_point(
         _chk(direct, torch.float32, "direct"), _chk(coords, torch.float32, "coords"),
         _chk(hypo_pts, torch.float32, "hypo_pts"), _chk(inliers, torch.uint8, "inliers"), tn, vn, hn,
-        float(inlier_thresh), hip_lib._stream()), "voting_for_hypothesis_vanishing_point")
+        float(inlier_thresh), hip_lib.current_stream()), "voting_for_hypothesis_vanishing_point")
 
 
 def vote_count(direct, coords, hypo_pts, inlier_thresh):
@@ -57,8 +57,8 @@ def vote_count(direct, coords, hypo_pts, inlier_thresh):
     homo = hypo_pts.shape[2] == 3
     tn, vn, hn = _dims(direct, coords, hypo_pts, 3 if homo else 2)
     counts = torch.empty((hn, vn), dtype=torch.int32, device=direct.device)
-    hip_lib._check(hip_lib.load().gdrnpp_vote_count(
+    hip_lib.check(hip_lib.load().gdrnpp_vote_count(
         _chk(direct, torch.float32, "direct"), _chk(coords, torch.float32, "coords"),
         _chk(hypo_pts, torch.float32, "hypo_pts"), counts.data_ptr(), tn, vn, hn, float(inlier_thresh),
-        1 if homo else 0, hip_lib._stream()), "vote_count")
+        1 if homo else 0, hip_lib.current_stream()), "vote_count")
     return counts

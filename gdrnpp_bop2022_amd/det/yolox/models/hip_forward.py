@@ -56,7 +56,7 @@ def _csp(layer, src, dst, buf, name, h, w):
 
 def _plan(model, b, H, W, device) -> _Buffers:
     plans = model.__dict__.setdefault("_gdrnpp_yolox_buffers", {})
-    key = (b, H, W, device, hip_lib._stream())
+    key = (b, H, W, device, hip_lib.current_stream())
     buf = plans.get(key)
     if buf is None:
         if len(plans) >= _MAX_PLANS:

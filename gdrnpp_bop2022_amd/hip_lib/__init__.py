@@ -1,0 +1,42 @@
+"""ctypes binding of ``libgdrnpp_hip.so`` (the C ABI declared in ``include/gdrnpp_hip.h``).
+
+PyTorch is used here only as the owner of device memory and streams: every wrapper checks
+device / dtype / contiguity, then hands raw ``data_ptr()``s and the current HIP stream to the
+C entry point.  There is NO CPU fallback: if the shared library is missing or a call returns a
+non-zero status, a ``RuntimeError`` is raised (reference behaviour for misuse is
+``TORCH_CHECK`` -> ``RuntimeError``, ransac_voting.cpp:7-19).
+
+This file is the namespace and nothing else.  The modules, in dependency order (a module imports only from those in front of it):
+``abi`` (signature table, loader, pointer checks, the one launch path), ``dispatch`` (kernel-choice thresholds), ``range_words``
+(three-product range words and launch count), then one module per kernel family: ``gemm``, ``net``, ``pose``, ``roi``, ``yolox``.
+State that somebody assigns lives in its owner and is assigned there (``hip_lib.dispatch.SPLIT2_MIN_TILES = 1``); the three
+``SPLIT2_*`` thresholds can be READ here, always as the owner's current value.
+"""
+from . import abi, dispatch, gemm, net, pose, range_words, roi, yolox  # noqa: F401
+from .abi import (LIB_PATH, SIGNATURES, LaunchTimer, check, copy_d2d, current_stream, dev_ptr, gdrnpp_meshes,  # noqa: F401
+                  gdrnpp_roi_table, load, set_launch_timer, set_option, spin)
+from .dispatch import (set_conv_splitk, shared_min_rows, shared_min_tiles, shared_min_tiles_scope, split2_tiles_ok,  # noqa: F401
+                       split_gemm_tiles)
+from .gemm import (A_F16X2_ROWS, C_F16X2_ROWS, X3, conv2d_f32_split, conv3x3_f32_split, conv3x3_groupnorm_act,  # noqa: F401
+                   conv_transpose2d_f32_split, conv_transpose2d_groupnorm_act, convnext_mlp_f32_fused, f16x2_rows_decode,
+                   linear_f32_split, linear_f32_split_grouped, linear_f32_splitk, mlp_fused_rows_in_range, mlp_fused_supported,
+                   pack_conv3x3_weight_bf16x3, pack_conv_weight_bf16x3, pack_conv_weight_f16x2, pack_deconv_weight_bf16x3, pack_deconv_weight_f16x2,
+                   pack_mlp_fused_f16x2, pack_weight_bf16x3, pack_weight_f16x2, packed_rows_in_range, unpack_weight_bf16x3,
+                   unpack_weight_f16x2)
+from .net import (POINT_PNP_TILE, ROT_DIMS, ROT_MODES, T_MODES, bias_act_nhwc_, dwconv7x7_ln, groupnorm_act, head_tail_nhwc,  # noqa: F401
+                  layernorm_nhwc, pnp_fc_heads, pnp_fc_heads_pose, point_pnp_fc, point_pnp_pool, stem_conv4x4_ln, upsample_bilinear2x)
+from .pose import (MeshSet, decode_correspondences, depth_refine, epnp_batched, epnp_ransac, flow_forward, fps, nnd_backward,  # noqa: F401
+                   nnd_forward, pack_pose_records, paste_masks_rle, pnp_iter_from_correspondences, pose_from_pred,
+                   pose_from_pred_centroid_z, refine_kernel_name, refine_to_records, render_depth, set_refine_event_sink,
+                   uncertainty_pnp_batched, zoom_K)
+from .range_words import (X3_NONFINITE, X3_SLOTS, X3_SMALL_ROWS, range_words_of, split2_nonfinite, split2_range_words,  # noqa: F401
+                          x3_flag_ptr, x3_flag_scope, x3_flags, x3_launch_count)
+from .roi import ROI_TABLE_COLUMNS, crop_resize_roi, roi_align, roi_pool, roi_table, rois_from_dets  # noqa: F401
+from .yolox import (CONV_ACTS, conv_bias_act_f32, letterbox_sizes, pack_conv_weight_kmajor, spp_maxpool_5_9_13,  # noqa: F401
+                    upsample_nearest2x_slice, yolox_focus, yolox_letterbox, yolox_postprocess)
+
+
+def __getattr__(name):
+    if name in ("SPLIT2_MIN_TILES", "SPLIT2_SHARED_MIN_TILES", "SPLIT2_SHARED_MIN_ROWS"):
+        return getattr(dispatch, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

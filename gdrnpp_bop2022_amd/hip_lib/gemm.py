@@ -1,0 +1,296 @@
+"""The split-GEMM family: weight packing, linear / convolution / transposed-convolution launches in the six-product (bf16x3) and
+three-product (fp16x2) forms, the fused ConvNeXt MLP and the GEMM + GroupNorm pairs."""
+from __future__ import annotations
+
+import torch
+
+from . import dispatch
+from .abi import channels_last_f32, dev_ptr, f32_ptr, launch, load, opt_f32_ptr
+from .range_words import count_x3, x3_flag_ptr
+
+X3 = "_x3"   # LaunchTimer kind suffix of the three-product (fp16x2) kernels: 3 instead of 6 MFMA flops per fp32-equivalent flop
+A_F16X2_ROWS, C_F16X2_ROWS = 1, 2      # include/gdrnpp_hip.h
+_EPILOGUES = {"none": 0, "gelu": 1, "scale_res": 2}
+
+
+def f16x2_rows_decode(t: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    """(h, l) as float16 tensors of ``t``'s shape from an "f16x2 rows" tensor (tests / debugging): x ~ h + l."""
+    k = t.shape[-1]
+    v = t.contiguous().view(torch.float16).view(*t.shape[:-1], k // 8, 2, 8)
+    return v[..., 0, :].reshape(t.shape), v[..., 1, :].reshape(t.shape)
+
+
+def pack_weight_bf16x3(weight):
+    """nn.Linear weight f32[N,K] -> bf16[N/128, K/16, 3, 2, 128, 8]: exact 3-way bf16 split (w == h + m + l) of every
+    128x16 tile, laid out as gdrnpp_linear_f32_split stages it (split, k-block, row, 8 k)."""
+    n, k = weight.shape
+    packed = torch.empty((n // 128, k // 16, 3, 2, 128, 8), dtype=torch.bfloat16, device=weight.device)
+    launch("gdrnpp_pack_weight_bf16x3", f32_ptr(weight, "weight"), packed.data_ptr(), n, k)
+    return packed
+
+
+def pack_weight_f16x2(weight):
+    """nn.Linear weight f32[N,K] -> fp16[N/128, K/16, 2, 2, 128, 8]: two-way fp16 split (w * 2^e ~ h + l, 22 significant bits) of
+    every 128x16 tile for the three-product kernels (csrc/gemm_split2_pipe.hip).  The returned tensor is a VIEW of a buffer that
+    also carries the 16-byte trailer with the power-of-two scale behind the tiles: pass it on as it is (a copy loses the trailer)."""
+    n, k = weight.shape
+    nbytes = load().gdrnpp_pack_weight_f16x2_bytes(n, k)
+    buf = torch.empty((nbytes,), dtype=torch.uint8, device=weight.device)
+    launch("gdrnpp_pack_weight_f16x2", f32_ptr(weight, "weight"), buf.data_ptr(), n, k)
+    packed = buf[:n * k * 4].view(torch.float16).view(n // 128, k // 16, 2, 2, 128, 8)
+    packed._gdrnpp_base = buf
+    return packed
+
+
+def mlp_fused_supported(c: int, hidden: int) -> bool:
+    return load().gdrnpp_pack_mlp_fused_f16x2_bytes(int(c), int(hidden)) > 0
+
+
+def pack_mlp_fused_f16x2(w1, w2):
+    """fc1.weight f32[hidden,C], fc2.weight f32[C,hidden] -> the packed image of ``convnext_mlp_f32_fused`` (u8 buffer: per hidden
+    tile of 32 the fp16 h / l fragments of both layers in LDS order + a 32-byte trailer with the two power-of-two scales)."""
+    hidden, c = w1.shape
+    if tuple(w2.shape) != (c, hidden):
+        raise ValueError("pack_mlp_fused_f16x2: fc2.weight must be [C, hidden] for fc1.weight [hidden, C]")
+    nbytes = load().gdrnpp_pack_mlp_fused_f16x2_bytes(c, hidden)
+    if nbytes == 0:
+        raise ValueError(f"the fused MLP exists for C = 128, hidden = 512, not {c} / {hidden}")
+    buf = torch.empty((nbytes,), dtype=torch.uint8, device=w1.device)
+    launch("gdrnpp_pack_mlp_fused_f16x2", f32_ptr(w1, "w1"), f32_ptr(w2, "w2"), buf.data_ptr(), c, hidden)
+    return buf
+
+
+def mlp_fused_rows_in_range(packed_buf) -> tuple:
+    """(fc1 ok, fc2 ok): False when the pack kernel found a non-zero weight row of that layer below the three-product range."""
+    tr = packed_buf[-32:].view(torch.int32).cpu()
+    return int(tr[3]) == 0, int(tr[7]) == 0
+
+
+def convnext_mlp_f32_fused(x2d, packed_buf, b1, b2, gamma, resid, slot_fc1: int = 0, slot_fc2: int = 0):
+    """y = resid + gamma * fc2(gelu(fc1(x))) in one launch (``gdrnpp_convnext_mlp_f32_fused``, three-product form, C = 128)."""
+    m, c = x2d.shape
+    hidden = b1.shape[0]
+    y = torch.empty((m, c), dtype=torch.float32, device=x2d.device)
+    count_x3()
+    launch("gdrnpp_convnext_mlp_f32_fused", f32_ptr(x2d, "x"), packed_buf.data_ptr(), f32_ptr(b1, "b1"), f32_ptr(b2, "b2"),
+           f32_ptr(gamma, "gamma"), f32_ptr(resid, "resid"), y.data_ptr(), m, c, hidden, x3_flag_ptr(slot_fc1), x3_flag_ptr(slot_fc2),
+           timed=("mlp_fused" + X3, 4.0 * m * c * hidden, 4.0 * m * c * 3 + 8.0 * c * hidden))    # bytes: x + residual + y, both weights once
+    return y
+
+
+def packed_rows_in_range(packed) -> bool:
+    """False when gdrnpp_pack_weight_f16x2 found a non-zero weight row whose scaled rms is below 2^-4 (trailer word 3): the layer
+    belongs on the six-product kernels.  One 16-byte read-back, done once per packed weight (x3_policy caches it)."""
+    trailer = packed._gdrnpp_base[packed.numel() * 2:].view(torch.int32)
+    return int(trailer[3].item()) == 0
+
+
+def unpack_weight_f16x2(packed):
+    """For tests: (fp16[2, N, K] planes h / l of the SCALED weight, 2^-e) of a pack_weight_f16x2 result."""
+    tn, tk = packed.shape[:2]
+    planes = packed.permute(2, 0, 4, 1, 3, 5).reshape(2, tn * 128, tk * 16)
+    trailer = packed._gdrnpp_base[packed.numel() * 2:].view(torch.float32)
+    return planes, float(trailer[1])
+
+
+def unpack_weight_bf16x3(packed):
+    """Inverse view of pack_weight_bf16x3 for tests: bf16[3, N, K] planes."""
+    tn, tk = packed.shape[:2]
+    return packed.permute(2, 0, 4, 1, 3, 5).reshape(3, tn * 128, tk * 16)
+
+
+def pack_conv_weight_bf16x3(weight):
+    """nn.Conv2d weight f32[Cout,Cin,KH,KW] -> packed split image of the [Cout, (ky,kx,Cin)] GEMM weight."""
+    cout, cin, kh, kw = weight.shape
+    return pack_weight_bf16x3(weight.permute(0, 2, 3, 1).reshape(cout, kh * kw * cin).contiguous())
+
+
+pack_conv3x3_weight_bf16x3 = pack_conv_weight_bf16x3
+
+
+def pack_conv_weight_f16x2(weight):
+    """nn.Conv2d weight [Cout, Cin, KH, KW] -> pack_weight_f16x2 of the (tap, channel)-ordered [Cout, KH*KW*Cin] matrix."""
+    cout, cin, kh, kw = weight.shape
+    return pack_weight_f16x2(weight.detach().permute(0, 2, 3, 1).reshape(cout, kh * kw * cin).contiguous())
+
+
+def pack_deconv_weight_bf16x3(weight):
+    """nn.ConvTranspose2d weight [Cin, Cout, KS, KS] -> packed GEMM weight with rows (ky, kx, co), K = Cin."""
+    cin, cout, kh, kw = weight.shape
+    return pack_weight_bf16x3(weight.detach().permute(2, 3, 1, 0).reshape(kh * kw * cout, cin).contiguous())
+
+
+def pack_deconv_weight_f16x2(weight):
+    """pack_deconv_weight_bf16x3 in the three-product format."""
+    cin, cout, kh, kw = weight.shape
+    return pack_weight_f16x2(weight.detach().permute(2, 3, 1, 0).reshape(kh * kw * cout, cin).contiguous())
+
+
+def _packed_weight(weight_packed, k: int, what: str, contiguous: bool = False):
+    """Validate a packed split-GEMM weight with GEMM depth ``k`` (``contiguous``: and that it is contiguous); returns
+    (N, True for the three-product fp16x2 format).  ``what`` is the caller's message."""
+    fp16x2 = weight_packed.dtype == torch.float16     # pack_weight_f16x2: the three-product kernel
+    if weight_packed.dtype not in (torch.bfloat16, torch.float16) or weight_packed.dim() != 6 \
+            or (contiguous and not weight_packed.is_contiguous()) \
+            or weight_packed.shape[1] * 16 != k or weight_packed.shape[2] != (2 if fp16x2 else 3):
+        raise ValueError(what)
+    return weight_packed.shape[0] * 128, fp16x2
+
+
+def linear_f32_split(x2d, weight_packed, bias, epilogue: str = "none", gamma=None, resid=None, _kind: str = "linear", x3_slot: int = 0,
+                     a_rows: bool = False, c_rows: bool = False):
+    """out = epilogue(x2d @ W^T + bias) with the weight given as pack_weight_bf16x3(weight); runs on the bf16 matrix cores
+    with six partial products per fp32 product (fp32-accurate, see csrc/gemm_split.hip).  With a pack_weight_f16x2 weight: the
+    three-product kernel; there ``a_rows`` = x2d is an "f16x2 rows" tensor (epilogues gelu / scale_res), ``c_rows`` = write the
+    result as one (epilogues none / gelu) — gdrnpp_linear_f32_split2_rows, bit-identical to the fp32 hand-over."""
+    m, k = x2d.shape
+    n, fp16x2 = _packed_weight(weight_packed, k, "weight_packed must be the contiguous tensor from pack_weight_bf16x3 / pack_weight_f16x2 with matching K",
+                               contiguous=True)
+    out = torch.empty((m, n), dtype=torch.float32, device=x2d.device)
+    args = (f32_ptr(x2d, "x"), weight_packed.data_ptr(), opt_f32_ptr(bias, "bias"), opt_f32_ptr(gamma, "gamma"), opt_f32_ptr(resid, "resid"),
+            out.data_ptr(), m, n, k, _EPILOGUES[epilogue])
+    if (a_rows or c_rows) and not fp16x2:
+        raise ValueError("f16x2-rows tensors exist for the three-product kernel (pack_weight_f16x2) only")
+    nbytes = 4.0 * m * k + (4.0 if fp16x2 else 6.0) * n * k + 4.0 * m * n * (2 if epilogue == "scale_res" else 1)
+    if fp16x2:
+        count_x3()
+        launch("gdrnpp_linear_f32_split2_rows", *args, (A_F16X2_ROWS if a_rows else 0) | (C_F16X2_ROWS if c_rows else 0), x3_flag_ptr(x3_slot),
+               timed=(_kind + X3, 2.0 * m * n * k, nbytes))
+    else:
+        launch("gdrnpp_linear_f32_split", *args, timed=(_kind, 2.0 * m * n * k, nbytes))
+    return out
+
+
+def linear_f32_split_grouped(x2d, weight_packed_stack, bias_stack, group_sel, rows_per_group: int, n_store: int | None = None):
+    """out[m] = x2d[m] @ W[sel[m // rows_per_group]]^T + bias[sel[...]]: the class-sliced output layer of the geometry head.
+    ``weight_packed_stack`` = pack_weight_bf16x3 of the slices stacked along N ([groups * N, K]), ``bias_stack`` f32[groups, N],
+    ``group_sel`` i32[M / rows_per_group].  Returns f32[M, N]; columns >= n_store are left unwritten.  Rows whose selector is
+    outside [0, groups) come back as NaN (nothing is read out of bounds)."""
+    m, k = x2d.shape
+    n = bias_stack.shape[1]
+    if weight_packed_stack.dtype != torch.bfloat16 or weight_packed_stack.dim() != 6 or weight_packed_stack.shape[1] * 16 != k \
+            or (weight_packed_stack.shape[0] * 128) % n:
+        raise ValueError("weight_packed_stack must come from pack_weight_bf16x3 of the stacked [groups*N, K] weight")
+    out = torch.empty((m, n), dtype=torch.float32, device=x2d.device)
+    launch("gdrnpp_linear_f32_split_grouped", f32_ptr(x2d, "x"), weight_packed_stack.data_ptr(), f32_ptr(bias_stack, "bias_stack"),
+           dev_ptr(group_sel, torch.int32, "group_sel"), int(bias_stack.shape[0]), int(rows_per_group), out.data_ptr(), m, n, k,
+           int(n_store if n_store is not None else n),
+           timed=("linear_grouped", 2.0 * m * n * k, 4.0 * m * k + 6.0 * n * k * group_sel.numel() + 4.0 * m * (n_store or n)))
+    return out
+
+
+def linear_f32_splitk(x2d, weight_packed, bias, epilogue: str = "none", gamma=None, resid=None):
+    """Same contract as linear_f32_split for problems with few output tiles: split-K with a deterministic reduction that
+    also applies bias and epilogue."""
+    m, k = x2d.shape
+    if weight_packed.dtype != torch.bfloat16 or weight_packed.dim() != 6 or weight_packed.shape[1] * 16 != k:   # six-product only
+        raise ValueError("weight_packed must be the contiguous bf16 tensor from pack_weight_bf16x3 with matching K")
+    n = weight_packed.shape[0] * 128
+    out = torch.empty((m, n), dtype=torch.float32, device=x2d.device)
+    nbytes = load().gdrnpp_linear_f32_splitk_workspace_bytes(m, n, k)
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=x2d.device)
+    launch("gdrnpp_linear_f32_splitk", f32_ptr(x2d, "x"), weight_packed.data_ptr(), opt_f32_ptr(bias, "bias"), opt_f32_ptr(gamma, "gamma"),
+           opt_f32_ptr(resid, "resid"), out.data_ptr(), m, n, k, _EPILOGUES[epilogue], ws.data_ptr(), nbytes,
+           timed=("linear_splitk", 2.0 * m * n * k, 4.0 * m * k + 6.0 * n * k + 4.0 * m * n * (2 if epilogue == "scale_res" else 1)))
+    return out
+
+
+def conv2d_f32_split(x_cl, weight_packed, bias, kh: int, kw: int, stride: int, pad: int, gelu: bool = False, _kind: str = "conv",
+                     x3_slot: int = 0):
+    """KHxKW / stride / zero-pad convolution of a channels_last tensor [N,Cin,H,W] on the bf16 matrix cores (fp32-accurate
+    split GEMM, implicit im2col) -> channels_last [N,Cout,OH,OW]."""
+    n, cin, h, w = channels_last_f32(x_cl, "conv2d_f32_split")
+    cout, fp16x2 = _packed_weight(weight_packed, kh * kw * cin, "weight_packed must come from pack_conv_weight_bf16x3 / pack_conv_weight_f16x2 with matching Cin and kernel size")
+    oh, ow = (h + 2 * pad - kh) // stride + 1, (w + 2 * pad - kw) // stride + 1
+    out = torch.empty((n, cout, oh, ow), dtype=torch.float32, device=x_cl.device, memory_format=torch.channels_last)
+    if fp16x2 and kh * kw > 32:
+        raise ValueError("the three-product convolution takes at most 32 taps")
+    args = (x_cl.data_ptr(), weight_packed.data_ptr(), opt_f32_ptr(bias, "bias"),
+            out.data_ptr(), n, h, w, cin, cout, kh, kw, stride, pad, 1 if gelu else 0)
+    flops = 2.0 * n * oh * ow * cout * kh * kw * cin
+    nbytes = 4.0 * n * (h * w * cin + oh * ow * cout) + (4.0 if fp16x2 else 6.0) * cout * kh * kw * cin
+    if fp16x2:
+        count_x3()
+        launch("gdrnpp_conv2d_f32_split2", *args, x3_flag_ptr(x3_slot), timed=(_kind + X3, flops, nbytes))
+        return out
+    ws_bytes = load().gdrnpp_conv2d_f32_splitk_workspace_bytes(n, oh, ow, cin, cout, kh, kw) if dispatch._CONV_SPLITK else 0
+    if ws_bytes:    # few output tiles (small ROI batches): K in chunks, partial sums through a workspace
+        ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=x_cl.device)
+        launch("gdrnpp_conv2d_f32_splitk", *args, ws.data_ptr(), ws_bytes, timed=("conv_splitk", flops, nbytes))
+    else:
+        launch("gdrnpp_conv2d_f32_split", *args, timed=(_kind, flops, nbytes))
+    return out
+
+
+def conv3x3_f32_split(x_cl, weight_packed, bias, gelu: bool = False, x3_slot: int = 0):
+    """3x3 / stride 1 / pad 1 convolution of a channels_last tensor [N,Cin,H,W] on the bf16 matrix cores (fp32-accurate
+    split GEMM, implicit im2col) -> channels_last [N,Cout,H,W] (gdrnpp_conv3x3_f32_split = the general entry with 3, 3, 1, 1)."""
+    return conv2d_f32_split(x_cl, weight_packed, bias, 3, 3, 1, 1, gelu, _kind="conv3x3", x3_slot=x3_slot)
+
+
+def _deconv_cols(x_cl, weight_packed, ks: int, stride: int, pad: int, out_pad: int, x3_slot: int, what: str):
+    """First half of a transposed convolution: the GEMM into ``cols`` [N*H*W, KS*KS*Cout] and the empty channels_last result
+    the col2im gather fills; returns (cols, y, cout, oh, ow)."""
+    n, cin, h, w = channels_last_f32(x_cl, what)
+    cout = weight_packed.shape[0] * 128 // (ks * ks)
+    cols = linear_f32_split(x_cl.permute(0, 2, 3, 1).reshape(n * h * w, cin), weight_packed, None, _kind="deconv", x3_slot=x3_slot)
+    oh, ow = (h - 1) * stride - 2 * pad + ks + out_pad, (w - 1) * stride - 2 * pad + ks + out_pad
+    y = torch.empty((n, cout, oh, ow), dtype=torch.float32, device=x_cl.device, memory_format=torch.channels_last)
+    return cols, y, cout, oh, ow
+
+
+def conv_transpose2d_f32_split(x_cl, weight_packed, bias, ks: int, stride: int, pad: int, out_pad: int, x3_slot: int = 0):
+    """nn.ConvTranspose2d of a channels_last tensor [N,Cin,H,W] as split GEMM + col2im gather -> channels_last
+    [N,Cout,OH,OW] (``weight_packed`` from pack_deconv_weight_bf16x3)."""
+    n, _, h, w = x_cl.shape
+    cols, y, cout, _, _ = _deconv_cols(x_cl, weight_packed, ks, stride, pad, out_pad, x3_slot, "conv_transpose2d_f32_split")
+    launch("gdrnpp_deconv_col2im_nhwc", cols.data_ptr(), opt_f32_ptr(bias, "bias"), y.data_ptr(), n, h, w, cout, ks, stride, pad, out_pad)
+    return y
+
+
+def _groupnorm_apply(y, part, P: int, gamma, beta, n: int, hw: int, cout: int, groups: int, eps: float, gelu: bool):
+    """Second half of a GEMM + GroupNorm pair: normalise ``y`` with the partial sums the GEMM's epilogue / gather left in ``part``."""
+    out = torch.empty_like(y)
+    launch("gdrnpp_groupnorm_apply_nhwc", y.data_ptr(), part.data_ptr(), P, f32_ptr(gamma, "gamma"), f32_ptr(beta, "beta"),
+           out.data_ptr(), n, hw, cout, groups, float(eps), 1 if gelu else 0, timed=("hbm:groupnorm_apply", 0.0, 8.0 * y.numel()))
+    return out
+
+
+def conv_transpose2d_groupnorm_act(x_cl, weight_packed, bias, ks: int, stride: int, pad: int, out_pad: int, gamma, beta, groups: int,
+                                   eps: float = 1e-5, gelu: bool = False, x3_slot: int = 0):
+    """nn.ConvTranspose2d -> GroupNorm(groups) [-> GELU] of a channels_last tensor: split GEMM, then the col2im gather leaves the
+    GroupNorm partial sums (``gdrnpp_deconv_col2im_gn_nhwc``) and the norm is one more pass (``gdrnpp_groupnorm_apply_nhwc``) —
+    bitwise the result of conv_transpose2d_f32_split + groupnorm_act, one launch fewer."""
+    n, _, h, w = x_cl.shape
+    cols, y, cout, oh, ow = _deconv_cols(x_cl, weight_packed, ks, stride, pad, out_pad, x3_slot, "conv_transpose2d_groupnorm_act")
+    nbytes = load().gdrnpp_groupnorm_workspace_bytes(n, oh * ow, groups)
+    P = nbytes // (16 * n * groups)
+    part = torch.empty((n, P, groups, 2), dtype=torch.float64, device=x_cl.device)
+    launch("gdrnpp_deconv_col2im_gn_nhwc", cols.data_ptr(), opt_f32_ptr(bias, "bias"), y.data_ptr(), part.data_ptr(), n, h, w, cout, ks, stride,
+           pad, out_pad, groups)
+    return _groupnorm_apply(y, part, P, gamma, beta, n, oh * ow, cout, groups, eps, gelu)
+
+
+def conv3x3_groupnorm_act(x_cl, weight_packed, bias, gamma, beta, groups: int, eps: float = 1e-5, gelu: bool = False, x3_slot: int = 0,
+                          _min_tiles: int = 256):
+    """conv3x3 (stride 1, pad 1) -> GroupNorm(groups) [-> GELU] of a channels_last tensor: the convolution's epilogue
+    leaves the GroupNorm partial sums, the norm is one more pass (``gdrnpp_conv3x3_f32_split_gnstats`` +
+    ``gdrnpp_groupnorm_apply_nhwc``).  Returns None when the shape is outside the fused form (H*W % 256, 8 channels
+    per group) or the launch has fewer than 256 tiles of 256 x 128 (a dispatch rule, not a limit of the kernels; ``_min_tiles`` is a
+    test / A-B knob like ``_kind``, not a tuning parameter: tests lower it to reach the kernels' smallest shape): the caller then runs the two layers separately."""
+    n, cin, h, w = channels_last_f32(x_cl, "conv3x3_groupnorm_act")
+    cout, fp16x2 = _packed_weight(weight_packed, 9 * cin, "weight_packed must come from pack_conv_weight_bf16x3 / pack_conv_weight_f16x2 with matching Cin")
+    P = load().gdrnpp_conv3x3_gnstats_partials(h, w)
+    if P <= 0 or cout != 8 * groups or (n * h * w // 256) * (cout // 128) < _min_tiles:   # below: the 128x128-tile kernels are faster
+        return None
+    y = torch.empty((n, cout, h, w), dtype=torch.float32, device=x_cl.device, memory_format=torch.channels_last)
+    part = torch.empty((n, P, groups, 2), dtype=torch.float64, device=x_cl.device)
+    args = (x_cl.data_ptr(), weight_packed.data_ptr(), opt_f32_ptr(bias, "bias"), y.data_ptr(), part.data_ptr(), n, h, w, cin, cout, groups)
+    flops = 2.0 * n * h * w * cout * 9 * cin
+    nbytes = 4.0 * n * h * w * (cin + cout) + (4.0 if fp16x2 else 6.0) * cout * 9 * cin
+    if fp16x2:
+        count_x3()
+        launch("gdrnpp_conv3x3_f32_split2", *args, 0, x3_flag_ptr(x3_slot), timed=("conv3x3" + X3, flops, nbytes))
+    else:
+        launch("gdrnpp_conv3x3_f32_split_gnstats", *args, timed=("conv3x3", flops, nbytes))
+    return _groupnorm_apply(y, part, P, gamma, beta, n, h * w, cout, groups, eps, gelu)

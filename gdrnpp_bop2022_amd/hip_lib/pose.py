@@ -1,0 +1,291 @@
+"""Pose post-processing: the resident meshes, sampling and nearest-neighbour kernels, correspondence decoding, the PnP solvers,
+pose decoding, the depth renderer and refinement, pose records, flow and mask pasting."""
+from __future__ import annotations
+
+import ctypes
+
+import torch
+
+from .abi import dev_ptr, f32_ptr, gdrnpp_meshes, launch, load, opt_f32_ptr
+from .net import ROT_MODES, T_MODES
+
+
+class MeshSet:
+    """All object models of a dataset, flat and resident in HBM (``gdrnpp_meshes``)."""
+
+    def __init__(self, vertices: list, faces: list, device="cuda"):
+        import numpy as np
+
+        assert len(vertices) == len(faces) and len(vertices) > 0
+        v_off, f_off = [0], [0]
+        for v, f in zip(vertices, faces):
+            v_off.append(v_off[-1] + int(len(v)))
+            f_off.append(f_off[-1] + int(len(f)))
+        self.n_obj = len(vertices)
+        self.verts = torch.from_numpy(np.ascontiguousarray(np.concatenate(vertices, 0), np.float32)).to(device)
+        self.faces = torch.from_numpy(np.ascontiguousarray(np.concatenate(faces, 0), np.int32)).to(device)
+        self.vert_off = torch.tensor(v_off, dtype=torch.int32, device=device)
+        self.face_off = torch.tensor(f_off, dtype=torch.int32, device=device)
+        self.n_verts = v_off[1:]
+        self.n_faces = f_off[1:]
+        self._c = gdrnpp_meshes(self.verts.data_ptr(), self.faces.data_ptr(), self.vert_off.data_ptr(),
+                                self.face_off.data_ptr(), self.n_obj, max(len(v) for v in vertices),
+                                max(len(f) for f in faces))
+
+    @property
+    def c(self):
+        return ctypes.byref(self._c)
+
+    def bytes_per_render(self, obj: int) -> int:
+        return 12 * (self.n_verts[obj] - (self.n_verts[obj - 1] if obj else 0)) + 12 * (
+            self.n_faces[obj] - (self.n_faces[obj - 1] if obj else 0))
+
+
+def fps(pts: torch.Tensor, sn: int, init_center: bool = True, start_idx: torch.Tensor | None = None) -> torch.Tensor:
+    """pts f32[b,pn,3] -> idxs i32[b,sn]."""
+    lib = load()
+    assert pts.dim() == 3 and pts.shape[2] == 3
+    b, pn, _ = pts.shape
+    idxs = torch.empty((b, sn), dtype=torch.int32, device=pts.device)
+    ws_bytes = lib.gdrnpp_fps_workspace_bytes(b, pn)
+    ws = torch.empty((max(ws_bytes, 4),), dtype=torch.uint8, device=pts.device)
+    sp = dev_ptr(start_idx, torch.int32, "start_idx") if start_idx is not None else None
+    launch("gdrnpp_fps", f32_ptr(pts, "pts"), idxs.data_ptr(), sp, b, pn, sn, 1 if init_center else 0, ws.data_ptr())
+    return idxs
+
+
+def nnd_forward(xyz1, xyz2, dist1, dist2, idx1, idx2) -> int:
+    b, n, _ = xyz1.shape
+    m = xyz2.shape[1]
+    launch("gdrnpp_nnd_forward", f32_ptr(xyz1, "xyz1"), f32_ptr(xyz2, "xyz2"), f32_ptr(dist1, "dist1"), f32_ptr(dist2, "dist2"),
+           dev_ptr(idx1, torch.int32, "idx1"), dev_ptr(idx2, torch.int32, "idx2"), b, n, m)
+    return 1
+
+
+def nnd_backward(xyz1, xyz2, gradxyz1, gradxyz2, graddist1, graddist2, idx1, idx2) -> int:
+    b, n, _ = xyz1.shape
+    m = xyz2.shape[1]
+    launch("gdrnpp_nnd_backward", f32_ptr(xyz1, "xyz1"), f32_ptr(xyz2, "xyz2"), f32_ptr(gradxyz1, "gradxyz1"), f32_ptr(gradxyz2, "gradxyz2"),
+           f32_ptr(graddist1, "graddist1"), f32_ptr(graddist2, "graddist2"), dev_ptr(idx1, torch.int32, "idx1"),
+           dev_ptr(idx2, torch.int32, "idx2"), b, n, m)
+    return 1
+
+
+def uncertainty_pnp_batched(pts2d, pts3d, wgt2d, K, init_rt, return_info: bool = False):
+    b, pn, _ = pts2d.shape
+    out = torch.empty((b, 6), dtype=torch.float64, device=pts2d.device)
+    info = torch.zeros((b, 2), dtype=torch.int32, device=pts2d.device)
+    launch("gdrnpp_uncertainty_pnp_batched", dev_ptr(pts2d, torch.float64, "pts2d"), dev_ptr(pts3d, torch.float64, "pts3d"),
+           dev_ptr(wgt2d, torch.float64, "wgt2d"), dev_ptr(K, torch.float64, "K"), dev_ptr(init_rt, torch.float64, "init_rt"),
+           out.data_ptr(), info.data_ptr(), b, pn)
+    return (out, info) if return_info else out
+
+
+def decode_correspondences(coor_x, coor_y, coor_z, mask_raw, coord2d, extent, im_wh, mask_type: int = 0,
+                           mask_thr: float = 0.5, want_mask: bool = True):
+    """Maps [b,1,h,w] (or [b,h,w]) -> (count i32[b], sel_idx i32[b,hw], img_pts f32[b,hw,2], mdl_pts f32[b,hw,3],
+    out_mask f32[b,1,h,w] | None).  Rows >= count[b] are undefined."""
+    b = coor_x.shape[0]
+    hw = coor_x[0].numel()
+    dev = coor_x.device
+    count = torch.empty((b,), dtype=torch.int32, device=dev)
+    sel_idx = torch.empty((b, hw), dtype=torch.int32, device=dev)
+    img_pts = torch.empty((b, hw, 2), dtype=torch.float32, device=dev)
+    mdl_pts = torch.empty((b, hw, 3), dtype=torch.float32, device=dev)
+    out_mask = torch.empty_like(mask_raw) if want_mask else None
+    launch("gdrnpp_decode_correspondences", f32_ptr(coor_x, "coor_x"), f32_ptr(coor_y, "coor_y"), f32_ptr(coor_z, "coor_z"),
+           f32_ptr(mask_raw, "mask"), f32_ptr(coord2d, "coord2d"), f32_ptr(extent, "extent"), f32_ptr(im_wh, "im_wh"),
+           out_mask.data_ptr() if want_mask else None, count.data_ptr(), sel_idx.data_ptr(), img_pts.data_ptr(), mdl_pts.data_ptr(),
+           b, hw, mask_type, float(mask_thr))
+    return count, sel_idx, img_pts, mdl_pts, out_mask
+
+
+def pose_from_pred_centroid_z(rot6d, t_, cams, centers, whs, resize_ratios, z_type: str = "REL", is_allo: bool = True):
+    b = rot6d.shape[0]
+    rot = torch.empty((b, 3, 3), dtype=torch.float32, device=rot6d.device)
+    trans = torch.empty((b, 3), dtype=torch.float32, device=rot6d.device)
+    launch("gdrnpp_pose_from_pred_centroid_z", f32_ptr(rot6d, "rot6d"), f32_ptr(t_, "t_"), f32_ptr(cams, "cams"), f32_ptr(centers, "centers"),
+           f32_ptr(whs, "whs"), f32_ptr(resize_ratios, "resize_ratios"), rot.data_ptr(), trans.data_ptr(), b,
+           {"REL": 0, "ABS": 1}[z_type], 1 if is_allo else 0)
+    return rot, trans
+
+
+def pose_from_pred(rot_in, t_, cams, centers=None, whs=None, resize_ratios=None, rot_mode: str = "rot6d",
+                   t_mode: str = "centroid_z_rel", is_allo: bool = True):
+    """``gdrnpp_pose_from_pred``: every ROT_TYPE (rot6d / quat / log_quat / lie_vec / matrix) x TRANS_TYPE (centroid_z REL or
+    ABS, centroid_z_abs, trans) combination of GDRN_double_mask.py:162-200 -> (R_ego f32[b,3,3], t f32[b,3])."""
+    b = rot_in.shape[0]
+    rot = torch.empty((b, 3, 3), dtype=torch.float32, device=rot_in.device)
+    trans = torch.empty((b, 3), dtype=torch.float32, device=rot_in.device)
+    rm, tm = ROT_MODES[rot_mode], T_MODES[t_mode]
+    launch("gdrnpp_pose_from_pred", f32_ptr(rot_in, "rot_in"), rm, f32_ptr(t_, "t_"), tm, f32_ptr(cams, "cams"), opt_f32_ptr(centers, "centers"),
+           opt_f32_ptr(whs, "whs"), opt_f32_ptr(resize_ratios, "resize_ratios"), rot.data_ptr(), trans.data_ptr(), b, 1 if is_allo else 0)
+    return rot, trans
+
+
+def zoom_K(K, centers, scales, out_res: float):
+    b = K.shape[0]
+    out = torch.empty_like(K)
+    launch("gdrnpp_zoom_K", f32_ptr(K, "K"), f32_ptr(centers, "centers"), f32_ptr(scales, "scales"), out.data_ptr(), b, float(out_res))
+    return out
+
+
+def render_depth(meshes: MeshSet, obj, K, R, t, res: int, z_near: float = 0.1, z_far: float = 100.0,
+                 want_xyz: bool = False):
+    b = obj.shape[0]
+    depth = torch.empty((b, res, res), dtype=torch.float32, device=obj.device)
+    xyz = torch.empty((b, res, res, 3), dtype=torch.float32, device=obj.device) if want_xyz else None
+    launch("gdrnpp_render_depth", meshes.c, dev_ptr(obj, torch.int32, "obj"), f32_ptr(K, "K"), f32_ptr(R, "R"), f32_ptr(t, "t"), depth.data_ptr(),
+           xyz.data_ptr() if want_xyz else None, b, res, z_near, z_far)
+    return (depth, xyz) if want_xyz else depth
+
+
+_REFINE_EVENT_SINK = None
+
+
+def set_refine_event_sink(sink):
+    """bench.py's roofline pass: a list that receives one (start, stop) HIP event pair per depth-refine launch, recorded
+    on the launch stream (torch's current stream); None switches it off."""
+    global _REFINE_EVENT_SINK
+    _REFINE_EVENT_SINK = sink
+
+
+def refine_kernel_name() -> str:
+    return "depth_refine_kernel"
+
+
+def _launch_refine(name: str, meshes: MeshSet, b: int, device, *args) -> None:
+    """Launch a depth-refine entry point with ``args`` + the workspace it asks for; between two events when a sink is set."""
+    nbytes = load().gdrnpp_depth_refine_workspace_bytes(meshes.c, b)
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=device) if nbytes else None
+    sink = _REFINE_EVENT_SINK
+    if sink is not None:
+        ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+        ev[0].record()
+    launch(name, meshes.c, *args, ws.data_ptr() if ws is not None else None, nbytes)
+    if sink is not None:
+        ev[1].record()
+        sink.append(ev)
+
+
+def depth_refine(meshes: MeshSet, obj, coor_x, coor_y, coor_z, mask_raw, roi_depth, K_crop, R, t, res: int = 64,
+                 iters: int = 2, threshold: float = 0.8, mask_type: int = 0, use_coor_z: bool = False,
+                 z_near: float = 0.1, z_far: float = 100.0, debug: bool = False, out: torch.Tensor | None = None):
+    """-> t_refined f64[b,3] (and the per-iteration renders f32[b,iters,res,res] when debug)."""
+    b = obj.shape[0]
+    t_out = out if out is not None else torch.empty((b, 3), dtype=torch.float64, device=obj.device)
+    dbg = torch.zeros((b, iters, res, res), dtype=torch.float32, device=obj.device) if debug else None
+    if roi_depth.shape[-1] != roi_depth.shape[-2]:
+        raise RuntimeError(f"depth_refine: roi_depth must be square, got {tuple(roi_depth.shape[-2:])}")
+    _launch_refine(
+        "gdrnpp_depth_refine", meshes, b, obj.device, dev_ptr(obj, torch.int32, "obj"), f32_ptr(coor_x, "coor_x"), f32_ptr(coor_y, "coor_y"), f32_ptr(coor_z, "coor_z"),
+        f32_ptr(mask_raw, "mask"), f32_ptr(roi_depth, "roi_depth"), f32_ptr(K_crop, "K_crop"), f32_ptr(R, "R"), f32_ptr(t, "t"),
+        dev_ptr(t_out, torch.float64, "t_out"), dbg.data_ptr() if debug else None,
+        b, res, int(roi_depth.shape[-1]), iters, float(threshold), mask_type, 1 if use_coor_z else 0, z_near, z_far)
+    return (t_out, dbg) if debug else t_out
+
+
+def refine_to_records(meshes: MeshSet, obj, coor_x, coor_y, coor_z, mask_raw, roi_depth, cam, center, scale, R, t, score=None,
+                      roi_id=None, res: int = 64, iters: int = 2, threshold: float = 0.8, mask_type: int = 0,
+                      use_coor_z: bool = False, z_near: float = 0.1, z_far: float = 100.0):
+    """The refine configuration's post-processing tail in ONE launch (``gdrnpp_refine_to_records``): K_crop from cam /
+    center / scale, the depth refinement, and the f32[b,16] pose records."""
+    b = obj.shape[0]
+    rec = torch.empty((b, 16), dtype=torch.float32, device=obj.device)
+    if b == 0:
+        return rec
+    _launch_refine(
+        "gdrnpp_refine_to_records", meshes, b, obj.device, dev_ptr(obj, torch.int32, "obj"), f32_ptr(coor_x, "coor_x"), f32_ptr(coor_y, "coor_y"), f32_ptr(coor_z, "coor_z"),
+        f32_ptr(mask_raw, "mask"), f32_ptr(roi_depth, "roi_depth"), f32_ptr(cam, "cam"), f32_ptr(center, "center"), f32_ptr(scale, "scale"),
+        f32_ptr(R, "R"), f32_ptr(t, "t"), opt_f32_ptr(score, "score"),
+        dev_ptr(roi_id, torch.int32, "roi_id") if roi_id is not None else None, rec.data_ptr(),
+        b, res, int(roi_depth.shape[-1]), iters, float(threshold), mask_type, 1 if use_coor_z else 0, z_near, z_far)
+    return rec
+
+
+def pack_pose_records(R, t_refined, t_net, score, obj_id, roi_id):
+    b = R.shape[0]
+    rec = torch.empty((b, 16), dtype=torch.float32, device=R.device)
+    launch("gdrnpp_pack_pose_records", f32_ptr(R, "R"), dev_ptr(t_refined, torch.float64, "t_refined") if t_refined is not None else None,
+           opt_f32_ptr(t_net, "t_net"), opt_f32_ptr(score, "score"), dev_ptr(obj_id, torch.int32, "obj_id") if obj_id is not None else None,
+           dev_ptr(roi_id, torch.int32, "roi_id") if roi_id is not None else None, rec.data_ptr(), b)
+    return rec
+
+
+def pnp_iter_from_correspondences(img_pts, mdl_pts, count, K, R_net, t_net, return_info: bool = False):
+    """Net-initialised iterative PnP (gdrn_evaluator.py:241-371, pnp_type="iter") for all ROIs at once."""
+    b, stride, _ = img_pts.shape
+    R_out = torch.empty((b, 3, 3), dtype=torch.float32, device=img_pts.device)
+    t_out = torch.empty((b, 3), dtype=torch.float32, device=img_pts.device)
+    info = torch.zeros((b, 2), dtype=torch.int32, device=img_pts.device)
+    launch("gdrnpp_pnp_iter_from_correspondences", f32_ptr(img_pts, "img_pts"), f32_ptr(mdl_pts, "mdl_pts"), dev_ptr(count, torch.int32, "count"),
+           stride, f32_ptr(K, "K"), f32_ptr(R_net, "R_net"), f32_ptr(t_net, "t_net"), R_out.data_ptr(), t_out.data_ptr(), info.data_ptr(), b)
+    return (R_out, t_out, info) if return_info else (R_out, t_out)
+
+
+def epnp_ransac(img_pts, mdl_pts, count, K, iters: int = 100, reproj_err: float = 3.0, confidence: float = 0.99,
+                draws: "torch.Tensor | None" = None):
+    """cv2.solvePnPRansac(flags=SOLVEPNP_EPNP) for every ROI (``gdrnpp_epnp_ransac``): img_pts f32[b,stride,2], mdl_pts
+    f32[b,stride,3], count i32[b] (``decode_correspondences`` outputs), K f32[b,9|3,3]; ``draws`` i32/u32[b,n] injects the
+    random words of the minimal sets (default: OpenCV's fixed-seed cv::RNG).  -> (R f32[b,3,3], t f32[b,3], n_inliers
+    i32[b], status i32[b], inlier_mask u8[b,stride])."""
+    b, stride, _ = img_pts.shape
+    dev = img_pts.device
+    Rm = torch.empty((b, 3, 3), dtype=torch.float32, device=dev)
+    t = torch.empty((b, 3), dtype=torch.float32, device=dev)
+    n_inl = torch.empty((b,), dtype=torch.int32, device=dev)
+    status = torch.empty((b,), dtype=torch.int32, device=dev)
+    mask = torch.empty((b, stride), dtype=torch.uint8, device=dev)
+    if b == 0:
+        return Rm, t, n_inl, status, mask
+    nbytes = load().gdrnpp_epnp_ransac_workspace_bytes(b, stride, iters)
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    n_draws = 0
+    if draws is not None:
+        if draws.dtype not in (torch.int32, torch.uint32) or not draws.is_cuda or not draws.is_contiguous() or draws.shape[0] != b:
+            raise RuntimeError("draws must be a contiguous 32-bit integer CUDA(HIP) tensor [b, n_words]")
+        n_draws = int(draws.shape[1])
+    launch("gdrnpp_epnp_ransac", f32_ptr(img_pts, "img_pts"), f32_ptr(mdl_pts, "mdl_pts"), dev_ptr(count, torch.int32, "count"),
+           stride, f32_ptr(K.reshape(b, 9), "K"), draws.data_ptr() if draws is not None else None, n_draws, int(iters),
+           float(reproj_err), float(confidence), Rm.data_ptr(), t.data_ptr(), n_inl.data_ptr(), status.data_ptr(), mask.data_ptr(),
+           b, ws.data_ptr(), nbytes)
+    return Rm, t, n_inl, status, mask
+
+
+def epnp_batched(img_pts, mdl_pts, K):
+    """Plain EPnP on all n >= 4 points of each problem: img_pts f32[b,n,2], mdl_pts f32[b,n,3], K f32[b,9|3,3]
+    -> (R f32[b,3,3], t f32[b,3], status i32[b])."""
+    b, n, _ = img_pts.shape
+    dev = img_pts.device
+    Rm = torch.empty((b, 3, 3), dtype=torch.float32, device=dev)
+    t = torch.empty((b, 3), dtype=torch.float32, device=dev)
+    status = torch.empty((b,), dtype=torch.int32, device=dev)
+    launch("gdrnpp_epnp_batched", f32_ptr(img_pts, "img_pts"), f32_ptr(mdl_pts, "mdl_pts"), n, f32_ptr(K.reshape(b, 9), "K"), Rm.data_ptr(),
+           t.data_ptr(), status.data_ptr(), b)
+    return Rm, t, status
+
+
+def paste_masks_rle(mask_probs, boxes_xyxy, im_h: int, im_w: int, threshold: float = 0.5, max_runs: int = 4096):
+    """mask_probs f32[B,hm,wm], boxes f32[B,4] (device) -> list of B uncompressed COCO count lists (column-major, first
+    run = zeros).  The launch is repeated with a larger buffer if an instance needs more than ``max_runs`` runs."""
+    b, hm, wm = mask_probs.shape
+    while True:
+        counts = torch.empty((b, max_runs), dtype=torch.int32, device=mask_probs.device)
+        n_runs = torch.empty((b,), dtype=torch.int32, device=mask_probs.device)
+        launch("gdrnpp_paste_masks_rle", f32_ptr(mask_probs, "mask_probs"), f32_ptr(boxes_xyxy, "boxes"), b, hm, wm, im_h, im_w, float(threshold),
+               counts.data_ptr(), n_runs.data_ptr(), max_runs)
+        n = n_runs.tolist()
+        if max(n) <= max_runs:
+            c = counts.cpu().numpy().view("uint32")
+            return [c[i, :n[i]].astype("int64").tolist() for i in range(b)]
+        max_runs = max(n)
+
+
+def flow_forward(depth_src, depth_tgt, KT, Kinv):
+    """depth f32[B,1,H,W] x2, KT f32[B,3,4], Kinv f32[B,3,3] (device) -> flow f32[B,2,H,W], valid f32[B,1,H,W]."""
+    b, _, h, w = depth_src.shape
+    flow = torch.empty((b, 2, h, w), dtype=torch.float32, device=depth_src.device)
+    valid = torch.empty((b, 1, h, w), dtype=torch.float32, device=depth_src.device)
+    launch("gdrnpp_flow_forward", f32_ptr(depth_src, "depth_src"), f32_ptr(depth_tgt, "depth_tgt"), f32_ptr(KT, "KT"), f32_ptr(Kinv, "Kinv"),
+           flow.data_ptr(), valid.data_ptr(), b, h, w)
+    return flow, valid

@@ -117,4 +117,4 @@ def test_wrappers_reject_cpu_tensors():
     from gdrnpp_bop2022_amd import hip_lib
 
     with pytest.raises(RuntimeError, match="CUDA"):
-        hip_lib._dev(torch.zeros(3), torch.float32, "x")
+        hip_lib.dev_ptr(torch.zeros(3), torch.float32, "x")

@@ -700,15 +700,15 @@ def test_three_product_tile_rule_alone_and_on_a_shared_chip():
 
     old = (hip_lib.SPLIT2_MIN_TILES, hip_lib.SPLIT2_SHARED_MIN_TILES, hip_lib.SPLIT2_SHARED_MIN_ROWS)
     try:
-        hip_lib.SPLIT2_MIN_TILES, hip_lib.SPLIT2_SHARED_MIN_TILES, hip_lib.SPLIT2_SHARED_MIN_ROWS = 256, 0, 4096
+        hip_lib.dispatch.SPLIT2_MIN_TILES, hip_lib.dispatch.SPLIT2_SHARED_MIN_TILES, hip_lib.dispatch.SPLIT2_SHARED_MIN_ROWS = 256, 0, 4096
         assert hip_lib.split2_tiles_ok(128 * 256, 256) and not hip_lib.split2_tiles_ok(127 * 256, 256)      # 256 / 254 tiles
         assert not hip_lib.split2_tiles_ok(32768, 128) and not hip_lib.split2_tiles_ok(1 << 20, 192)
-        hip_lib.SPLIT2_SHARED_MIN_TILES = 128
+        hip_lib.dispatch.SPLIT2_SHARED_MIN_TILES = 128
         assert hip_lib.split2_tiles_ok(32768, 128)                  # 128 tiles, 32768 rows (Patch-PnP's second convolution at 128 ROIs)
         assert not hip_lib.split2_tiles_ok(2048, 2048)              # 128 tiles but 8 row tiles only (stage-2 fc1 at 8 ROIs): stays six-product
         assert not hip_lib.split2_tiles_ok(32768 - 256, 128) and not hip_lib.split2_tiles_ok(1 << 20, 192)
     finally:
-        hip_lib.SPLIT2_MIN_TILES, hip_lib.SPLIT2_SHARED_MIN_TILES, hip_lib.SPLIT2_SHARED_MIN_ROWS = old
+        hip_lib.dispatch.SPLIT2_MIN_TILES, hip_lib.dispatch.SPLIT2_SHARED_MIN_TILES, hip_lib.dispatch.SPLIT2_SHARED_MIN_ROWS = old
 
 
 def test_default_compute_streams_looks_at_the_post_processing_branch_too():

@@ -262,7 +262,7 @@ def three_products(hip):
     range_check._X3_OVERFLOW_STEPS = 0
     yield hip_layers
     hip_layers.set_gemm_products(old_products)          # what the session ran before (the library default: 3)
-    hip.SPLIT2_MIN_TILES = old_tiles
+    hip.dispatch.SPLIT2_MIN_TILES = old_tiles
     hip_layers.reset_x3_demotions()
     range_check._X3_OVERFLOW_STEPS = 0
 
@@ -273,7 +273,7 @@ def test_network_with_three_products_matches_reference_forward(hip, three_produc
     from gdrnpp_bop2022_amd.gdrn_modeling.config import get_cfg
     from gdrnpp_bop2022_amd.gdrn_modeling.GDRN_double_mask import build_model_optimizer
 
-    hip.SPLIT2_MIN_TILES = 1
+    hip.dispatch.SPLIT2_MIN_TILES = 1
     fx = NG.load_fixture(ds)
     model, _ = build_model_optimizer(get_cfg(NG.cfg_name(ds), opts=["TEST.USE_DEPTH_REFINE=True"]))
     model.load_state_dict(NG.seeded_reference_state_dict(model, fx), strict=True)
@@ -453,7 +453,7 @@ def test_small_scale_layer_input_moves_that_layer_to_six_products(hip, three_pro
     from gdrnpp_bop2022_amd.gdrn_modeling.backbones import Mlp
 
     hip_layers = three_products
-    hip.SPLIT2_MIN_TILES = 1
+    hip.dispatch.SPLIT2_MIN_TILES = 1
     torch.manual_seed(21)
     c = 128
     mlp = Mlp(c, 4 * c).cuda().eval()

@@ -146,7 +146,7 @@ def test_split_weight_returns_what_the_inline_form_returned(case, want):
 
     x3_policy.reset()
     try:
-        with mock.patch.object(hip_lib, "packed_rows_in_range", lambda packed: in_range), mock.patch.object(hip_lib, "SPLIT2_MIN_TILES", 256):
+        with mock.patch.object(hip_lib, "packed_rows_in_range", lambda packed: in_range), mock.patch.object(hip_lib.dispatch, "SPLIT2_MIN_TILES", 256):
             cache = {}
             assert x3_policy.slot({}, "conv") == 1           # another layer launched first
             if is_demoted:

@@ -14,7 +14,7 @@ state = B.build_state(args, ["ycbv_convnext_a6"], True, "refine", b, 0, dev, 0)
 m = [o for o in gc.get_objects() if isinstance(o, dict) and "model" in o and "batches" in o and "post" in o][0]
 model, post, batches = m["model"], m["post"], m["batches"]
 def run(rule, products=3):
-    hip_lib.SPLIT2_SHARED_MIN_TILES = rule
+    hip_lib.dispatch.SPLIT2_SHARED_MIN_TILES = rule
     with hip_layers.forced_gemm_products(products):
         recs, nets = [], []
         for bt in batches:
@@ -23,7 +23,7 @@ def run(rule, products=3):
                 out = model(bt["roi_img"], roi_classes=bt["roi_cls"], roi_cams=bt["roi_cam"], roi_whs=bt["roi_wh"], roi_centers=bt["roi_center"],
                             resize_ratios=bt["resize_ratio"], roi_coord_2d=bt.get("roi_coord_2d"), roi_extents=bt.get("roi_extent"))
             nets.append((out["rot"].clone().to(dev), out["trans"].clone()))
-    hip_lib.SPLIT2_SHARED_MIN_TILES = 0
+    hip_lib.dispatch.SPLIT2_SHARED_MIN_TILES = 0
     return recs, nets
 r_off, n_off = run(0); r_on, n_on = run(128); r_6, n_6 = run(0, 6)
 for name, (ra, na), (rb, nb) in (("rule on vs rule off", (r_on, n_on), (r_off, n_off)), ("rule on vs six products", (r_on, n_on), (r_6, n_6)), ("rule off vs six products", (r_off, n_off), (r_6, n_6))):

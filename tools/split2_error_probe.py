@@ -49,7 +49,7 @@ def network_level():
         for name in ("six products", "three products", "vendor fp32"):
             hip_layers.set_enabled(name != "vendor fp32")
             hip_layers.set_gemm_products(3 if name == "three products" else 6)
-            hip.SPLIT2_MIN_TILES = 1 if name == "three products" else 256
+            hip.dispatch.SPLIT2_MIN_TILES = 1 if name == "three products" else 256
             with torch.no_grad():
                 out = {k: v.cpu().numpy().astype(np.float64) for k, v in model(x, **kw).items()}
             e = {k: np.abs(out[k] - fx[k]).max() / np.abs(fx[k]).max() for k in ("mask", "full_mask", "coor_x", "coor_y", "coor_z")}
@@ -58,7 +58,7 @@ def network_level():
                   f"   rot {np.abs(out['rot'] - fx['rot']).max():.1e}  trans {np.abs(out['trans'] - fx['trans']).max():.1e}")
         hip_layers.set_enabled(True)
         hip_layers.set_gemm_products(6)
-        hip.SPLIT2_MIN_TILES = 256
+        hip.dispatch.SPLIT2_MIN_TILES = 256
 
 
 network_level()

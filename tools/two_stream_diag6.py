@@ -32,11 +32,11 @@ y = torch.empty((n, cout, h, w), dtype=torch.float32, device=dev, memory_format=
 part = torch.empty((n, P, groups, 2), dtype=torch.float64, device=dev)
 out = torch.empty_like(y)
 def gemm():
-    hip_lib._check(lib.gdrnpp_conv3x3_f32_split2(x.data_ptr(), w_pk.data_ptr(), None, y.data_ptr(), part.data_ptr(), n, h, w, cin, cout, groups, 0,
-                                                 hip_lib._x3_flag_ptr(slot), hip_lib._stream()), "gemm")
+    hip_lib.check(lib.gdrnpp_conv3x3_f32_split2(x.data_ptr(), w_pk.data_ptr(), None, y.data_ptr(), part.data_ptr(), n, h, w, cin, cout, groups, 0,
+                                                 hip_lib.x3_flag_ptr(slot), hip_lib.current_stream()), "gemm")
 def apply():
-    hip_lib._check(lib.gdrnpp_groupnorm_apply_nhwc(y.data_ptr(), part.data_ptr(), P, gn.weight.data_ptr(), gn.bias.data_ptr(), out.data_ptr(), n, h * w, cout,
-                                                   groups, float(gn.eps), 1, hip_lib._stream()), "apply")
+    hip_lib.check(lib.gdrnpp_groupnorm_apply_nhwc(y.data_ptr(), part.data_ptr(), P, gn.weight.data_ptr(), gn.bias.data_ptr(), out.data_ptr(), n, h * w, cout,
+                                                   groups, float(gn.eps), 1, hip_lib.current_stream()), "apply")
 gemm(); apply(); torch.cuda.synchronize()
 streams = [torch.cuda.Stream(), torch.cuda.Stream()]
 for s in streams: s.wait_stream(torch.cuda.current_stream())

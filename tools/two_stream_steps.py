@@ -15,7 +15,7 @@ cfg_no, cfg_names, b_default, refine, label = B.WORKLOADS[wname]
 b = args.batch or b_default
 state = B.build_state(args, cfg_names, refine, wname, b, 0, dev, 0)
 launch = state["launch"]
-hip_lib.SPLIT2_SHARED_MIN_TILES = hip_lib.SPLIT2_MIN_TILES // 2          # the same kernels on one stream and on two
+hip_lib.dispatch.SPLIT2_SHARED_MIN_TILES = hip_lib.SPLIT2_MIN_TILES // 2          # the same kernels on one stream and on two
 
 
 def run(n, depth):

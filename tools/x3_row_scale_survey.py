@@ -82,7 +82,9 @@ def main():
             stats(f"conv3x3+gn {tuple(x_cl.shape)}", conv_rows_ms(x_cl, 3, 3, 1, 1), k.get("x3_slot", 0))
         return cgn(x_cl, wp, *a, **k)
 
-    hip_lib.linear_f32_split, hip_lib.conv2d_f32_split, hip_lib.conv3x3_groupnorm_act = lin_w, conv_w, cgn_w
+    for name, wrapped in (("linear_f32_split", lin_w), ("conv2d_f32_split", conv_w), ("conv3x3_groupnorm_act", cgn_w)):
+        setattr(hip_lib.gemm, name, wrapped)      # calls inside the family: conv3x3 -> conv2d, transposed conv -> linear
+        setattr(hip_lib, name, wrapped)           # everybody else resolves the namespace at call time
     with torch.no_grad():
         model(img, roi_classes=T(det["roi_cls"]), roi_cams=T(det["roi_cam"]), roi_whs=T(det["roi_wh"]), roi_centers=T(det["roi_center"]),
               resize_ratios=T(det["resize_ratio"]), roi_coord_2d=T(S.coord2d_roi(det["roi_center"], det["scale"])),
