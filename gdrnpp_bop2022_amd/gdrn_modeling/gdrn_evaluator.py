@@ -112,19 +112,25 @@ class GDRN_Evaluator:
                 b[key] = _cat(inputs, key, device, torch.float32)
         return b
 
+    def _pose_records(self, inputs, out_dict):
+        """The batched post-processing of every ROI of ``inputs`` (``cfg.TEST`` selects direct / PnP / refine) -> host f32[n,16]
+        pose records in running ROI order, or None when the images hold no ROI."""
+        n = sum(len(d["roi_cls"]) for d in inputs)
+        if n == 0:
+            return None
+        dev = out_dict["trans"].device
+        batch = self._roi_batch(inputs, dev)
+        rec = self.post.process(batch, out_dict, torch.arange(n, device=dev, dtype=torch.int32))
+        return rec.to(self._cpu_device).numpy()           # the one synchronising copy: 64 B per ROI
+
     def process(self, inputs, outputs, out_dict):
         """inputs: list of per-image dicts; outputs: list of ``{"time": forward time}``; out_dict: ``GDRN_Net.forward``'s.
         Appends one BOP record per ROI to ``self._predictions`` (gdrn_evaluator.py:155-239 direct, :241-459 PnP variants,
         :461-573 depth refinement — selected by the same ``cfg.TEST`` switches)."""
         start = time.perf_counter()
-        n_per_image = [len(d["roi_cls"]) for d in inputs]
-        n = sum(n_per_image)
-        if n == 0:
+        rec = self._pose_records(inputs, out_dict)
+        if rec is None:
             return
-        dev = out_dict["trans"].device
-        batch = self._roi_batch(inputs, dev)
-        rec = self.post.process(batch, out_dict, torch.arange(n, device=dev, dtype=torch.int32))
-        rec = rec.to(self._cpu_device).numpy()           # the one synchronising copy: 64 B per ROI
         spent = time.perf_counter() - start
         out_i = -1
         for _input, output in zip(inputs, outputs):
@@ -149,14 +155,19 @@ class GDRN_Evaluator:
         """gdrn_evaluator.py:575-585: gather every rank's records (the reference pickles its dict lists through
         ``comm.all_gather``, my_comm.py:70-171 — a one-off at the end of the dataset, kept as an object gather), then the
         main process writes the BOP csv.  The per-step device-side pose gather of the hot path is ``engine.gather_records``."""
+        if not self._gather_predictions():
+            return
+        return self._eval_predictions()
+
+    def _gather_predictions(self) -> bool:
+        """Every rank's records onto every rank; True on the main process (the one that evaluates)."""
         if self._distributed and dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
             dist.barrier()
             parts = [None] * dist.get_world_size()
             dist.all_gather_object(parts, self._predictions)
             self._predictions = list(itertools.chain(*parts))
-            if dist.get_rank() != 0:
-                return
-        return self._eval_predictions()
+            return dist.get_rank() == 0
+        return True
 
     def _process_time_of_preds(self, results):
         """gdrn_evaluator.py:598-610: every record of an image carries the largest time recorded for that image."""

@@ -212,6 +212,43 @@ def pack_pose_records(R, t_refined, t_net, score, obj_id, roi_id):
     return rec
 
 
+def pose_errors(meshes: MeshSet, obj, R_est, t_est, R_gt, t_gt, K, sym_rots=None, sym_off=None, symmetric=None) -> torch.Tensor:
+    """``gdrnpp_pose_errors``: the custom evaluator's errors of b (estimate, ground truth) pairs -> f64[b,4] = ad (ADD, or ADI for
+    a class flagged in ``symmetric``), re (degrees, against the closest symmetric ground-truth rotation), te, proj (pixels).
+    obj i32[b]; R_est, R_gt, K f64[b,3,3|9]; t_est, t_gt f64[b,3] (metres); sym_rots f64[n_sym_total,3,3|9] with sym_off
+    i32[n_obj+1]; symmetric u8[n_obj].  All device tensors; ``obj`` is checked against the mesh set here (one read-back of two
+    integers), so that a class index without a model is an error and not a NaN row."""
+    dev = meshes.verts.device
+    b = int(obj.shape[0])
+    out = torch.empty((b, 4), dtype=torch.float64, device=dev)
+    if b == 0:
+        return out
+    op = dev_ptr(obj, torch.int32, "obj")
+    lo, hi = torch.aminmax(obj)
+    if int(lo) < 0 or int(hi) >= meshes.n_obj:
+        raise RuntimeError(f"pose_errors: obj must lie in [0, {meshes.n_obj}), got [{int(lo)}, {int(hi)}]")
+    ptrs = []
+    for t, name, cols in ((R_est, "R_est", 9), (t_est, "t_est", 3), (R_gt, "R_gt", 9), (t_gt, "t_gt", 3), (K, "K", 9)):
+        ptrs.append(dev_ptr(t, torch.float64, name))
+        if t.numel() != b * cols:
+            raise RuntimeError(f"pose_errors: {name} must hold {b} x {cols} values, got {tuple(t.shape)}")
+    if (sym_rots is None) != (sym_off is None):
+        raise RuntimeError("pose_errors: sym_rots and sym_off come together")
+    sp = so = fp = None
+    if sym_rots is not None:
+        sp, so = dev_ptr(sym_rots, torch.float64, "sym_rots"), dev_ptr(sym_off, torch.int32, "sym_off")
+        if sym_off.numel() != meshes.n_obj + 1:
+            raise RuntimeError(f"pose_errors: sym_off must hold n_obj + 1 = {meshes.n_obj + 1} offsets")
+    if symmetric is not None:
+        fp = dev_ptr(symmetric, torch.uint8, "symmetric")
+        if symmetric.numel() != meshes.n_obj:
+            raise RuntimeError(f"pose_errors: symmetric must hold n_obj = {meshes.n_obj} flags")
+    nbytes = load().gdrnpp_pose_errors_workspace_bytes(meshes.c, b)
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    launch("gdrnpp_pose_errors", meshes.c, op, *ptrs, sp, so, fp, out.data_ptr(), b, ws.data_ptr(), nbytes)
+    return out
+
+
 def pnp_iter_from_correspondences(img_pts, mdl_pts, count, K, R_net, t_net, return_info: bool = False):
     """Net-initialised iterative PnP (gdrn_evaluator.py:241-371, pnp_type="iter") for all ROIs at once."""
     b, stride, _ = img_pts.shape

@@ -323,6 +323,23 @@ int gdrnpp_refine_to_records(const gdrnpp_meshes* meshes, const int* obj, const 
                              float threshold, int mask_type, int use_coor_z, float z_near, float z_far, void* workspace,
                              size_t workspace_bytes, void* stream);
 
+/* ---- pose errors of the custom evaluator — gdrn_custom_evaluator.py:672-730 with lib/pysixd/pose_error.py:256-296 (add,
+ * adi), :359-374 (re), :406-417 (te), :440-445 (arp_2d) and pose_utils.py:472-496 (get_closest_rot) ----------------------
+ * All b (estimate, ground truth) pairs of a dataset in one call, pairs of different classes mixed.  Device pointers:
+ * obj i32[b] class index into `models` (whose verts are the model points; the float64 values of those float32 numbers);
+ * R_est, R_gt, K f64[b,9]; t_est, t_gt f64[b,3] in metres; sym_rots f64[n_sym_total,9] with sym_off i32[n_obj+1] (both NULL:
+ * no class has a symmetry list); symmetric u8[n_obj] (NULL: none), 1 = the class takes adi and the closest symmetric
+ * ground-truth rotation (symmetries visited in order, replaced on a strictly smaller re) for re and proj, while adi itself
+ * keeps the unmodified R_gt.  out f64[b,4] = ad, re (degrees), te, proj (pixels).  An obj outside [0, n_obj), an empty model
+ * or one with more vertices than models->max_verts gives NaN for ad and proj.  models->max_verts must be set (> 0).
+ * Sums have a fixed order: two calls give bit-equal output.  workspace: gdrnpp_pose_errors_workspace_bytes(models, b) =
+ * 8 * b * (24 + 2 * ceil(max_verts / 256)) bytes.  Argument errors return GDRNPP_EINVAL / GDRNPP_ELIMIT and launch nothing. */
+size_t gdrnpp_pose_errors_workspace_bytes(const gdrnpp_meshes* models, int b);
+int gdrnpp_pose_errors(const gdrnpp_meshes* models, const int* obj, const double* R_est, const double* t_est,
+                       const double* R_gt, const double* t_gt, const double* K, const double* sym_rots,
+                       const int* sym_off, const unsigned char* symmetric, double* out, int b, void* workspace,
+                       size_t workspace_bytes, void* stream);
+
 /* device-to-device copy into a raw device pointer on `stream` — the transfer CppEGLRenderer::map_tensor performs with
  * cudaMemcpy2DFromArray in the reference (lib/egl_renderer/cpp/egl_renderer.cpp:262-298): attachment -> caller's tensor */
 int gdrnpp_copy_d2d(void* dst, const void* src, size_t bytes, void* stream);
