@@ -1,0 +1,305 @@
+"""BOP19 scoring of a results file: what the reference does offline with its BOP-toolkit fork after ``GDRN_Evaluator`` wrote the csv
+(core/gdrn_modeling/engine/test_utils.py:33-80 -> lib/pysixd/scripts/eval_pose_results_more.py:39-156, 354-381 -> eval_calc_errors.py:254-612
+and eval_calc_scores.py:180-276), with the per-pair NumPy arithmetic replaced by a handful of kernel calls for the whole dataset:
+
+    reference, per error type:   a process per type, per (estimate, ground truth) pair a NumPy pass over the model per symmetry
+    here:                        pair every estimate with the ground truths of its object in its image once, then ONE
+                                 ``hip_lib.bop_errors`` call (mssd, mspd) and ONE ``hip_lib.pose_errors`` call per ADD / ADI flavour
+                                 (ad, add, adi, re, te, rete, proj) for all pairs; matching and recall stay host code
+
+VSD is not computed (it needs the datasets' depth images and a renderer): ``vsd``, ``cus``, the ``*S``, ``ABS*`` and ``AUC*`` types raise
+NotImplementedError.  Units are those of a BOP results file: translations and model vertices in millimetres."""
+from __future__ import annotations
+
+import json
+import logging
+import os
+
+import numpy as np
+import torch
+
+from .. import hip_lib
+from ..lib.pysixd import inout, misc, pose_matching, score
+
+logger = logging.getLogger(__name__)
+
+MAX_SYM_DISC_STEP = 0.01            # eval_pose_results_more.py:162
+# eval_pose_results_more.py:39-156, the same expressions so that the floats are the same
+CORRECT_THS = {
+    "mssd": [[th] for th in np.arange(0.05, 0.51, 0.05)],
+    "mspd": [[th] for th in np.arange(5, 51, 5)],
+    "ad": [[th] for th in [0.02, 0.05, 0.1]],
+    "add": [[th] for th in [0.02, 0.05, 0.1]],
+    "adi": [[th] for th in [0.02, 0.05, 0.1]],
+    "re": [[th] for th in [2, 5, 10]],
+    "te": [[th] for th in [2, 5, 10]],
+    "rete": [[2, 2], [5, 5], [10, 10]],
+    "proj": [[th] for th in [2, 5, 10]],
+}
+KNOWN_NOT_IMPLEMENTED = ("vsd", "cus", "reS", "teS", "reteS", "projS", "ABSad", "ABSadd", "ABSadi", "AUCad", "AUCadd", "AUCadi")
+NORMALIZED_BY_DIAMETER = ("ad", "add", "adi", "mssd")      # eval_calc_scores.py:70-72
+NORMALIZED_BY_IM_WIDTH = ("mspd",)
+
+
+class BopGT:
+    """What scoring needs of a BOP dataset split, loaded once:
+
+    scene_gt {scene_id: {im_id: [{"obj_id", "cam_R_m2c" f64[3,3], "cam_t_m2c" f64[3] (mm)}, ...]}}, scene_gt_info {scene_id: {im_id:
+    [{"visib_fract"}, ...]}}, scene_camera {scene_id: {im_id: {"cam_K" f64[3,3]}}}, targets [{"scene_id", "im_id", "obj_id",
+    "inst_count"}, ...], models_info {obj_id: {"diameter", "symmetries_discrete", "symmetries_continuous"}}, symmetric_obj_ids (the
+    objects that ``ad`` scores with ADI), vertices {obj_id: f32[n,3] eval-model points in mm}, im_width, and the id lists the recall
+    averages run over: obj_ids (default: the models), scene_ids (default: the scenes of the targets)."""
+
+    def __init__(self, scene_gt, scene_gt_info, scene_camera, targets, models_info, symmetric_obj_ids, vertices, im_width,
+                 obj_ids=None, scene_ids=None):
+        self.scene_gt = {int(s): {int(i): [dict(obj_id=int(g["obj_id"]), cam_R_m2c=np.asarray(g["cam_R_m2c"], np.float64).reshape(3, 3),
+                                                cam_t_m2c=np.asarray(g["cam_t_m2c"], np.float64).reshape(3)) for g in gts]
+                                  for i, gts in per_im.items()} for s, per_im in scene_gt.items()}
+        self.scene_gt_info = {int(s): {int(i): [dict(visib_fract=g["visib_fract"]) for g in infos] for i, infos in per_im.items()}
+                              for s, per_im in scene_gt_info.items()}
+        self.scene_camera = {int(s): {int(i): dict(cam_K=np.asarray(c["cam_K"], np.float64).reshape(3, 3)) for i, c in per_im.items()}
+                             for s, per_im in scene_camera.items()}
+        self.targets = [dict(scene_id=int(t["scene_id"]), im_id=int(t["im_id"]), obj_id=int(t["obj_id"]),
+                             inst_count=int(t["inst_count"])) for t in targets]
+        self.models_info = {int(k): v for k, v in models_info.items()}
+        self.symmetric_obj_ids = [int(o) for o in symmetric_obj_ids]
+        self.vertices = {int(k): np.ascontiguousarray(v, np.float32).reshape(-1, 3) for k, v in vertices.items()}
+        self.im_width = im_width
+        self.obj_ids = [int(o) for o in obj_ids] if obj_ids is not None else sorted(self.models_info)
+        self.scene_ids = [int(s) for s in scene_ids] if scene_ids is not None else sorted({t["scene_id"] for t in self.targets})
+
+    @classmethod
+    def from_bop_dir(cls, dataset_dir, split="test", targets_filename="test_targets_bop19.json", models_dir="models_eval",
+                     symmetric_obj_ids=(), im_width=640, obj_ids=None, scene_ids=None):
+        """The standard BOP layout: ``<dataset_dir>/<models_dir>/models_info.json`` + ``obj_{id:06d}.ply``,
+        ``<dataset_dir>/<targets_filename>`` and ``<dataset_dir>/<split>/{scene_id:06d}/scene_gt.json | scene_gt_info.json |
+        scene_camera.json`` for the scenes the targets name."""
+        def load(*parts):
+            with open(os.path.join(dataset_dir, *parts)) as f:
+                return json.load(f)
+
+        targets = load(targets_filename)
+        models_info = {int(k): v for k, v in load(models_dir, "models_info.json").items()}
+        vertices = {o: inout.load_ply(os.path.join(dataset_dir, models_dir, f"obj_{o:06d}.ply"))["pts"] for o in models_info}
+        per_scene = {name: {} for name in ("scene_gt", "scene_gt_info", "scene_camera")}
+        for s in sorted({int(t["scene_id"]) for t in targets}):
+            for name in per_scene:
+                per_scene[name][s] = load(split, f"{s:06d}", name + ".json")
+        return cls(per_scene["scene_gt"], per_scene["scene_gt_info"], per_scene["scene_camera"], targets, models_info, symmetric_obj_ids,
+                   vertices, im_width, obj_ids, scene_ids)
+
+    def meshes(self, device="cuda"):
+        """The eval models as a ``hip_lib.MeshSet`` in ``sorted(models_info)`` order (points only)."""
+        no_face = np.zeros((1, 3), np.int32)
+        ids = sorted(self.models_info)
+        return hip_lib.MeshSet([self.vertices[o] for o in ids], [no_face] * len(ids), device=device)
+
+
+def average_time_per_image(records) -> float:
+    """eval_pose_results_more.py:243-265: the mean of the per-image times; -1 once an estimate has none (< 0); the estimates of an
+    image must agree within 1e-3."""
+    times = {}
+    for r in records:
+        key = (int(r["scene_id"]), int(r["im_id"]))
+        if r["time"] < 0:
+            return -1.0
+        if key in times:
+            if abs(times[key] - r["time"]) > 0.001:
+                raise ValueError("The running time for scene {} and image {} is not the same for all estimates.".format(*key))
+        else:
+            times[key] = r["time"]
+    return float(np.mean(list(times.values())))
+
+
+def _check_types(error_types):
+    for t in error_types:
+        if t not in CORRECT_THS:
+            raise NotImplementedError(f"bop19_scores: error type {t!r} is not computed here"
+                                      + ("" if t in KNOWN_NOT_IMPLEMENTED else " (and unknown to the BOP toolkit)"))
+
+
+def _organize_targets(targets):
+    org = {}
+    for t in targets:
+        org.setdefault(t["scene_id"], {}).setdefault(t["im_id"], {})[t["obj_id"]] = t
+    return org
+
+
+def pair_estimates(records, gt: BopGT, targets, n_top: int):
+    """eval_calc_errors.py:254-358.  -> (ests, pairs): ``ests`` one entry per evaluated estimate, in the script's order (targets by
+    scene, image, object; estimates by falling score, stable) ``{"scene_id", "im_id", "obj_id", "est_id", "score", "gt_ids", "pairs"}``
+    with ``est_id`` the estimate's position among its object's estimates of the image before the sort; ``pairs`` a list of
+    (R_e f64[9], t_e f64[3], obj_id, scene_id, im_id, gt_id), one per (estimate, ground truth of the same object in the image)."""
+    ests_org = {}
+    for r in records:
+        ests_org.setdefault(int(r["scene_id"]), {}).setdefault(int(r["im_id"]), {}).setdefault(int(r["obj_id"]), []).append(r)
+    ests, pairs = [], []
+    for scene_id, scene_targets in _organize_targets(targets).items():
+        for im_id, im_targets in scene_targets.items():
+            for obj_id, target in im_targets.items():
+                n_top_curr = None if n_top == 0 else (target["inst_count"] if n_top == -1 else n_top)
+                obj_ests = ests_org.get(scene_id, {}).get(im_id, {}).get(obj_id, [])
+                ranked = sorted(enumerate(obj_ests), key=lambda x: x[1]["score"], reverse=True)[slice(0, n_top_curr)]
+                for est_id, est in ranked:
+                    entry = dict(scene_id=scene_id, im_id=im_id, obj_id=obj_id, est_id=est_id, score=est["score"], gt_ids=[], pairs=[])
+                    R_e, t_e = np.asarray(est["R"], np.float64).reshape(9), np.asarray(est["t"], np.float64).reshape(3)
+                    for gt_id, g in enumerate(gt.scene_gt[scene_id][im_id]):
+                        if g["obj_id"] != obj_id:
+                            continue
+                        entry["gt_ids"].append(gt_id)
+                        entry["pairs"].append(len(pairs))
+                        pairs.append((R_e, t_e, obj_id, scene_id, im_id, gt_id))
+                    ests.append(entry)
+    return ests, pairs
+
+
+def calc_errors(records, gt: BopGT, targets, models_info, meshes, error_types, n_top: int):
+    """-> {error_type: {scene_id: [{"im_id", "obj_id", "est_id", "score", "errors": {gt_id: [elements]}}, ...]}}: the content of the
+    script's ``errors_{scene_id:06d}.json`` files (eval_calc_errors.py:343-612), un-normalised."""
+    _check_types(error_types)
+    ests, pairs = pair_estimates(records, gt, targets, n_top)
+    ids = sorted(models_info)
+    index = {o: k for k, o in enumerate(ids)}
+    P = len(pairs)
+    values = {}
+    if P:
+        dev = meshes.verts.device
+        R_e = np.stack([p[0] for p in pairs])
+        t_e = np.stack([p[1] for p in pairs])
+        obj_ids = np.array([p[2] for p in pairs])
+        g = [gt.scene_gt[p[3]][p[4]][p[5]] for p in pairs]
+        R_g = np.stack([x["cam_R_m2c"].reshape(9) for x in g])
+        t_g = np.stack([x["cam_t_m2c"] for x in g])
+        K = np.stack([gt.scene_camera[p[3]][p[4]]["cam_K"].reshape(9) for p in pairs])
+        obj = np.array([index[o] for o in obj_ids], np.int32)
+        # eval_calc_errors.py:373-374, per pair as the script does it
+        overlap = np.array([np.linalg.norm(t_e[i].reshape(3, 1) - t_g[i].reshape(3, 1)) < models_info[obj_ids[i]]["diameter"]
+                            for i in range(P)], bool)
+
+        def dev_args(sel):
+            return [torch.from_numpy(np.ascontiguousarray(a[sel])).to(dev) for a in (obj, R_e, t_e, R_g, t_g, K)]
+
+        def scatter(sel, out, cols):
+            full = np.full((P, cols), np.inf)
+            full[sel] = out.cpu().numpy()
+            return full
+
+        everything, near = np.arange(P), np.nonzero(overlap)[0]
+        if "mssd" in error_types or "mspd" in error_types:
+            sel = everything if "mspd" in error_types else near
+            if len(sel):
+                syms = [misc.get_symmetry_transformations(models_info[o], MAX_SYM_DISC_STEP) for o in ids]
+                sym_R, sym_t, sym_off = misc.flatten_symmetry_transformations(syms)
+                out = hip_lib.bop_errors(meshes, *dev_args(sel), torch.from_numpy(sym_R).to(dev), torch.from_numpy(sym_t).to(dev), sym_off)
+                full = scatter(sel, out, 2)
+                values["mssd"], values["mspd"] = np.where(overlap, full[:, 0], np.inf), full[:, 1]
+        plain = [t for t in error_types if t in ("add", "re", "te", "rete", "proj")]
+        flavours = []                                          # (the types served, pairs, ADI flags)
+        if plain:
+            flavours.append((plain, near if plain == ["add"] else everything, None))
+        if "adi" in error_types:
+            flavours.append((["adi"], near, np.ones(len(ids), np.uint8)))
+        if "ad" in error_types:
+            flavours.append((["ad"], near, np.array([o in gt.symmetric_obj_ids for o in ids], np.uint8)))
+        for served, sel, flags in flavours:
+            if not len(sel):
+                continue
+            symmetric = torch.from_numpy(flags).to(dev) if flags is not None else None
+            full = scatter(sel, hip_lib.pose_errors(meshes, *dev_args(sel), symmetric=symmetric), 4)
+            for t in served:
+                if t in ("ad", "add", "adi"):
+                    values[t] = np.where(overlap, full[:, 0], np.inf)
+                else:
+                    values["re"], values["te"], values["proj"] = full[:, 1], full[:, 2] / 10, full[:, 3]     # te: mm -> cm
+    inf = np.full((P,), np.inf)
+
+    def elements(t, k):
+        if t == "rete":
+            return [float(values["re"][k]), float(values["te"][k])]
+        return [float(values.get(t, inf)[k])]
+
+    out = {}
+    for t in error_types:
+        per_scene = {s: [] for s in _organize_targets(targets)}
+        for e in ests:
+            per_scene[e["scene_id"]].append(dict(im_id=e["im_id"], obj_id=e["obj_id"], est_id=e["est_id"], score=e["score"],
+                                                 errors={g_id: elements(t, k) for g_id, k in zip(e["gt_ids"], e["pairs"])}))
+        out[t] = per_scene
+    return out
+
+
+def valid_gts(gt: BopGT, scene_id, scene_targets):
+    """eval_calc_scores.py:205-238 with ``visib_gt_min = -1``: per target image, the ``inst_count`` most visible ground truths of every
+    target object are valid (a stable sort by falling ``visib_fract``), all others are not."""
+    valid = {}
+    for im_id, im_targets in scene_targets.items():
+        im_gt, info = gt.scene_gt[scene_id][im_id], gt.scene_gt_info[scene_id][im_id]
+        left = {obj_id: t["inst_count"] for obj_id, t in im_targets.items()}
+        valid[im_id] = [False] * len(im_gt)
+        for gt_id in sorted(range(len(im_gt)), key=lambda k: info[k]["visib_fract"], reverse=True):
+            obj_id = im_gt[gt_id]["obj_id"]
+            if left.get(obj_id, 0) > 0:
+                valid[im_id][gt_id] = True
+                left[obj_id] -= 1
+    return valid
+
+
+def score_errors(errors_by_scene, gt: BopGT, targets, models_info, error_type, correct_th, n_top, im_width, do_print=False):
+    """eval_calc_scores.py:180-276 for one threshold: normalise (by the object's diameter, or by 640 / image width), match per scene,
+    count.  -> (matches, scores)."""
+    matches = []
+    for scene_id, scene_targets in _organize_targets(targets).items():
+        scene_gt_curr = {im_id: gt.scene_gt[scene_id][im_id] for im_id in scene_targets}
+        errs = []
+        for e in errors_by_scene.get(scene_id, []):
+            if error_type in NORMALIZED_BY_DIAMETER:
+                diameter = float(models_info[e["obj_id"]]["diameter"])
+                e = dict(e, errors={k: [x / diameter for x in v] for k, v in e["errors"].items()})
+            elif error_type in NORMALIZED_BY_IM_WIDTH:
+                factor = 640.0 / float(im_width)
+                e = dict(e, errors={k: [factor * x for x in v] for k, v in e["errors"].items()})
+            errs.append(e)
+        matches += pose_matching.match_poses_scene(scene_id, scene_gt_curr, valid_gts(gt, scene_id, scene_targets), errs,
+                                                   [float(th) for th in correct_th], n_top)
+    return matches, score.calc_localization_scores(gt.scene_ids, gt.obj_ids, matches, n_top, do_print=do_print)
+
+
+def scores_from_errors(errors, records, gt: BopGT, targets, models_info, error_types, n_top, im_width) -> dict:
+    """eval_pose_results_more.py:268-381 from computed errors: per type the recall at every threshold and their mean."""
+    final, recalls_of, obj_recalls_of = {}, {}, {}
+    for t in error_types:
+        recalls, obj_recalls = [], []
+        for th in CORRECT_THS[t]:
+            _, s = score_errors(errors[t], gt, targets, models_info, t, th, n_top, im_width)
+            recalls.append(s["recall"])
+            obj_recalls.append(s["obj_recalls"])
+        recalls_of[t], obj_recalls_of[t] = recalls, obj_recalls
+        final[f"bop19_average_recall_{t}"] = float(np.mean(recalls))
+    if all(t in error_types for t in ("mspd", "mssd", "vsd")):          # never here: vsd is not computed; no two-metric average
+        final["bop19_average_recall"] = float(np.mean([final[f"bop19_average_recall_{t}"] for t in ("mspd", "mssd", "vsd")]))
+    final["bop19_average_time_per_image"] = average_time_per_image(records)
+    final["recalls"] = recalls_of                     # per type: the recall at each threshold of CORRECT_THS
+    final["obj_recalls"] = obj_recalls_of             # per type: {obj_id: recall} at each threshold
+    return final
+
+
+def bop19_scores(records, gt: BopGT, targets=None, models_info=None, meshes=None, error_types=("mssd", "mspd"), n_top=-1,
+                 im_width=None) -> dict:
+    """records: BOP estimates ``{"scene_id", "im_id", "obj_id", "score", "R" (9 values), "t" (3, mm), "time"}`` (what ``GDRN_Evaluator``
+    writes to the csv).  targets / models_info / im_width default to ``gt``'s; meshes: the eval models as a ``hip_lib.MeshSet`` in
+    ``sorted(models_info)`` order (default: built from ``gt.vertices``).  error_types: a sequence, or the comma-separated string of
+    ``VAL.ERROR_TYPES``.  n_top: estimates per target, -1 = the target's ``inst_count``, 0 = all.
+
+    -> ``bop19_average_recall_<type>`` per type (the mean recall over the type's thresholds), ``bop19_average_time_per_image``,
+    ``recalls`` and ``obj_recalls`` (per type, per threshold); ``bop19_average_recall`` only if mspd, mssd and vsd were all computed."""
+    if isinstance(error_types, str):
+        error_types = [t for t in error_types.split(",") if t]
+    error_types = list(error_types)
+    targets = gt.targets if targets is None else targets
+    models_info = gt.models_info if models_info is None else {int(k): v for k, v in models_info.items()}
+    im_width = gt.im_width if im_width is None else im_width
+    _check_types(error_types)                                            # before anything is launched
+    if meshes is None:
+        meshes = gt.meshes()
+    errors = calc_errors(records, gt, targets, models_info, meshes, error_types, int(n_top))
+    return scores_from_errors(errors, records, gt, targets, models_info, error_types, int(n_top), im_width)

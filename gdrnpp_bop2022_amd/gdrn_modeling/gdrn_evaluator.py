@@ -17,6 +17,7 @@ each image its own share of the Python loop; (3) ``score`` is stored as a float 
 from __future__ import annotations
 
 import itertools
+import json
 import logging
 import os
 import time
@@ -68,10 +69,11 @@ class GDRN_Evaluator:
     """Drop-in for the reference class of the same name.  The dataset registry (``MetadataCatalog`` / ``ref.<dataset>``)
     is not rebuilt: the two facts the hot path needs from it are passed in — ``obj_names`` (class order of the dataset,
     ``self._metadata.objs``) and ``obj2id`` (``data_ref.obj2id``) — plus the object meshes for the depth refinement
-    (``hip_lib.MeshSet`` in class order, replacing ``lib.render_vispy.model3d.load_models``)."""
+    (``hip_lib.MeshSet`` in class order, replacing ``lib.render_vispy.model3d.load_models``).  ``bop_gt`` (a ``bop_eval.BopGT``:
+    the split's ground truth, targets and eval models) lets ``evaluate()`` score the results it wrote, see ``_eval_predictions``."""
 
     def __init__(self, cfg, dataset_name=None, distributed=False, output_dir=None, train_objs=None, *, obj_names, obj2id,
-                 meshes: "hip_lib.MeshSet | None" = None):
+                 meshes: "hip_lib.MeshSet | None" = None, bop_gt=None):
         self.cfg = cfg
         self.dataset_name = dataset_name
         self._distributed = distributed
@@ -83,6 +85,7 @@ class GDRN_Evaluator:
         self.obj_ids = [self.obj2id[n] for n in self.obj_names]
         self.depth_refine_threshold = cfg.TEST.DEPTH_REFINE_THRESHOLD
         self.post = GdrnHipPost(cfg, meshes)
+        self.bop_gt = bop_gt
         self._predictions = []
 
     # ---- protocol ------------------------------------------------------------------------------------------------
@@ -178,15 +181,34 @@ class GDRN_Evaluator:
             item["time"] = float(np.max(times["{}/{}".format(item["scene_id"], item["im_id"])]))
 
     def _eval_predictions(self):
-        """gdrn_evaluator.py:587-596 up to the BOP results file (test_utils.py:33-52); running the BOP toolkit on it is
-        the reference's offline tooling and stays there."""
+        """gdrn_evaluator.py:587-596: the BOP results file (test_utils.py:33-52) and, with a ``bop_gt``, ``VAL.USE_BOP`` set and
+        ``VAL.SAVE_BOP_CSV_ONLY`` not set, its BOP19 scores (test_utils.py:53-80: ``VAL.ERROR_TYPES`` and ``VAL.N_TOP`` handed to
+        eval_pose_results_more.py; here ``bop_eval.bop19_scores`` on the records just written, errors always computed as with
+        ``VAL.SCORE_ONLY=False``) in ``<output_dir>/<results file name without .csv>/scores_bop19.json``.  Without a ``bop_gt`` the csv is
+        all there is and {} is returned."""
         self._process_time_of_preds(self._predictions)
+        csv_name = bop_csv_name(self.cfg)
         if self._output_dir:
             os.makedirs(self._output_dir, exist_ok=True)
-            path = os.path.join(self._output_dir, bop_csv_name(self.cfg))
+            path = os.path.join(self._output_dir, csv_name)
             save_bop_csv(self._predictions, path)
             logger.info("wrote %d BOP records (%s) to %s", len(self._predictions), BOP_CSV_HEADER, path)
-        return {}
+        val = self.cfg.get("VAL", {})
+        if self.bop_gt is None or not val.get("USE_BOP", False) or val.get("SAVE_BOP_CSV_ONLY", False):
+            return {}
+        from .bop_eval import bop19_scores
+
+        scores = bop19_scores(self._predictions, self.bop_gt, error_types=val.get("ERROR_TYPES", "ad,rete,re,te,proj"),
+                              n_top=val.get("N_TOP", 1))
+        final = {k: v for k, v in scores.items() if k.startswith("bop19_")}
+        if self._output_dir:
+            result_dir = os.path.join(self._output_dir, os.path.splitext(csv_name)[0])
+            os.makedirs(result_dir, exist_ok=True)
+            with open(os.path.join(result_dir, "scores_bop19.json"), "w") as f:
+                json.dump(final, f, sort_keys=True, indent=2)
+        for name, value in sorted(final.items()):
+            logger.info("- %s: %s", name, value)
+        return scores
 
 
 def packed_loader(data_loader, pack_rois: int):

@@ -249,6 +249,47 @@ def pose_errors(meshes: MeshSet, obj, R_est, t_est, R_gt, t_gt, K, sym_rots=None
     return out
 
 
+def bop_errors(meshes: MeshSet, obj, R_est, t_est, R_gt, t_gt, K, sym_R, sym_t, sym_off) -> torch.Tensor:
+    """``gdrnpp_bop_errors``: BOP19 MSSD and MSPD of b (estimate, ground truth) pairs -> f64[b,2] = mssd, mspd (pixels).
+    obj i32[b]; R_est, R_gt, K f64[b,3,3|9]; t_est, t_gt f64[b,3], in the unit of the meshes' vertices (millimetres for a BOP results
+    file); sym_R f64[n_sym_total,3,3|9] and sym_t f64[n_sym_total,3|3,1]: every object's symmetry transformations
+    (``lib.pysixd.misc.get_symmetry_transformations``), object after object; sym_off: n_obj + 1 offsets into them (a sequence, an
+    array or a tensor; it is read on the host, where it sizes the launch).  The other arguments are device tensors; ``obj`` is
+    checked against the mesh set here (one read-back of two integers)."""
+    import numpy as np
+
+    dev = meshes.verts.device
+    b = int(obj.shape[0])
+    out = torch.empty((b, 2), dtype=torch.float64, device=dev)
+    if b == 0:
+        return out
+    op = dev_ptr(obj, torch.int32, "obj")
+    lo, hi = torch.aminmax(obj)
+    if int(lo) < 0 or int(hi) >= meshes.n_obj:
+        raise RuntimeError(f"bop_errors: obj must lie in [0, {meshes.n_obj}), got [{int(lo)}, {int(hi)}]")
+    ptrs = []
+    for t, name, cols in ((R_est, "R_est", 9), (t_est, "t_est", 3), (R_gt, "R_gt", 9), (t_gt, "t_gt", 3), (K, "K", 9)):
+        ptrs.append(dev_ptr(t, torch.float64, name))
+        if t.numel() != b * cols:
+            raise RuntimeError(f"bop_errors: {name} must hold {b} x {cols} values, got {tuple(t.shape)}")
+    off = np.ascontiguousarray(sym_off.cpu().numpy() if isinstance(sym_off, torch.Tensor) else sym_off).reshape(-1)
+    if off.dtype.kind not in "iu" or off.size != meshes.n_obj + 1:
+        raise RuntimeError(f"bop_errors: sym_off must hold n_obj + 1 = {meshes.n_obj + 1} integer offsets")
+    off = off.astype(np.int32)
+    n_sym = int(off[-1])
+    if off[0] != 0 or (np.diff(off) <= 0).any():
+        raise RuntimeError("bop_errors: sym_off must start at 0 and give every object at least one transformation (the identity)")
+    for t, name, cols in ((sym_R, "sym_R", 9), (sym_t, "sym_t", 3)):
+        ptrs.append(dev_ptr(t, torch.float64, name))
+        if t.numel() != n_sym * cols:
+            raise RuntimeError(f"bop_errors: {name} must hold sym_off[-1] x {cols} = {n_sym} x {cols} values, got {tuple(t.shape)}")
+    offp = off.ctypes.data
+    nbytes = load().gdrnpp_bop_errors_workspace_bytes(meshes.c, offp, b)
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    launch("gdrnpp_bop_errors", meshes.c, op, *ptrs, offp, out.data_ptr(), b, ws.data_ptr(), nbytes)
+    return out
+
+
 def pnp_iter_from_correspondences(img_pts, mdl_pts, count, K, R_net, t_net, return_info: bool = False):
     """Net-initialised iterative PnP (gdrn_evaluator.py:241-371, pnp_type="iter") for all ROIs at once."""
     b, stride, _ = img_pts.shape

@@ -340,6 +340,23 @@ int gdrnpp_pose_errors(const gdrnpp_meshes* models, const int* obj, const double
                        const int* sym_off, const unsigned char* symmetric, double* out, int b, void* workspace,
                        size_t workspace_bytes, void* stream);
 
+/* ---- BOP19 MSSD / MSPD — lib/pysixd/pose_error.py:131-179 with misc.py:568-582 (project_pts), the two errors that
+ * eval_calc_errors.py:397-423 computes for every (estimate, ground truth of the same object in the same image) pair -------
+ * All b pairs of a dataset in one call, objects mixed.  Device pointers: obj i32[b] index into `models` (the eval-model
+ * vertices in the unit of the translations, millimetres for a BOP results file); R_est, R_gt, K f64[b,9]; t_est, t_gt
+ * f64[b,3]; sym_R f64[n_sym_total,9], sym_t f64[n_sym_total,3]: the symmetry transformations of every object, object after
+ * object (misc.get_symmetry_transformations).  sym_off i32[n_obj+1] is a HOST array: it sizes the grid, and the kernels read
+ * a copy placed in the workspace.  It starts at 0, and every object holds at least one transformation (the identity for an
+ * object without symmetries): an empty range is an argument error.  out f64[b,2] = mssd, mspd (pixels; z is not clamped).
+ * An obj outside [0, n_obj) or an empty model gives NaN.  fp64 throughout; maxima and minima only, so two calls give
+ * bit-equal output.  workspace: gdrnpp_bop_errors_workspace_bytes(models, sym_off, b) = round_up(4 (n_obj + 1), 16) +
+ * 16 * b * ceil(max symmetries of an object / 8) bytes (0 for arguments that gdrnpp_bop_errors refuses).  Argument errors
+ * return GDRNPP_EINVAL / GDRNPP_ELIMIT and launch nothing. */
+size_t gdrnpp_bop_errors_workspace_bytes(const gdrnpp_meshes* models, const int* sym_off, int b);
+int gdrnpp_bop_errors(const gdrnpp_meshes* models, const int* obj, const double* R_est, const double* t_est,
+                      const double* R_gt, const double* t_gt, const double* K, const double* sym_R, const double* sym_t,
+                      const int* sym_off, double* out, int b, void* workspace, size_t workspace_bytes, void* stream);
+
 /* device-to-device copy into a raw device pointer on `stream` — the transfer CppEGLRenderer::map_tensor performs with
  * cudaMemcpy2DFromArray in the reference (lib/egl_renderer/cpp/egl_renderer.cpp:262-298): attachment -> caller's tensor */
 int gdrnpp_copy_d2d(void* dst, const void* src, size_t bytes, void* stream);
