@@ -72,7 +72,6 @@ int ensure_dynamic_lds(const void* kernel, int bytes);
 int option_split_gemm_glds();   // 1: 256-row split-GEMM tiles use the LDS-DMA kernel
 int option_split_gemm_mi4();    // -1: by tile count, 0 / 1: force 128- / 256-row tiles (A/B measurements)
 int option_splitk_small_tiles();   // 1 (default): unsplit problems of gdrnpp_linear_f32_splitk pick their tile height by tile count (128 rows below 256 tiles of 256x128: 8 ROIs 4.65 -> 4.41 ms per step), 0: always 256-row tiles
-int option_split2_wide();        // 1: 256x256 block tiles of the three-product kernels when N % 256 == 0 (A/B; default off: measured slower)
 int option_mlp_fused_pipe();    // 1 (default): software-pipelined tile loop of the fused MLP; 0: plain loop (A/B)
 int option_dwconv_tile();       // -1 (default): by launch size; 0 / 1 / 2: force the 2x8 / 2x4 / 1x4 pixel tile of dwconv7x7+LN
 int option_dwconv_lds_w();      // 1 (default): [49][C] weights in LDS + persistent workgroups where they fit; 0: weights through L1 / L2, no LDS (A/B:

@@ -406,8 +406,8 @@ int launch_split_epi(const float* A, const uint4* Wp, const float* bias, const f
   // ROIs, +2.2 % at 64, +0.1 % at 32; 128: -0.5 % at 32, -0.9 % at 16); gdrnpp_set_option("split_gemm_mi4", 0/1) forces the choice.
   const int force = gdrnpp::option_split_gemm_mi4();
   const bool big = force >= 0 ? force == 1 : tiles256 >= gdrnpp::option_split_gemm_big_tiles();
-  if (big && gdrnpp::option_split_gemm_pipe() && (!CONV || gdrnpp::option_split_gemm_pipe_conv())) {   // software-pipelined LDS-DMA kernel
-    const int rc = launch_split_pipe(A, Wp, bias, gamma, resid, C, M, N, K, EPI, CONV, cg, gdrnpp::option_split_gemm_pipe(), st, what);
+  if (!CONV && big && gdrnpp::option_split_gemm_pipe()) {   // software-pipelined LDS-DMA kernel (linear form only)
+    const int rc = launch_split_pipe(A, Wp, bias, gamma, resid, C, M, N, K, EPI, cg, gdrnpp::option_split_gemm_pipe(), st, what);
     if (rc >= 0) return rc;
   }
   // the kernels' A form: linear, the 3x3 / stride 1 / pad 1 convolution, the general convolution
@@ -558,7 +558,7 @@ extern "C" int gdrnpp_linear_f32_splitk(const float* A, const void* W_packed, co
     if (rc >= 0) return rc;
   }
   if (plan.pipe && splits == 1) {   // enough tiles for the chip: one launch, fused epilogue
-    const int rc = launch_split_pipe(A, (const uint4*)W_packed, bias, gamma, resid, C, M, N, K, epilogue, false,
+    const int rc = launch_split_pipe(A, (const uint4*)W_packed, bias, gamma, resid, C, M, N, K, epilogue,
                                      ConvGeom{0, 0, 0, 0, 0, 0, 0, 0, 0}, a_stages, st, "gdrnpp_linear_f32_splitk");
     if (rc >= 0) return rc;
   }

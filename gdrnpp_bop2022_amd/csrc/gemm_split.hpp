@@ -66,11 +66,10 @@ inline int check_conv_shape(const char* what, int n_img, int H, int W, int Cin, 
   return 0;
 }
 
-// Software-pipelined LDS-DMA kernel (gemm_split_pipe.hip).  Handles the linear form and the 3x3/1/1 convolution with
-// M*K*4 (resp. the image bytes) below 4 GiB; returns -1 when the problem is outside its domain (the caller then uses the
+// Software-pipelined LDS-DMA kernel (gemm_split_pipe.hip).  Handles the linear form with M*K*4 below 4 GiB; returns -1 when the problem is outside its domain (the caller then uses the
 // kernels of gemm_split.hip), else the launch status.
 int launch_split_pipe(const float* A, const uint4* Wp, const float* bias, const float* gamma, const float* resid, float* C,
-                      int M, int N, int K, int epilogue, bool conv, ConvGeom cg, int a_stages, hipStream_t st, const char* what);
+                      int M, int N, int K, int epilogue, ConvGeom cg, int a_stages, hipStream_t st, const char* what);
 
 // The same kernel as a split-K launch (linear form): grid (256x128 tiles, K chunks of nk_split k-tiles), raw partial sums to
 // partials[chunk][M][N]; -1 outside its domain.
@@ -86,6 +85,5 @@ int launch_split_pipe128(const float* A, const uint4* Wp, const float* bias, con
 int option_split_gemm_pipe();       // 0: off, 2 / 3 (default): pipelined kernel with that many A stages for 256-row tiles (linear form)
 int option_split_gemm_panel();      // row blocks per tile panel of wide layers in the pipelined kernel (default 4; 0: row-major)
 int option_split_gemm_big_tiles();  // 256x128 tiles (pipelined / LDS-DMA kernels) from this many of them on
-int option_split_gemm_pipe_conv();  // 1: the 3x3/1/1 convolution uses it too (default 0: measured 1 % slower than the LDS-DMA kernel)
 
 }  // namespace gdrnpp

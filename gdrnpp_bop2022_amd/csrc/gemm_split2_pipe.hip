@@ -36,13 +36,15 @@
 //
 // Kernel: the software-pipelined LDS-DMA kernel of gemm_split_pipe.hip with 24 instead of 48 MFMA slots per k-tile: block tile
 // 256x128x16, 4 waves stacked along M (2 x 4 MFMA tiles each), fp32 A by LDS-DMA into three 16 KB stages private to the waves,
-// pre-packed fp16 weight tiles (8 KB: [split][k-block][128][8]) by LDS-DMA into two stages, the split of k-tile t+1 (cvt_pk,
-// v_fma_mix_f32 residual, cvt_pk: 32 VALU operations) spread over the MFMA slots of k-tile t, both weight fragment sets read
-// just in time (l behind the barrier of the previous k-tile, h in slots 1 and 3), one barrier per k-tile behind slot 19.
-// 80 KB of dynamic LDS (three A stages, four weight slots: one barrier per two k-tiles), two workgroups per CU.  Linear form, the 3x3 / stride 1 / pad 1 convolution and the general K x K /
-// stride / pad convolution (implicit im2col, k-tile order of gemm_split.hpp), optional GroupNorm statistics in the epilogue (GnStats,
-// split_gemm_device.hpp).  -DGDRNPP2_TIMING_NO_{BREAD,SPLIT,SYNC,DMA}: timing-only builds (results invalid) behind
-// profiles/r03y_split2_kloop_dissection.txt.
+// pre-packed fp16 weight tiles (8 KB: [split][k-block][128][8]) by LDS-DMA into four slots (k-tile kt in slot kt & 3, the DMA two
+// k-tiles ahead), the split of k-tile t+1 (cvt_pk, v_fma_mix_f32 residual, cvt_pk: 32 VALU operations) spread over the MFMA
+// slots of k-tile t, both weight fragment sets read just in time (l behind slot 19 of the previous k-tile, h in slots 1 and 3),
+// one barrier per two k-tiles behind slot 19 of the odd one.  80 KB of dynamic LDS (three A stages, four weight slots), two
+// workgroups per CU.  Linear form, the 3x3 / stride 1 / pad 1 convolution and the general K x K / stride / pad convolution
+// (implicit im2col, k-tile order of gemm_split.hpp), optional GroupNorm statistics in the epilogue (GnStats,
+// split_gemm_device.hpp).  -DGDRNPP2_TIMING_NO_{BREAD,SPLIT,SYNC,DMA}, -DGDRNPP2_NO_RANGE_CHECK: timing-only builds (results
+// invalid) that take one component out of the k-loop (profiles/r03y_split2_kloop_dissection.txt).  The alternatives this kernel
+// was measured against are retired (docs/DESIGN_HISTORY.md, "Retired variants").
 #include "split2_common.hpp"
 
 namespace {
@@ -53,6 +55,9 @@ constexpr int NA = 3;                          // A stages: the A DMA runs two k
 constexpr int A_STAGE_B = 256 * BK * 4;        // fp32 A image of one k-tile: 16 KB
 constexpr int W2_TILE_SLOTS = 2 * KB * BN;     // uint4 slots of one packed 128x16 fp16x2 weight tile
 constexpr int W2_TILE_B = W2_TILE_SLOTS * 16;  // 8 KB
+constexpr int NB = 4;                          // weight slots: k-tile kt in slot kt & 3, the weight DMA runs two k-tiles ahead
+constexpr int NJ = 4;                          // 32-column MFMA tiles per wave: the block tile is 256 x 128
+constexpr int LDS_BYTES = NA * A_STAGE_B + NB * W2_TILE_B;   // 80 KB: two workgroups fill the CU's 160 KB
 
 __device__ int g_split2_range_word;  // sticky range word (GDRNPP_SPLIT2_NONFINITE | GDRNPP_SPLIT2_SMALL_ROWS) of launches that pass no word of their own
 
@@ -98,25 +103,6 @@ struct HalfSplit2T {
   }
 };
 
-#ifdef GDRNPP2_TIMING_A_DIRECT
-// Timing-only experiment (results invalid; profiles/r04_a_direct.txt): what would the k-loop cost if the fp32 A rows of the
-// linear form went from global memory straight to VGPRs — no LDS-DMA fill and no ds_read of the A stages (they are private to
-// their wave, LDS buys them only asynchrony)?  A lane issues the loads of its MFMA operand rows (8 consecutive k per half: two
-// global_load_dwordx4 per half and k-tile) for k-tile kt + 2 in slots 4 / 5 of k-tile kt and waits for them at the end of the
-// same k-tile; the data lands in four scratch registers and is NOT used — the split keeps working on whatever its x registers
-// hold.  (A build that used the data faulted: a value that is still in flight must not be copied, and the register allocator
-// copies loop-carried values at the back edge — a production form needs the k-loop in assembly.)
-using u32x4v = __attribute__((ext_vector_type(4))) unsigned;
-struct ADirectScratch { u32x4v d[4]; };
-__device__ __forceinline__ void gload_scratch(u32x4v& a, u32x4v& b, unsigned voff, const void* sbase) {
-  asm volatile("global_load_dwordx4 %0, %2, %3\n\tglobal_load_dwordx4 %1, %2, %3 offset:16"
-               : "=&v"(a), "=&v"(b) : "v"(voff), "s"(sbase) : "memory");
-}
-__device__ __forceinline__ void wait_scratch(ADirectScratch& s) {
-  asm volatile("s_waitcnt vmcnt(0)" : "+v"(s.d[0]), "+v"(s.d[1]), "+v"(s.d[2]), "+v"(s.d[3]) : : "memory");
-}
-#endif
-
 // W f32[N][K] -> packed fp16 [N/128][K/16][2][2][128][8]; one thread per (row, k-block) = 8 consecutive k.
 // trailer (16 B behind the tiles): {amax bits, 2^-e, 2^e, rows-below-range bit (weight_rows_range_kernel)}
 __global__ void pack_weight2_kernel(const float* __restrict__ W, uint4* __restrict__ packed, int N, int K) {
@@ -151,38 +137,24 @@ __global__ void pack_weight2_kernel(const float* __restrict__ W, uint4* __restri
 // CONV: 0 = linear (A row-major [M,K]), 1 = 3x3 / stride 1 / pad 1 convolution over an NHWC image (geometry folded at compile
 //       time), 2 = any KH x KW / stride / zero padding with at most 32 taps (ConvNeXt's 2x2/2 downsamples, Patch-PnP's 3x3/2)
 // GNS: GroupNorm (sum, sum of squares) partials of the stored result per wave (64 rows x 8-channel groups), CONV only
-// NJ: 32-column MFMA tiles per wave.  4: block tile 256 x 128, 24 slots per k-tile, 80 KB LDS, two workgroups per CU.
-//     8: block tile 256 x 256 (two packed weight tiles side by side), 48 slots per k-tile, 256 accumulator registers — one wave
-//     per SIMD, 80 KB LDS, one workgroup per CU: per MFMA half the A traffic (LDS-DMA, raw fragment reads, split arithmetic) of NJ = 4.
 // APRE: A is an "f16x2 rows" tensor (linear form only).  c_rows (run time): C is written as one (bias / GELU epilogues).
-template <int EPI, int CONV, bool GNS, int NJ, bool APRE = false>
-__global__ __launch_bounds__(256, NJ == 4 ? 2 : 1) void gemm_split2_pipe_kernel(const float* __restrict__ A, const uint4* __restrict__ Wp,
+template <int EPI, int CONV, bool GNS, bool APRE = false>
+__global__ __launch_bounds__(256, 2) void gemm_split2_pipe_kernel(const float* __restrict__ A, const uint4* __restrict__ Wp,
                                                                   const float* __restrict__ bias,
                                                                   const float* __restrict__ gamma,
                                                                   const float* __restrict__ resid, float* __restrict__ C,
                                                                   int M, int N, int K, ConvGeom cg, int panel, GnStats gn, int* range_flag, int c_rows) {
   static_assert(!APRE || CONV == 0, "f16x2-rows A: linear form only");
   using HalfSplit2 = HalfSplit2T<APRE>;
-  constexpr int BNB = NJ * 32;                     // block columns
-  constexpr int NWT = NJ / 4;                      // packed 128-column weight tiles per block
-  constexpr int B_STAGE_B = NWT * W2_TILE_B;       // 8 / 16 KB
-#ifndef GDRNPP2_SINGLE_BARRIER   // -DGDRNPP2_SINGLE_BARRIER: the two-slot form with a barrier per k-tile (A/B; bitwise equal, 0.75 % slower per step)
-  // PAIR: FOUR weight slots (k-tile kt in slot kt & 3), the weight DMA runs two k-tiles ahead and the workgroup meets at ONE barrier per
-  // TWO k-tiles (behind the odd one): the slots a pair of k-tiles reads were complete at the previous barrier, the slots its DMA
-  // fills were last read before it.  Waves of a workgroup may then drift by a whole k-tile instead of waiting for each other 2 x.
-  constexpr bool PAIR = NJ == 4;
-#else
-  constexpr bool PAIR = false;
-#endif
-  constexpr int NS = 6 * NJ;                       // MFMA slots per k-tile
-  constexpr int NBP = 2 * NWT;                     // weight DMA pieces per wave and k-tile
-  constexpr int SB = NS - NJ / 2 - 3;              // slot of the barrier: behind it NJ/2 slots of fragment reads + one raw A read
-  extern __shared__ uint4 smem[];  // the only LDS object: [NA][1024] A slots | [2][NWT * 512] weight slots
+  constexpr int NS = 6 * NJ;   // MFMA slots per k-tile: 24
+  constexpr int SB = 19;       // slot of the wait (and, in odd k-tiles, the barrier): behind it two slots of weight fragment
+                               // reads and one raw A read
+  extern __shared__ uint4 smem[];  // the only LDS object: [NA][1024] A slots | [NB][512] weight slots
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int ntn = N / BNB;
+  const int ntn = N / BN;
   const TileMN tile = tile_coords(xcd_tile_id(), ntn, panel, M);   // panel order for wide layers, see launch_split_pipe (gemm_split_pipe.hip)
-  const int tile_n = tile.n, m0 = tile.m * 256, n0 = tile_n * BNB;
+  const int tile_n = tile.n, m0 = tile.m * 256, n0 = tile_n * BN;
   const int nk = K / BK;
   const unsigned lds0 = lds_addr(smem);
   const float wsc = reinterpret_cast<const float*>(Wp + (size_t)(N / BN) * nk * W2_TILE_SLOTS)[1];   // 2^-e of the weight scale (trailer)
@@ -232,7 +204,7 @@ __global__ __launch_bounds__(256, NJ == 4 ? 2 : 1) void gemm_split2_pipe_kernel(
   if constexpr (CONV) cpt = cg.C / BK;
   const int ntaps = CONV == 1 ? 9 : (CONV == 2 ? K / cg.C : 1), ckw = CONV == 1 ? 3 : cg.KW, cpad = CONV == 1 ? 1 : cg.pad;
   const unsigned boff = (unsigned)((wave * 2) * 64 + lane) * 16u;
-  const char* const wbase = reinterpret_cast<const char*>(Wp + (size_t)tile_n * NWT * nk * W2_TILE_SLOTS);
+  const char* const wbase = reinterpret_cast<const char*>(Wp + (size_t)tile_n * nk * W2_TILE_SLOTS);
   const unsigned ldsA = lds0 + (unsigned)(wave * 4) * 1024u;
   const unsigned ldsB = lds0 + (unsigned)(NA * A_STAGE_B) + (unsigned)(wave * 2) * 1024u;
 
@@ -257,8 +229,8 @@ __global__ __launch_bounds__(256, NJ == 4 ? 2 : 1) void gemm_split2_pipe_kernel(
       GDRNPP_CONV_KTILE(kt, cpt, ntaps);
       wkt = tap * cpt + chunk;
     }
-    constexpr int t = c >> 1, sub = c & 1;   // piece c = half `sub` of this wave's 2 KB share of the packed 128-column tile t
-    dma_s(boff, wbase + (((size_t)t * nk + wkt) * W2_TILE_B + sub * 1024), ldsB + sb + (unsigned)(t * W2_TILE_B + sub * 1024));
+    // piece c = half c of this wave's 2 KB share of the packed weight tile
+    dma_s(boff, wbase + ((size_t)wkt * W2_TILE_B + c * 1024), ldsB + sb + (unsigned)(c * 1024));
   };
 
   f32x16 acc[2][NJ];
@@ -275,56 +247,43 @@ __global__ __launch_bounds__(256, NJ == 4 ? 2 : 1) void gemm_split2_pipe_kernel(
   const int aslot0 = 4 * lrow0 + ((2 * fk) ^ g0), aslot1 = 4 * lrow0 + ((2 * fk + 1) ^ g0);
   const uint4* const sA = smem;
   const uint4* const sBf = smem + NA * (A_STAGE_B / 16) + fk * BN + frow;
-#ifdef GDRNPP2_TIMING_A_DIRECT
-  constexpr bool ADIR = CONV == 0;     // linear form only
-  const unsigned gvoff0 = (unsigned)min(m0 + lrow0, M - 1) * (unsigned)(K * 4) + (unsigned)(fk * 32);
-  const unsigned gvoff1 = (unsigned)min(m0 + lrow0 + 32, M - 1) * (unsigned)(K * 4) + (unsigned)(fk * 32);
-  [[maybe_unused]] ADirectScratch ads;
-#else
-  constexpr bool ADIR = false;
-#endif
 
   auto load_half = [&](HalfSplit2& hs, int stage, int half) {
     hs.load(sA + stage * (A_STAGE_B / 16) + half * 128, aslot0, aslot1);
   };
 
-  // fragment slot of column tile J, split plane P, relative to sBf (+ stage)
-  auto bslot = [](int P, int J) { return (J >> 2) * W2_TILE_SLOTS + P * KB * BN + (J & 3) * 32; };
+  // fragment slot of column tile J, split plane P, relative to sBf (+ weight slot)
+  auto bslot = [](int P, int J) { return P * KB * BN + J * 32; };
 
   // range check: per lane the sum of squares of the h halves it has multiplied (row frow / frow + 32 of the wave, k-blocks fk),
   // two accumulators per row half; -DGDRNPP2_NO_RANGE_CHECK: timing-only build without it
   [[maybe_unused]] float ssq[4] = {0.f, 0.f, 0.f, 0.f};
 
-  // One k-tile, NS = 6 NJ slots (slot S: product group G = S / (2 NJ) in the order h*l, l*h, h*h; row half I, column tile J).
+  // One k-tile, NS = 24 slots (slot S: product group G = S / 8 in the order h*l, l*h, h*h; row half I, column tile J).
   // cur: split A fragments of k-tile kt; nxt: receives the split of k-tile kt+1 (its raw first half is already in nxt[0].x).
-  // fbL holds the weight split l of kt on entry (dead after slot 2 NJ - 1, refilled with the split l of kt+1 behind the
-  // barrier); fbH is read in slots 1, 3, .. NJ - 1 and used from slot 2 NJ.  BS: weight stage of kt (compile-time parity).
+  // fbL holds the weight split l of kt on entry (dead after slot 7, refilled with the split l of kt+1 behind slot SB); fbH is
+  // read in slots 1 and 3 and used from slot 8.  ODD: parity of kt (compile time).  The workgroup meets at ONE barrier per TWO
+  // k-tiles, behind slot SB of the odd one: the weight slots a pair of k-tiles reads were complete at the previous barrier, the
+  // slots its DMA fills were last read before it.  Waves of a workgroup may then drift by a whole k-tile.
   // sa1 / sa2 / sa_wr: A stages of kt+1, of kt+2, and the one receiving kt+NA (= the stage kt has left).
-  auto ktile = [&](int kt, HalfSplit2 (&cur)[2], HalfSplit2 (&nxt)[2], f16x8 (&fbL)[NJ], f16x8 (&fbH)[NJ], auto bs_, int sa1, int sa2,
+  auto ktile = [&](int kt, HalfSplit2 (&cur)[2], HalfSplit2 (&nxt)[2], f16x8 (&fbL)[NJ], f16x8 (&fbH)[NJ], auto odd_, int sa1, int sa2,
                    int sa_wr) {
-    constexpr int BS = decltype(bs_)::value;
-    const uint4* const b = sBf + (PAIR ? (kt & 3) : BS) * (B_STAGE_B / 16);
-    const uint4* const bn = sBf + (PAIR ? ((kt + 1) & 3) : (BS ^ 1)) * (B_STAGE_B / 16);
-    const int kt_b = min(kt + (PAIR ? 2 : 1), nk - 1), kt_a = min(kt + NA, nk - 1);
-    const unsigned sb_wr = (unsigned)((PAIR ? ((kt + 2) & 3) : (BS ^ 1)) * B_STAGE_B), sa_wr_b = (unsigned)(sa_wr * A_STAGE_B);
+    constexpr int ODD = decltype(odd_)::value;
+    const uint4* const b = sBf + (kt & 3) * (W2_TILE_B / 16);
+    const uint4* const bn = sBf + ((kt + 1) & 3) * (W2_TILE_B / 16);
+    const int kt_b = min(kt + 2, nk - 1), kt_a = min(kt + NA, nk - 1);
+    const unsigned sb_wr = (unsigned)(((kt + 2) & 3) * W2_TILE_B), sa_wr_b = (unsigned)(sa_wr * A_STAGE_B);
     static_for<0, NS>([&](auto s_) {
       constexpr int S = decltype(s_)::value;
       constexpr int G = S / (2 * NJ), I = (S % (2 * NJ)) / NJ, J = S % NJ;
       const f16x8 fa = (G == 1) ? cur[I].template frag<1>() : cur[I].template frag<0>();
       const f16x8 fb = (G == 0) ? fbL[J] : fbH[J];
       acc[I][J] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa, fb, acc[I][J], 0, 0, 0);
-      // weight DMA of k-tile kt+1, then A DMA of k-tile kt+NA (the A pieces are the newest four loads at the wait)
+      // weight DMA of k-tile kt+2 (slots 0, 2), then A DMA of k-tile kt+NA (slots 4 .. 10; the A pieces are the newest four
+      // loads at the wait)
 #ifndef GDRNPP2_TIMING_NO_DMA
-      if constexpr (S % 2 == 0 && S < 2 * NBP) dma_b(kt_b, sb_wr, std::integral_constant<int, S / 2>{});
-      if constexpr (!ADIR && S % 2 == 0 && S >= 2 * NBP && S < 2 * NBP + 8) dma_a(kt_a, sa_wr_b, std::integral_constant<int, (S - 2 * NBP) / 2>{});
-#endif
-#ifdef GDRNPP2_TIMING_A_DIRECT
-      if constexpr (ADIR) {
-        const char* gsrc = reinterpret_cast<const char*>(A) + (size_t)min(kt + 2, nk - 1) * (BK * 4);
-        if constexpr (S == 2 * NBP) gload_scratch(ads.d[0], ads.d[1], gvoff0, gsrc);
-        if constexpr (S == 2 * NBP + 1) gload_scratch(ads.d[2], ads.d[3], gvoff1, gsrc);
-        if constexpr (S == NS - 1) wait_scratch(ads);
-      }
+      if constexpr (S % 2 == 0 && S < 4) dma_b(kt_b, sb_wr, std::integral_constant<int, S / 2>{});
+      if constexpr (S % 2 == 0 && S >= 4 && S < 12) dma_a(kt_a, sa_wr_b, std::integral_constant<int, (S - 4) / 2>{});
 #endif
 #ifndef GDRNPP2_TIMING_NO_BREAD   // timing-only builds (results invalid)
       if constexpr (S % 2 == 1 && S < NJ) {   // weight split h of kt
@@ -334,21 +293,19 @@ __global__ __launch_bounds__(256, NJ == 4 ? 2 : 1) void gemm_split2_pipe_kernel(
       }
 #endif
 #ifndef GDRNPP2_NO_RANGE_CHECK
-      // sums of squares of cur's h halves in slots without split arithmetic (cur[..].h stays live through group h*h);
-      // -DGDRNPP2_RC_SLOTS=a,b,c,d moves the four pairs for A/B timing (profiles/r04c_range_check_slots.txt)
-#ifndef GDRNPP2_RC_SLOTS
-#define GDRNPP2_RC_SLOTS 0, 2, 11, 12
-#endif
+      // sums of squares of cur's h halves in the four slots without split arithmetic (cur[..].h stays live through group
+      // h*h); the fastest of the placements measured in profiles/r04c_range_check_slots.txt
       {
-        constexpr int rc[4] = {GDRNPP2_RC_SLOTS};
+        constexpr int rc[4] = {0, 2, 11, 12};
         if constexpr (S == rc[0]) { ssq[2] = sumsq2(cur[1].h[0], ssq[2]); ssq[3] = sumsq2(cur[1].h[1], ssq[3]); }
         if constexpr (S == rc[1]) { ssq[2] = sumsq2(cur[1].h[2], ssq[2]); ssq[3] = sumsq2(cur[1].h[3], ssq[3]); }
         if constexpr (S == rc[2]) { ssq[0] = sumsq2(cur[0].h[0], ssq[0]); ssq[1] = sumsq2(cur[0].h[1], ssq[1]); }
         if constexpr (S == rc[3]) { ssq[0] = sumsq2(cur[0].h[2], ssq[0]); ssq[1] = sumsq2(cur[0].h[3], ssq[1]); }
       }
 #endif
-      constexpr int S1 = NJ == 4 ? 13 : 20;   // first split slot of the second half (its raw read four slots earlier)
-      if constexpr (!ADIR && S == S1 - 4) load_half(nxt[1], sa1, 1);   // APRE: nxt[1].h / .l directly (dead since the previous k-tile)
+      constexpr int S1 = 13;   // first split slot of the second row half (its raw read four slots earlier).  Declared here and
+                               // not beside SB: from there the f16x2-rows kernels come out with other register numbers
+      if constexpr (S == S1 - 4) load_half(nxt[1], sa1, 1);   // APRE: nxt[1].h / .l directly (dead since the previous k-tile)
       // split of the next k-tile: first half in slots 3..10, second half in slots S1..S1+7
 #ifndef GDRNPP2_TIMING_NO_SPLIT
       if constexpr (S >= 3 && S < 11) nxt[0].template step<S - 3>();
@@ -363,12 +320,12 @@ __global__ __launch_bounds__(256, NJ == 4 ? 2 : 1) void gemm_split2_pipe_kernel(
 #ifndef GDRNPP2_TIMING_NO_SYNC
         wait_vmcnt<4>();
         __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): every LDS read of the stages about to be refilled has returned
-        if constexpr (!PAIR || BS == 1) __builtin_amdgcn_s_barrier();
+        if constexpr (ODD) __builtin_amdgcn_s_barrier();
 #endif
       }
-      // behind the barrier: weight split l of k-tile kt+1 (fbL is dead since slot 7) and the raw first half of k-tile kt+2
+      // behind slot SB: weight split l of k-tile kt+1 (fbL is dead since slot 7) and the raw first half of k-tile kt+2
       // (cur[0] is nxt[0] of the next k-tile; only cur[0].h / .l are still in use)
-      // (APRE: the A read goes first — it IS the operand of slot 0 of the next k-tile, cur[0].h / .l are dead since slots 4 NJ + NJ - 1 / 3 NJ - 1)
+      // (APRE: the A read goes first — it IS the operand of slot 0 of the next k-tile, cur[0].h / .l are dead since slots 19 / 11)
       constexpr int SL = APRE ? SB + 1 : SB;         // slot before the first weight read
 #ifndef GDRNPP2_TIMING_NO_BREAD
       if constexpr (S > SL && S <= SL + NJ / 2) {
@@ -377,35 +334,27 @@ __global__ __launch_bounds__(256, NJ == 4 ? 2 : 1) void gemm_split2_pipe_kernel(
         fbL[j0 + 1] = __builtin_bit_cast(f16x8, bn[bslot(1, j0 + 1)]);
       }
 #endif
-      if constexpr (!ADIR && S == (APRE ? SB + 1 : SB + NJ / 2 + 1)) load_half(cur[0], sa2, 0);
+      if constexpr (S == (APRE ? SB + 1 : SB + NJ / 2 + 1)) load_half(cur[0], sa2, 0);
       __builtin_amdgcn_sched_barrier(0);
     });
   };
 
-  // ---- prologue: k-tiles 0 .. 2 of A and k-tile 0 of the weights; split k-tile 0; first fragments of the loop
+  // ---- prologue: k-tiles 0 .. 2 of A and k-tiles 0, 1 of the weights; split k-tile 0; first fragments of the loop
   HalfSplit2 f0[2], f1[2];
   f16x8 fbL[NJ], fbH[NJ];
-  if constexpr (!ADIR) {
-    static_for<0, 4>([&](auto c) { dma_a(0, 0u, c); });
-    static_for<0, NBP>([&](auto c) { dma_b(0, 0u, c); });
-    if constexpr (PAIR) static_for<0, NBP>([&](auto c) { dma_b(min(1, nk - 1), (unsigned)B_STAGE_B, c); });
-    static_for<0, 4>([&](auto c) { dma_a(min(1, nk - 1), (unsigned)A_STAGE_B, c); });
-    static_for<0, 4>([&](auto c) { dma_a(min(2, nk - 1), 2u * A_STAGE_B, c); });
-    wait_vmcnt<4>();
-    __builtin_amdgcn_s_barrier();
-    load_half(f0[0], 0, 0);
-    load_half(f0[1], 0, 1);
-  } else {   // timing-only: the x registers start from finite values and are never refilled
-    static_for<0, NBP>([&](auto c) { dma_b(0, 0u, c); });
-    wait_vmcnt<0>();
-    __builtin_amdgcn_s_barrier();
-#pragma unroll
-    for (int e = 0; e < 8; ++e) { f0[0].x[e] = f0[1].x[e] = f1[0].x[e] = f1[1].x[e] = 1.0f + 0.01f * (float)(e + lane); }
-  }
+  static_for<0, 4>([&](auto c) { dma_a(0, 0u, c); });
+  static_for<0, 2>([&](auto c) { dma_b(0, 0u, c); });
+  static_for<0, 2>([&](auto c) { dma_b(min(1, nk - 1), (unsigned)W2_TILE_B, c); });
+  static_for<0, 4>([&](auto c) { dma_a(min(1, nk - 1), (unsigned)A_STAGE_B, c); });
+  static_for<0, 4>([&](auto c) { dma_a(min(2, nk - 1), 2u * A_STAGE_B, c); });
+  wait_vmcnt<4>();
+  __builtin_amdgcn_s_barrier();
+  load_half(f0[0], 0, 0);
+  load_half(f0[1], 0, 1);
   static_for<0, 8>([&](auto s) { f0[0].template step<decltype(s)::value>(); f0[1].template step<decltype(s)::value>(); });
 #pragma unroll
   for (int j = 0; j < NJ; ++j) fbL[j] = __builtin_bit_cast(f16x8, sBf[bslot(1, j)]);
-  if constexpr (!ADIR) load_half(f1[0], 1, 0);
+  load_half(f1[0], 1, 0);
 
   // ---- main loop, two k-tiles per trip (nk is even: K % 32 == 0)
   int sa = 0;  // kt % NA
@@ -449,36 +398,26 @@ __global__ __launch_bounds__(256, NJ == 4 ? 2 : 1) void gemm_split2_pipe_kernel(
   if (word && lane == 0) atomicOr(range_flag ? range_flag : &g_split2_range_word, word);
 }
 
-template <int EPI, int CONV, bool GNS, int NJ, bool APRE = false>
-int launch_nj(const float* A, const uint4* Wp, const float* bias, const float* gamma, const float* resid, float* C, int M, int N,
-              int K, ConvGeom cg, int panel, GnStats gn, int* range_flag, hipStream_t st, const char* what, int c_rows = 0) {
-#ifndef GDRNPP2_SINGLE_BARRIER
-  constexpr int lds_bytes = NA * A_STAGE_B + (NJ == 4 ? 4 : 2) * (NJ / 4) * W2_TILE_B;   // NJ = 4: 80 KB, two workgroups fill the CU's 160 KB
-#else
-  constexpr int lds_bytes = NA * A_STAGE_B + 2 * (NJ / 4) * W2_TILE_B;
-#endif
-  const int rc = gdrnpp::ensure_dynamic_lds((const void*)gemm_split2_pipe_kernel<EPI, CONV, GNS, NJ, APRE>, lds_bytes);
+template <int EPI, int CONV, bool GNS, bool APRE = false>
+int launch_kernel(const float* A, const uint4* Wp, const float* bias, const float* gamma, const float* resid, float* C, int M, int N,
+                  int K, ConvGeom cg, int panel, GnStats gn, int* range_flag, hipStream_t st, const char* what, int c_rows = 0) {
+  const int rc = gdrnpp::ensure_dynamic_lds((const void*)gemm_split2_pipe_kernel<EPI, CONV, GNS, APRE>, LDS_BYTES);
   if (rc) return rc;
-  const long tiles = (long)((M + 255) / 256) * (N / (NJ * 32));
+  const long tiles = (long)((M + 255) / 256) * (N / BN);
   GDRNPP_REQUIRE(tiles < (1l << 30), GDRNPP_ELIMIT, "%s: grid too large", what);
-  hipLaunchKernelGGL((gemm_split2_pipe_kernel<EPI, CONV, GNS, NJ, APRE>), dim3((unsigned)tiles), dim3(256), lds_bytes, st, A, Wp, bias, gamma,
+  hipLaunchKernelGGL((gemm_split2_pipe_kernel<EPI, CONV, GNS, APRE>), dim3((unsigned)tiles), dim3(256), LDS_BYTES, st, A, Wp, bias, gamma,
                      resid, C, M, N, K, cg, panel, gn, range_flag, c_rows);
   return gdrnpp::check_launch(what);
 }
 
-// 256 x 256 block tiles (NJ = 8) are kept for A/B only (option split2_wide = 1, N % 256 == 0): bitwise equal, and measured slower
-// or equal on every ConvNeXt-B MLP shape of 128 ROIs (36 blocks 18.5 vs 17.0 ms; stage-2 fc2 207 vs 207 us, stage-3 fc2 246 vs
-// 189 us, stage-0 fc1 623 vs 533 us: one wave per SIMD has nobody to hide its LDS / DMA latencies behind)
+// a_rows: A is an f16x2-rows tensor; those forms exist for the two MLP layers (GELU / scale + residual)
 template <int EPI, int CONV, bool GNS>
 int launch_one(const float* A, const uint4* Wp, const float* bias, const float* gamma, const float* resid, float* C, int M, int N,
                int K, ConvGeom cg, int panel, GnStats gn, int* range_flag, hipStream_t st, const char* what, int a_rows = 0, int c_rows = 0) {
-  if constexpr (CONV == 0 && EPI != EPI_BIAS) {   // the f16x2-rows forms exist for the two MLP layers (GELU / scale + residual)
-    if (a_rows) return launch_nj<EPI, CONV, GNS, 4, true>(A, Wp, bias, gamma, resid, C, M, N, K, cg, panel, gn, range_flag, st, what, c_rows);
+  if constexpr (CONV == 0 && EPI != EPI_BIAS) {
+    if (a_rows) return launch_kernel<EPI, CONV, GNS, true>(A, Wp, bias, gamma, resid, C, M, N, K, cg, panel, gn, range_flag, st, what, c_rows);
   }
-  const int opt = gdrnpp::option_split2_wide();
-  const bool wide = N % 256 == 0 && opt == 1;
-  if (wide) return launch_nj<EPI, CONV, GNS, 8>(A, Wp, bias, gamma, resid, C, M, N, K, cg, panel, gn, range_flag, st, what, c_rows);
-  return launch_nj<EPI, CONV, GNS, 4>(A, Wp, bias, gamma, resid, C, M, N, K, cg, panel, gn, range_flag, st, what, c_rows);
+  return launch_kernel<EPI, CONV, GNS>(A, Wp, bias, gamma, resid, C, M, N, K, cg, panel, gn, range_flag, st, what, c_rows);
 }
 
 }  // namespace
@@ -581,8 +520,8 @@ extern "C" int gdrnpp_conv2d_f32_split2(const float* x_nhwc, const void* W_packe
   const uint4* Wp = (const uint4*)W_packed;
   const char* what = "gdrnpp_conv2d_f32_split2";
   if (epilogue == EPI_GELU)
-    return launch_nj<EPI_GELU, 2, false, 4>(x_nhwc, Wp, bias, nullptr, nullptr, y_nhwc, (int)M, Cout, KH * KW * Cin, cg, 0, gn, range_flag, st, what);
-  return launch_nj<EPI_BIAS, 2, false, 4>(x_nhwc, Wp, bias, nullptr, nullptr, y_nhwc, (int)M, Cout, KH * KW * Cin, cg, 0, gn, range_flag, st, what);
+    return launch_one<EPI_GELU, 2, false>(x_nhwc, Wp, bias, nullptr, nullptr, y_nhwc, (int)M, Cout, KH * KW * Cin, cg, 0, gn, range_flag, st, what);
+  return launch_one<EPI_BIAS, 2, false>(x_nhwc, Wp, bias, nullptr, nullptr, y_nhwc, (int)M, Cout, KH * KW * Cin, cg, 0, gn, range_flag, st, what);
 }
 
 // The library's own sticky range word (launches with range_flag == NULL): *word = the bits raised since the last reset

@@ -98,9 +98,9 @@ struct Grouped {
                            // out of bounds (a detector label >= NUM_CLASSES must not come out as finite garbage maps)
 };
 
-// CONV: 0 = linear (A row-major [M,K]), 1 = 3x3 / stride 1 / pad 1 convolution over an NHWC image (implicit im2col)
+// Linear form only (A row-major [M,K]); convolutions run on the kernels of gemm_split.hip.
 // NA: A stages (2: one k-tile ahead, 3: two k-tiles ahead)
-template <int EPI, int CONV, int NA>
+template <int EPI, int NA>
 __global__ __launch_bounds__(256, 2) void gemm_split_pipe_kernel(const float* __restrict__ A, const uint4* __restrict__ Wp,
                                                                  const float* __restrict__ bias,
                                                                  const float* __restrict__ gamma,
@@ -112,44 +112,24 @@ __global__ __launch_bounds__(256, 2) void gemm_split_pipe_kernel(const float* __
   const int ntn = N / BN;
   const TileMN tile = tile_coords(xcd_tile_id(), ntn, grp.panel, M);   // panel order for wide layers, see launch_split_pipe
   const int tile_n = tile.n, m0 = tile.m * 256, n0 = tile_n * BN;
-  // split-K (linear form, cg.nk_split > 0): workgroup (x, y) multiplies k-tiles [y * nk_split, (y + 1) * nk_split) and writes
+  // split-K (cg.nk_split > 0, the only field of cg in use): workgroup (x, y) multiplies k-tiles [y * nk_split, (y + 1) * nk_split) and writes
   // the partial result C + y*M*N; gdrnpp_linear_f32_splitk sums the partials in fixed order and applies bias / epilogue
-  const int kt0 = (!CONV && cg.nk_split > 0) ? (int)blockIdx.y * cg.nk_split : 0;
-  const int nk = (!CONV && cg.nk_split > 0) ? cg.nk_split : K / BK;
-  if (!CONV && cg.nk_split > 0) C += (size_t)blockIdx.y * (size_t)M * (size_t)N;
+  const int kt0 = cg.nk_split > 0 ? (int)blockIdx.y * cg.nk_split : 0;
+  const int nk = cg.nk_split > 0 ? cg.nk_split : K / BK;
+  if (cg.nk_split > 0) C += (size_t)blockIdx.y * (size_t)M * (size_t)N;
   const unsigned lds0 = lds_addr(smem);
 
   // ---- DMA lanes: piece c (0..3) of this wave fills A slots (wave*4 + c)*64 + lane = rows wave*64 + c*16 + lane/4, chunk
   // q = (lane & 3) ^ ((row >> 2) & 3) of the row's 64-byte k segment (the swizzle is on the source address)
   const int prow = lane >> 2, pq = lane & 3;
-  unsigned aoff[4];        // linear: byte offset of the lane's chunk from A + kt*64
-  const float* ap[4];      // conv: anchor pixel of the lane's row (+ chunk)
-  unsigned okmask[4];      // conv: bit tap = the tap lies inside the image
-  int cpt = 1;
+  unsigned aoff[4];        // byte offset of the lane's chunk from A + kt*64
 #pragma unroll
   for (int c = 0; c < 4; ++c) {
     const int lrow = wave * 64 + c * 16 + prow;
     const int q = pq ^ ((lrow >> 2) & 3);
     const int arow = min(m0 + lrow, M - 1);
-    if constexpr (CONV) {
-      const int img = arow / (cg.H * cg.W), pp = arow - img * (cg.H * cg.W);
-      const int iy = pp / cg.W, ix = pp - iy * cg.W;
-      ap[c] = A + ((size_t)arow) * cg.C + q * 4;
-      unsigned mk = 0;
-#pragma unroll
-      for (int t = 0; t < 9; ++t) {
-        const int dy = t / 3 - 1, dx = t % 3 - 1;
-        if ((unsigned)(iy + dy) < (unsigned)cg.H && (unsigned)(ix + dx) < (unsigned)cg.W) mk |= 1u << t;
-      }
-      okmask[c] = mk;
-      aoff[c] = 0;
-    } else {
-      aoff[c] = (unsigned)arow * (unsigned)(K * 4) + (unsigned)(q * 16);
-      ap[c] = nullptr;
-      okmask[c] = 0;
-    }
+    aoff[c] = (unsigned)arow * (unsigned)(K * 4) + (unsigned)(q * 16);
   }
-  if constexpr (CONV) cpt = cg.C / BK;
   const unsigned boff = (unsigned)((wave * 3) * 64 + lane) * 16u;
   const int grp_i = grp.sel ? grp.sel[m0 / grp.rows_per_group] : 0;   // weight / bias slice of this tile's rows
   if (grp.sel && (unsigned)grp_i >= (unsigned)grp.n_groups) {          // workgroup-uniform: nothing was issued yet
@@ -169,25 +149,11 @@ __global__ __launch_bounds__(256, 2) void gemm_split_pipe_kernel(const float* __
   // piece c of the A image of k-tile kt -> stage byte offset sb
   auto dma_a = [&](int kt, unsigned sb, auto cc) {
     constexpr int c = decltype(cc)::value;
-    if constexpr (CONV) {
-      GDRNPP_CONV_KTILE(kt, cpt, 9);
-      const int c0 = chunk * BK;
-      const int ky = tap / 3, dy = ky - 1, dx = tap - ky * 3 - 1;
-      const long off = ((long)dy * cg.W + dx) * cg.C + c0;
-      const bool ok = (okmask[c] >> tap) & 1u;
-      dma_v(ok ? (const void*)(ap[c] + off) : (const void*)g_zero_page, ldsA + sb + c * 1024u);
-    } else {
-      dma_s(aoff[c], reinterpret_cast<const char*>(A) + (size_t)(kt0 + kt) * (BK * 4), ldsA + sb + c * 1024u);
-    }
+    dma_s(aoff[c], reinterpret_cast<const char*>(A) + (size_t)(kt0 + kt) * (BK * 4), ldsA + sb + c * 1024u);
   };
   auto dma_b = [&](int kt, unsigned sb, auto cc) {
     constexpr int c = decltype(cc)::value;
-    int wkt = kt0 + kt;
-    if constexpr (CONV) {
-      GDRNPP_CONV_KTILE(kt, cpt, 9);
-      wkt = tap * cpt + chunk;
-    }
-    dma_s(boff, wbase + ((size_t)wkt * B_STAGE_B + c * 1024), ldsB + sb + c * 1024u);
+    dma_s(boff, wbase + ((size_t)(kt0 + kt) * B_STAGE_B + c * 1024), ldsB + sb + c * 1024u);
   };
 
   f32x16 acc[2][4];
@@ -229,9 +195,6 @@ __global__ __launch_bounds__(256, 2) void gemm_split_pipe_kernel(const float* __
       constexpr int SA_ = TA[G], SB_ = TB[G];
       const bf16x8 fa = cur[I].template frag<SA_>();
       const bf16x8 fb = (SB_ == 1) ? fbY[J] : fbX[J];
-#ifdef GDRNPP_TIMING_HALF_PRODUCTS   // timing-only build (results invalid): three of the six products
-      if constexpr (G >= 3)
-#endif
       acc[I][J] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa, fb, acc[I][J], 0, 0, 0);
       // weight DMA of k-tile kt+1, then A DMA of k-tile kt+NA (the A pieces are the newest four loads at the wait)
       if constexpr (S == 0) dma_b(kt_b, sb_wr, std::integral_constant<int, 0>{});
@@ -501,7 +464,7 @@ int launch_pipe128(const float* A, const uint4* Wp, const float* bias, const flo
 }
 
 // hipFuncSetAttribute is a per-device setting: done once per (kernel, device), not per launch
-template <int EPI, int CONV, int NA>
+template <int EPI, int NA>
 int launch_one(const float* A, const uint4* Wp, const float* bias, const float* gamma, const float* resid, float* C, int M,
                int N, int K, ConvGeom cg, Grouped grp, hipStream_t st, const char* what) {
   constexpr int lds_bytes = NA * A_STAGE_B + 2 * B_STAGE_B;
@@ -509,29 +472,28 @@ int launch_one(const float* A, const uint4* Wp, const float* bias, const float* 
   int dev = 0;
   GDRNPP_HIP_TRY(hipGetDevice(&dev));
   if (dev >= 0 && dev < 64 && !raised[dev]) {
-    GDRNPP_HIP_TRY(hipFuncSetAttribute((const void*)gemm_split_pipe_kernel<EPI, CONV, NA>,
+    GDRNPP_HIP_TRY(hipFuncSetAttribute((const void*)gemm_split_pipe_kernel<EPI, NA>,
                                        hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
     raised[dev] = true;
   }
   const long tiles = (long)((M + 255) / 256) * (N / BN);
-  const unsigned splits = (!CONV && cg.nk_split > 0) ? (unsigned)((K / BK) / cg.nk_split) : 1u;
-  hipLaunchKernelGGL((gemm_split_pipe_kernel<EPI, CONV, NA>), dim3((unsigned)tiles, splits), dim3(256), lds_bytes, st, A, Wp, bias,
+  const unsigned splits = cg.nk_split > 0 ? (unsigned)((K / BK) / cg.nk_split) : 1u;
+  hipLaunchKernelGGL((gemm_split_pipe_kernel<EPI, NA>), dim3((unsigned)tiles, splits), dim3(256), lds_bytes, st, A, Wp, bias,
                      gamma, resid, C, M, N, K, cg, grp);
   return gdrnpp::check_launch(what);
 }
 
-template <int EPI, int CONV>
+template <int EPI>
 int launch_na(int a_stages, const float* A, const uint4* Wp, const float* bias, const float* gamma, const float* resid,
               float* C, int M, int N, int K, ConvGeom cg, Grouped grp, hipStream_t st, const char* what) {
-  if (a_stages == 3) return launch_one<EPI, CONV, 3>(A, Wp, bias, gamma, resid, C, M, N, K, cg, grp, st, what);
-  return launch_one<EPI, CONV, 2>(A, Wp, bias, gamma, resid, C, M, N, K, cg, grp, st, what);
+  if (a_stages == 3) return launch_one<EPI, 3>(A, Wp, bias, gamma, resid, C, M, N, K, cg, grp, st, what);
+  return launch_one<EPI, 2>(A, Wp, bias, gamma, resid, C, M, N, K, cg, grp, st, what);
 }
 
-template <int CONV>
 int launch_epi(int epilogue, int a_stages, const float* A, const uint4* Wp, const float* bias, const float* gamma,
                const float* resid, float* C, int M, int N, int K, ConvGeom cg, Grouped grp, hipStream_t st, const char* what) {
   return with_epilogue(epilogue, [&](auto epi) {
-    return launch_na<decltype(epi)::value, CONV>(a_stages, A, Wp, bias, gamma, resid, C, M, N, K, cg, grp, st, what);
+    return launch_na<decltype(epi)::value>(a_stages, A, Wp, bias, gamma, resid, C, M, N, K, cg, grp, st, what);
   });
 }
 
@@ -541,8 +503,7 @@ namespace gdrnpp {
 namespace splitgemm {
 
 int launch_split_pipe(const float* A, const uint4* Wp, const float* bias, const float* gamma, const float* resid, float* C,
-                      int M, int N, int K, int epilogue, bool conv, ConvGeom cg, int a_stages, hipStream_t st,
-                      const char* what) {
+                      int M, int N, int K, int epilogue, ConvGeom cg, int a_stages, hipStream_t st, const char* what) {
   if (K % 32 || N % BN || M <= 0) return -1;
   // Wide layers (packed weight beyond an XCD's L2: N*K*6 bytes > 2 MB, at least 8 column tiles) walk the tiles in panels of
   // option split_gemm_panel (4) row blocks, column tile outer: workgroups that start back to back then share the weight tile
@@ -551,14 +512,10 @@ int launch_split_pipe(const float* A, const uint4* Wp, const float* bias, const 
   // Measured fetch of the 32768x512 -> 2048 layer per launch: row-major 464 MB, panels of 2/3/4/5/6/8/16: 464/415/317/376/
   // 348/357/575 MB (profiles/r02l_gemm_traffic_by_shape.md); launch time unchanged (the operands come from the memory-side
   // cache either way).
-  const int panel = (!conv && N / BN >= 8 && (long)N * K * 6 > (2l << 20)) ? gdrnpp::option_split_gemm_panel() : 0;
+  const int panel = (N / BN >= 8 && (long)N * K * 6 > (2l << 20)) ? gdrnpp::option_split_gemm_panel() : 0;
   const Grouped grp{nullptr, 1, 0, 0, N, panel, 1};
-  if (conv) {
-    if (!(cg.KW == 3 && cg.stride == 1 && cg.pad == 1 && K == 9 * cg.C && cg.C % BK == 0)) return -1;
-    return launch_epi<1>(epilogue, a_stages, A, Wp, bias, gamma, resid, C, M, N, K, cg, grp, st, what);
-  }
   if ((unsigned long long)M * (unsigned long long)K * 4ull >= (1ull << 32)) return -1;  // 32-bit lane offsets
-  return launch_epi<0>(epilogue, a_stages, A, Wp, bias, gamma, resid, C, M, N, K, cg, grp, st, what);
+  return launch_epi(epilogue, a_stages, A, Wp, bias, gamma, resid, C, M, N, K, cg, grp, st, what);
 }
 
 // 128-row form: plain launch with the fused epilogue (nk_split == 0) or split-K partials (nk_split > 0, bias-less raw sums)
@@ -577,7 +534,7 @@ int launch_split_pipe_splitk(const float* A, const uint4* Wp, float* partials, i
   if (K % 32 || N % BN || M <= 0 || nk_split < 2 || nk_split % 2 || (K / BK) % nk_split) return -1;
   if ((unsigned long long)M * (unsigned long long)K * 4ull >= (1ull << 32)) return -1;  // 32-bit lane offsets
   const Grouped grp{nullptr, 1, 0, 0, N, 0, 1};
-  return launch_epi<0>(EPI_BIAS, a_stages, A, Wp, nullptr, nullptr, nullptr, partials, M, N, K,
+  return launch_epi(EPI_BIAS, a_stages, A, Wp, nullptr, nullptr, nullptr, partials, M, N, K,
                        ConvGeom{0, 0, 0, 0, 0, 0, 0, 0, nk_split}, grp, st, what);
 }
 
@@ -599,6 +556,6 @@ extern "C" int gdrnpp_linear_f32_split_grouped(const float* A, const void* W_pac
                  "gdrnpp_linear_f32_split_grouped: M*K*4 must stay below 4 GiB");
   GDRNPP_REQUIRE((long)(M / 256) * (N / BN) < (1l << 30), GDRNPP_ELIMIT, "gdrnpp_linear_f32_split_grouped: grid too large");
   const Grouped grp{group_sel, rows_per_group, (long)(N / BN) * (K / BK) * W_TILE_SLOTS, N, n_store, 0, n_groups};
-  return launch_epi<0>(EPI_BIAS, gdrnpp::option_split_gemm_pipe() == 2 ? 2 : 3, A, (const uint4*)W_packed_stack, bias_stack, nullptr,
+  return launch_epi(EPI_BIAS, gdrnpp::option_split_gemm_pipe() == 2 ? 2 : 3, A, (const uint4*)W_packed_stack, bias_stack, nullptr,
                        nullptr, C, M, N, K, ConvGeom{0, 0, 0, 0, 0, 0, 0, 0, 0}, grp, (hipStream_t)stream, "gdrnpp_linear_f32_split_grouped");
 }

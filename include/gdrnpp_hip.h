@@ -44,7 +44,6 @@ const char* gdrnpp_last_error(void);
  *                              LDS-DMA kernel (default 1; results are bitwise identical)
  *   "split_gemm_pipe"  0 / 2 / 3   256-row tiles of the linear form use the software-pipelined LDS-DMA kernel with two /
  *                              three A stages (default 3; bitwise identical to the other kernels); 0 = off
- *   "split_gemm_pipe_conv"  0 / 1   the 3x3 / stride 1 / pad 1 convolution uses it too (default 0)
  *   "split_gemm_big_tiles"  >= 1    256x128 output tiles (pipelined / LDS-DMA kernels) when the problem has at least this many
  *                                   of them (default 256 = one per CU), 128x128 tiles below
  *   "split_gemm_panel"      0, 2..64  wide layers (packed weight > 2 MB, N >= 1024) walk their tiles in panels of that many
@@ -53,8 +52,6 @@ const char* gdrnpp_last_error(void);
  *   "dwconv_tile"      -1 / 0 / 1 / 2   output pixels per thread of the depthwise 7x7 kernel: by launch size (default: 2x8 at
  *                                   the headline batch, 2x4 / 1x4 when a launch has too few tiles for the chip) / force 2x8 / 2x4 / 1x4
  *   "mlp_fused_pipe"   0 / 1       fused stage-0 MLP (gdrnpp_convnext_mlp_f32_fused): software-pipelined tile loop (default 1) or the plain loop (A/B switch)
- *   "split2_wide"      0 / 1       three-product kernels (gdrnpp_*_split2): 256x256 block tiles whenever N % 256 == 0 (A/B switch,
- *                                   default 0: bitwise identical and measured slower than 256x128)
  *   "dwconv_lds_w"     0 / 1       depthwise 7x7 + LayerNorm: [49][C] weights in LDS with persistent workgroups where they fit (default 1) or
  *                                   through L1 / L2 without LDS (A/B switch: which of two kernels sharing the chip yields is decided by the LDS
  *                                   a workgroup holds, profiles/r06_dwconv_shared.txt; bitwise identical)

@@ -104,6 +104,17 @@ def test_python_binding_covers_header():
     assert lib.gdrnpp_version() >= 100
 
 
+def test_retired_options_are_unknown():
+    """The 256x256 three-product tiles and the 3x3 convolution on the pipelined six-product kernel are gone with their switches: a
+    stale A/B script fails instead of measuring the default twice."""
+    from gdrnpp_bop2022_amd import hip_lib
+
+    for name in ("split2_wide", "split_gemm_pipe_conv"):
+        with pytest.raises(RuntimeError, match=f"unknown option '{name}'"):
+            hip_lib.set_option(name, 1)
+    hip_lib.set_option("split_gemm_panel", 4)   # (its default)
+
+
 def test_missing_library_fails_loudly(tmp_path):
     from gdrnpp_bop2022_amd import hip_lib
 

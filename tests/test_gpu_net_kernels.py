@@ -188,7 +188,8 @@ def test_split_gemm_kernels_are_bitwise_equal(hip):
     """The 256-row kernels — register-staged (A split before the LDS store), LDS-DMA (fp32 A, split at fragment-read time)
     and the software-pipelined LDS-DMA kernel with 2 and 3 A stages (split of k-tile t+1 inside the MFMA stream of k-tile t,
     counted vmcnt) — add the same six partial products per k-step in the same order: identical bits, for the linear, 3x3
-    and general convolution forms, ragged M included (the general convolution stays on the first two kernels)."""
+    and general convolution forms, ragged M included (the pipelined kernel is linear-only: in every mode the convolutions run
+    on the first two kernels)."""
     modes = [(0, 0), (1, 0), (1, 2), (1, 3)]   # (split_gemm_glds, split_gemm_pipe)
     try:
         hip.set_option("split_gemm_mi4", 1)            # force 256-row tiles at these small sizes
@@ -197,7 +198,6 @@ def test_split_gemm_kernels_are_bitwise_equal(hip):
             torch.manual_seed(5)
             hip.set_option("split_gemm_glds", glds)
             hip.set_option("split_gemm_pipe", pipe)
-            hip.set_option("split_gemm_pipe_conv", 1 if pipe else 0)
             m, k, n = 1024 + 37, 512, 256
             x = torch.randn(m, k, device=DEV)
             w = torch.randn(n, k, device=DEV) * (k ** -0.5)
@@ -220,7 +220,6 @@ def test_split_gemm_kernels_are_bitwise_equal(hip):
         hip.set_option("split_gemm_mi4", -1)
         hip.set_option("split_gemm_glds", 1)
         hip.set_option("split_gemm_pipe", 3)
-        hip.set_option("split_gemm_pipe_conv", 0)
     for other in outs[1:]:
         for a_, b_ in zip(outs[0], other):
             assert torch.equal(a_, b_)

@@ -56,7 +56,8 @@ def test_packed_image_is_the_scaled_weight_to_22_bits(hip):
 
 
 @pytest.mark.parametrize("m,k,n,epi", [(4096, 128, 512, "gelu"), (4096, 512, 128, "scale_res"), (1000, 2048, 512, "scale_res"),
-                                       (777, 1024, 2304, "none"), (8192, 512, 2048, "gelu"), (2048, 4096, 1024, "none")])
+                                       (777, 1024, 2304, "none"), (8192, 512, 2048, "gelu"), (2048, 4096, 1024, "none"),
+                                       (3000, 256, 512, "gelu"), (1024, 2048, 256, "scale_res"), (70000, 128, 1024, "none")])
 def test_linear_three_products_vs_fp64(hip, m, k, n, epi):
     torch.manual_seed(m + k + n)
     x = torch.randn(m, k, device=DEV)
@@ -93,33 +94,6 @@ def test_linear_three_products_panel_walk_is_bitwise_row_major(hip):
     hip.set_option("split_gemm_panel", 4)
     for o in outs[1:]:
         assert torch.equal(o, outs[0])
-
-
-@pytest.mark.parametrize("m,k,n,epi", [(3000, 256, 512, "gelu"), (1024, 2048, 256, "scale_res"), (70000, 128, 1024, "none")])
-def test_wide_block_tiles_are_bitwise_equal(hip, m, k, n, epi):
-    """256 x 256 block tiles (one wave per SIMD, two packed weight tiles side by side) against 256 x 128: same products, same order."""
-    torch.manual_seed(m)
-    x, w, b = torch.randn(m, k, device=DEV), torch.randn(n, k, device=DEV) * k ** -0.5, torch.randn(n, device=DEV)
-    gamma = torch.randn(n, device=DEV) if epi == "scale_res" else None
-    res = torch.randn(m, n, device=DEV) if epi == "scale_res" else None
-    pk = hip.pack_weight_f16x2(w)
-    outs = []
-    for wide in (0, 1):
-        hip.set_option("split2_wide", wide)
-        outs.append(hip.linear_f32_split(x, pk, b, epi, gamma, res))
-    hip.set_option("split2_wide", -1)
-    assert torch.equal(outs[0], outs[1])
-    # the 3x3 convolution with GroupNorm statistics, both forms
-    xc = torch.randn(8, 64, 32, 32, device=DEV).contiguous(memory_format=torch.channels_last)
-    wc = torch.randn(256, 64, 3, 3, device=DEV) * (9 * 64) ** -0.5
-    pkc = hip.pack_conv_weight_f16x2(wc)
-    gw, gb = torch.randn(256, device=DEV), torch.randn(256, device=DEV)
-    ys = []
-    for wide in (0, 1):
-        hip.set_option("split2_wide", wide)
-        ys.append(hip.conv3x3_f32_split(xc, pkc, b[:256].contiguous(), True))
-    hip.set_option("split2_wide", -1)
-    assert torch.equal(ys[0], ys[1])
 
 
 def test_small_scale_activations_raise_the_small_rows_bit(hip):

@@ -91,18 +91,14 @@ def test_linear_three_products_c_abi_writes_m_rows(hip, m):
 
 
 @pytest.mark.parametrize("kind", ("int", "hl"))
-def test_wide_tiles_exact(hip, kind):
+def test_two_column_tiles_ragged_m_exact(hip, kind):
+    """Two 128-column tiles over two row blocks, the second with 44 of its 256 rows."""
     m, k, n = 300, 96, 256
     c = SL.linear_case(m, k, n, kind)
     x, pk = c["A"].to(DEV), hip.pack_weight_f16x2(c["W"].to(DEV))
-    try:
-        for wide in (0, 1):
-            hip.set_option("split2_wide", wide)
-            for epi in SL.EPILOGUES:
-                bias, name, gamma, resid = _epi_args(c, epi)
-                _exact(hip.linear_f32_split(x, pk, bias, name, gamma, resid), c["want"][epi], f"split2_wide={wide} {kind} {epi}")
-    finally:
-        hip.set_option("split2_wide", -1)
+    for epi in SL.EPILOGUES:
+        bias, name, gamma, resid = _epi_args(c, epi)
+        _exact(hip.linear_f32_split(x, pk, bias, name, gamma, resid), c["want"][epi], f"{kind} {epi}")
     _no_words(hip)
 
 

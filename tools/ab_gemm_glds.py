@@ -16,7 +16,6 @@ if os.environ.get("MODES"):
 def set_mode(m):
     hip_lib.set_option("split_gemm_glds", m[1])
     hip_lib.set_option("split_gemm_pipe", m[2])
-    hip_lib.set_option("split_gemm_pipe_conv", 1 if m[2] else 0)
 
 
 def timeit(fn, n=10):
@@ -93,7 +92,7 @@ for m in MODES:
 hip_lib.set_option("split_gemm_mi4", -1)
 res.append(dict(shape="linear odd M=70001", equal=all(torch.equal(ys[0], y) for y in ys[1:])))
 res.append(dict(shape="conv3x3 odd image 3x37x29", equal=all(torch.equal(yc[0], y) for y in yc[1:])))
-hip_lib.set_option("split_gemm_glds", 1); hip_lib.set_option("split_gemm_pipe", 3); hip_lib.set_option("split_gemm_pipe_conv", 0)
+hip_lib.set_option("split_gemm_glds", 1); hip_lib.set_option("split_gemm_pipe", 3)
 for r in res:
     print(json.dumps(r))
 print(json.dumps({"step_estimate_" + m[0] + "_ms": round(sum(r.get(m[0] + "_ms", 0) * r.get("weight", 0) for r in res), 3) for m in MODES}))

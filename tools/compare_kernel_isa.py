@@ -4,7 +4,10 @@ count, instructions between the first and the last v_mfma (the k-loop with its p
 streams are identical after normalising symbol names and label numbers.  Prints one markdown table row per kernel;
 --diff KERNEL_SUBSTRING prints the unified diff of the normalised streams of the kernels whose name contains it.
 
-    python tools/compare_kernel_isa.py OLD.s NEW.s [--diff SUBSTRING]
+--rename REGEX=REPLACEMENT (repeatable) rewrites the kernel names of OLD.s before they are matched, for a change that drops a
+template parameter: --rename 'gemm_split_pipe_kernel<(\d), 0, (\d)>=gemm_split_pipe_kernel<\1, \2>'.
+
+    python tools/compare_kernel_isa.py OLD.s NEW.s [--diff SUBSTRING] [--rename REGEX=REPLACEMENT]...
 """
 import difflib
 import re
@@ -68,10 +71,17 @@ def main():
         i = args.index("--diff")
         want = args[i + 1]
         del args[i:i + 2]
+    renames = []
+    while "--rename" in args:
+        i = args.index("--rename")
+        renames.append(args[i + 1].split("=", 1))
+        del args[i:i + 2]
     old, new = parse(args[0]), parse(args[1])
     names = demangle(sorted(set(old) | set(new)))
     by_short = lambda ks: {short(names[k]): v for k, v in ks.items()}
     old, new = by_short(old), by_short(new)
+    for pat, repl in renames:
+        old = {re.sub(pat, repl, k): v for k, v in old.items()}
     print("| kernel | vgpr | agpr | sgpr | spill | scratch | LDS | v_mfma | k-loop span | stream |")
     print("|---|---|---|---|---|---|---|---|---|---|")
     ok = True
