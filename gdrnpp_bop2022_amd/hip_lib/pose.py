@@ -290,6 +290,64 @@ def bop_errors(meshes: MeshSet, obj, R_est, t_est, R_gt, t_gt, K, sym_R, sym_t, 
     return out
 
 
+VSD_WORKSPACE_BUDGET = 256 << 20        # bytes of projected vertices one ``gdrnpp_vsd_counts`` launch may stage
+
+
+def vsd_counts(meshes: MeshSet, obj, im_idx, R_est, t_est, R_gt, t_gt, K, diameter, depth_test, taus, delta, z_near: float = 1.0,
+               z_far: float = 1e6, workspace_budget: int = VSD_WORKSPACE_BUDGET) -> torch.Tensor:
+    """``gdrnpp_vsd_counts``: the pixel counts behind BOP19 VSD of b (estimate, ground truth) pairs -> i32[b, 2 + n_tau] = union, inter,
+    cost_0 .. (a row of -1 for a pair whose obj or im_idx is out of range or whose object has no faces).  obj, im_idx i32[b]; R_est,
+    R_gt, K f64[b,3,3|9]; t_est, t_gt f64[b,3] in the unit of the meshes' vertices (mm); diameter f64[b] (1.0 = not normalised);
+    depth_test f32[n_im,H,W] in mm, 0 = missing: all device tensors.  taus: 1..16 floats (a sequence, an array or a tensor); delta: the
+    visibility tolerance.  The meshes need faces.  A launch stages 80 bytes per vertex of the largest model per pair, so the pairs run
+    in chunks that keep that workspace under ``workspace_budget`` bytes, on the current stream, into one output tensor."""
+    dev = meshes.verts.device
+    b = int(obj.shape[0])
+    tau_t = torch.as_tensor(taus, dtype=torch.float64).reshape(-1).to(dev).contiguous()
+    n_tau = int(tau_t.numel())
+    out = torch.empty((b, 2 + n_tau), dtype=torch.int32, device=dev)
+    if b == 0:
+        return out
+    if depth_test.dim() != 3:
+        raise RuntimeError(f"vsd_counts: depth_test must be f32[n_im,H,W], got {tuple(depth_test.shape)}")
+    n_im, H, W = (int(s) for s in depth_test.shape)
+    dp = f32_ptr(depth_test, "depth_test")
+    ints = [(obj, "obj"), (im_idx, "im_idx")]
+    for t, name in ints:
+        dev_ptr(t, torch.int32, name)
+        if t.numel() != b:
+            raise RuntimeError(f"vsd_counts: {name} must hold {b} values, got {tuple(t.shape)}")
+    f64s = [(R_est, "R_est", 9), (t_est, "t_est", 3), (R_gt, "R_gt", 9), (t_gt, "t_gt", 3), (K, "K", 9), (diameter, "diameter", 1)]
+    for t, name, cols in f64s:
+        dev_ptr(t, torch.float64, name)
+        if t.numel() != b * cols:
+            raise RuntimeError(f"vsd_counts: {name} must hold {b} x {cols} values, got {tuple(t.shape)}")
+    lib = load()
+    per_pair = lib.gdrnpp_vsd_counts_workspace_bytes(meshes.c, 1)
+    if per_pair == 0:
+        raise RuntimeError("vsd_counts: the mesh set does not say its largest vertex count")
+    chunk = max(1, min(b, int(workspace_budget) // per_pair))
+    nbytes = lib.gdrnpp_vsd_counts_workspace_bytes(meshes.c, chunk)
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    for i0 in range(0, b, chunk):                          # stream order keeps one workspace safe across the chunks
+        n = min(chunk, b - i0)
+        launch("gdrnpp_vsd_counts", meshes.c, *[t.reshape(-1)[i0:i0 + n].data_ptr() for t, _ in ints],
+               *[t.reshape(-1)[cols * i0:cols * (i0 + n)].data_ptr() for t, _, cols in f64s], dp, n_im, H, W, tau_t.data_ptr(), n_tau,
+               float(delta), float(z_near), float(z_far), out[i0:i0 + n].data_ptr(), n, ws.data_ptr(), nbytes)
+    return out
+
+
+def vsd_errors(meshes: MeshSet, obj, im_idx, R_est, t_est, R_gt, t_gt, K, diameter, depth_test, taus, delta, z_near: float = 1.0,
+               z_far: float = 1e6, workspace_budget: int = VSD_WORKSPACE_BUDGET) -> torch.Tensor:
+    """BOP19 VSD of b pairs -> f64[b, n_tau]: ``(cost_k + (union - inter)) / float(union)`` of ``vsd_counts`` as pose_error.py:110-126
+    forms it (integers below 2^31, one fp64 division), 1.0 for every tau where union is 0, NaN where the row is -1."""
+    c = vsd_counts(meshes, obj, im_idx, R_est, t_est, R_gt, t_gt, K, diameter, depth_test, taus, delta, z_near, z_far, workspace_budget)
+    union, inter = c[:, 0:1].to(torch.int64), c[:, 1:2].to(torch.int64)
+    e = (c[:, 2:].to(torch.int64) + (union - inter)).to(torch.float64) / union.to(torch.float64)
+    e = torch.where(union == 0, torch.ones_like(e), e)
+    return torch.where(union < 0, torch.full_like(e, float("nan")), e)
+
+
 def pnp_iter_from_correspondences(img_pts, mdl_pts, count, K, R_net, t_net, return_info: bool = False):
     """Net-initialised iterative PnP (gdrn_evaluator.py:241-371, pnp_type="iter") for all ROIs at once."""
     b, stride, _ = img_pts.shape

@@ -2,7 +2,8 @@
 reference's BOP-toolkit fork (lib/pysixd/inout.py ``load_ply``: dict with 'pts' [V,3], 'faces' [F,3] and, when
 present, 'normals', 'colors', 'texture_uv'), as used at gdrn_evaluator.py:58-63 and
 lib/render_vispy/model3d.py.  Written from the PLY format specification (ASCII and binary little/big endian,
-list properties for faces); polygons with more than 3 vertices are fan-triangulated."""
+list properties for faces); polygons with more than 3 vertices are fan-triangulated.  ``load_depth(path)`` reads a BOP depth image
+(16-bit PNG) as float32, as the reference's ``load_depth`` does with imageio."""
 from __future__ import annotations
 
 import struct
@@ -94,6 +95,21 @@ def load_ply(path, vertex_scale: float = 1.0) -> dict:
                 faces.append((poly[0], poly[j], poly[j + 1]))
     model["faces"] = np.asarray(faces, np.int64).reshape(-1, 3)
     return model
+
+
+def load_depth(path) -> np.ndarray:
+    """A depth image as float32 [H,W], the stored integers unscaled (multiply by the image's ``depth_scale`` for millimetres).  16-bit
+    PNG, read through PIL; the ``.tif`` depth of ITODD is not read."""
+    path = str(path)
+    if path.lower().endswith((".tif", ".tiff")):
+        raise NotImplementedError(f"load_depth: {path}: .tif depth images (itodd) are not read here, only 16-bit PNG")
+    from PIL import Image
+
+    with Image.open(path) as im:
+        d = np.asarray(im)
+    if d.ndim != 2:
+        raise ValueError(f"load_depth: {path}: expected a single-channel depth image, got shape {d.shape}")
+    return d.astype(np.float32)
 
 
 def models_to_meshset(models, device="cuda"):

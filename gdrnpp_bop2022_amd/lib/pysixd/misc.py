@@ -1,5 +1,6 @@
 """``get_symmetry_transformations`` with the signature and the result of the reference's lib/pysixd/misc.py:234-282: the set of rigid
-transformations that map an object model onto itself, which MSSD and MSPD take their minimum over (host code, NumPy)."""
+transformations that map an object model onto itself, which MSSD and MSPD take their minimum over, and ``overlapping_sphere_projections`` (:1219-1241), the host test that spares VSD a render
+(host code, NumPy)."""
 from __future__ import annotations
 
 import math
@@ -51,3 +52,15 @@ def flatten_symmetry_transformations(per_object: list):
     R = np.stack([np.asarray(t["R"], np.float64).reshape(9) for s in per_object for t in s])
     t = np.stack([np.asarray(t["t"], np.float64).reshape(3) for s in per_object for t in s])
     return np.ascontiguousarray(R), np.ascontiguousarray(t), off
+
+
+def overlapping_sphere_projections(radius, p1, p2) -> bool:
+    """Whether the silhouettes of two spheres of ``radius`` centred at p1 and p2 overlap, approximately, with the result of the
+    reference's misc.py:1219-1241: the test eval_calc_errors.py:363-378 makes before it renders a pair for VSD.  The centres are projected
+    to the plane z = 1; a sphere at depth z has the radius ``radius / z`` there.  A centre in the camera plane never overlaps."""
+    p1, p2 = np.asarray(p1, np.float64).reshape(3), np.asarray(p2, np.float64).reshape(3)
+    z1, z2 = p1[2], p2[2]
+    if z1 == 0 or z2 == 0:
+        return False
+    gap = np.linalg.norm((p1 / z1)[:2] - (p2 / z2)[:2])
+    return bool(gap < radius * (1.0 / z1 + 1.0 / z2))

@@ -2,7 +2,9 @@
 :440-445): NumPy arrays in, a float out.  Each call runs ``gdrnpp_pose_errors`` (csrc/pose_error.hip) with b = 1 on the current
 device; ``mssd / mspd`` (:131-179) run ``gdrnpp_bop_errors`` (csrc/bop_error.hip) the same way, the entry point
 ``gdrn_modeling.bop_eval.bop19_scores`` runs once for a whole results file — the entry point ``GDRN_EvaluatorCustom`` runs once for a whole dataset; use ``hip_lib.pose_errors`` directly for more
-than a handful of poses.  ``pts`` is taken as float32 (what a ``hip_lib.MeshSet`` holds); there is no CPU fallback."""
+than a handful of poses.  ``pts`` is taken as float32 (what a ``hip_lib.MeshSet`` holds); there is no CPU fallback.
+``vsd`` (:22-128) runs ``gdrnpp_vsd_counts`` (csrc/vsd_error.hip) with b = 1; its ``renderer`` is a ``VsdRenderer``: the resident meshes
+(with faces) that the kernel renders, in place of the toolkit's GL renderer."""
 from __future__ import annotations
 
 import numpy as np
@@ -88,3 +90,35 @@ def mssd(R_est, t_est, R_gt, t_gt, pts, syms):
 def mspd(R_est, t_est, R_gt, t_gt, K, pts, syms):
     """Maximum Symmetry-Aware Projection Distance: as ``mssd``, between the projections by ``K``, in pixels."""
     return float(_bop_errors(R_est, t_est, R_gt, t_gt, K, pts, syms)[1])
+
+
+class VsdRenderer:
+    """What ``vsd`` needs in place of the toolkit's renderer: the models as a ``hip_lib.MeshSet`` with faces, resident on the device,
+    and the map from BOP object id to the index in that set."""
+
+    def __init__(self, meshes, obj_index):
+        self.meshes = meshes
+        self.obj_index = {int(k): int(v) for k, v in obj_index.items()}
+
+
+def vsd(R_est, t_est, R_gt, t_gt, depth_test, K, delta, taus, normalized_by_diameter, diameter, renderer, obj_id, cost_type="step"):
+    """Visible Surface Discrepancy (Hodan, Michel et al., ECCV 2018), one error per misalignment tolerance in ``taus``: a list of floats.
+    depth_test: hxw test depth image in the unit of the model (mm), 0 = missing; renderer: a ``VsdRenderer``."""
+    if cost_type != "step":
+        if cost_type == "tlinear":
+            raise NotImplementedError("pysixd.pose_error.vsd: cost_type 'tlinear' is not computed here (the evaluation scripts use 'step')")
+        raise ValueError("Unknown pixel matching cost.")
+    if not torch.cuda.is_available():
+        raise RuntimeError("pysixd.pose_error: needs a HIP device (no CPU fallback)")
+    from ... import hip_lib
+
+    dev = renderer.meshes.verts.device
+
+    def T(a, n):
+        return torch.from_numpy(np.ascontiguousarray(np.asarray(a, np.float64).reshape(1, n))).to(dev)
+
+    depth = torch.from_numpy(np.ascontiguousarray(np.asarray(depth_test, np.float32))[None]).to(dev)
+    out = hip_lib.vsd_errors(renderer.meshes, torch.full((1,), renderer.obj_index[int(obj_id)], dtype=torch.int32, device=dev),
+                             torch.zeros(1, dtype=torch.int32, device=dev), T(R_est, 9), T(t_est, 3), T(R_gt, 9), T(t_gt, 3), T(K, 9),
+                             T(diameter if normalized_by_diameter else 1.0, 1), depth, [float(t) for t in taus], float(delta))
+    return [float(x) for x in out.cpu().numpy()[0]]

@@ -354,6 +354,24 @@ int gdrnpp_bop_errors(const gdrnpp_meshes* models, const int* obj, const double*
                       const double* R_gt, const double* t_gt, const double* K, const double* sym_R, const double* sym_t,
                       const int* sym_off, double* out, int b, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- BOP19 VSD — lib/pysixd/pose_error.py:22-128 (cost_type "step") with visibility.py:9-74 ("bop19") and misc.py:604-647, the error
+ * eval_calc_errors.py:376-395 computes per (estimate, ground truth) pair from two full-image depth renders and the test depth image.
+ * Device pointers: obj i32[b] class index into `models` (which need faces; used as gdrnpp_render_depth uses them); im_idx i32[b]
+ * index into depth_test f32[n_im,H,W] (millimetres, 0 = missing); R_est, R_gt, K f64[b,9] (of K only fx, fy, cx, cy are used, as the
+ * toolkit passes them); t_est, t_gt f64[b,3] in the unit of the vertices; diameter f64[b], the divisor of the pixel-wise distances
+ * (1.0 = not normalised: x / 1.0 is exact); taus f64[n_tau], 1 <= n_tau <= 16; delta: the visibility tolerance; only fragments with
+ * 0 < z_near <= Z <= z_far are rendered.  counts i32[b, 2 + n_tau] = union, inter, cost_0 .. cost_{n_tau-1} (pixel counts); the
+ * error at tau_k is (cost_k + (union - inter)) / (double)union, or 1.0 when union is 0.  What only the device can see — an obj outside
+ * [0, n_obj), an im_idx outside [0, n_im), an object without faces or vertices, or with more vertices than models->max_verts —
+ * gives that pair's whole row -1.  Integer sums only: two calls give bit-equal output.  models->max_verts must be set (> 0).
+ * workspace: gdrnpp_vsd_counts_workspace_bytes(models, b) = b * (2 * max_verts * 40 + 32) bytes (the projected vertices of both
+ * poses and their pixel boxes).  Argument errors return GDRNPP_EINVAL / GDRNPP_ELIMIT and launch nothing. */
+size_t gdrnpp_vsd_counts_workspace_bytes(const gdrnpp_meshes* models, int b);
+int gdrnpp_vsd_counts(const gdrnpp_meshes* models, const int* obj, const int* im_idx, const double* R_est, const double* t_est,
+                      const double* R_gt, const double* t_gt, const double* K, const double* diameter, const float* depth_test,
+                      int n_im, int H, int W, const double* taus, int n_tau, float delta, double z_near, double z_far, int* counts,
+                      int b, void* workspace, size_t workspace_bytes, void* stream);
+
 /* device-to-device copy into a raw device pointer on `stream` — the transfer CppEGLRenderer::map_tensor performs with
  * cudaMemcpy2DFromArray in the reference (lib/egl_renderer/cpp/egl_renderer.cpp:262-298): attachment -> caller's tensor */
 int gdrnpp_copy_d2d(void* dst, const void* src, size_t bytes, void* stream);
