@@ -102,6 +102,13 @@ def run_features(features, x):
                 continue
             x = hip_layers.groupnorm_act(layer, None, x)
         elif isinstance(layer, nn.UpsamplingBilinear2d) and layer.scale_factor in (2, 2.0):
+            nxt = features[i + 1] if i + 1 < n else None
+            if isinstance(nxt, ConvModule) and nxt.norm_name == "gn":   # upsample -> conv3x3 -> GN (-> GELU): the matrix work at the low resolution
+                y = hip_layers.upsample2x_conv3x3_groupnorm_act(nxt.conv, getattr(nxt, "gn"), nxt.activate, x)
+                if y is not None:
+                    x = y
+                    i += 2
+                    continue
             x = hip_layers.upsample2x(layer, x)
         elif isinstance(layer, nn.Conv2d):
             gn = features[i + 1] if i + 1 < n else None

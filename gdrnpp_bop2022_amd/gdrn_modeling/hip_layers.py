@@ -438,6 +438,46 @@ def conv3x3_groupnorm_act(conv: nn.Conv2d, gn: nn.GroupNorm, act: nn.Module | No
                                          gelu=act is not None, x3_slot=slot)
 
 
+# [UpsamplingBilinear2d(2), ConvModule 3x3] of the geometry head at the low resolution (hip_lib.upsample2x_conv3x3_groupnorm_act):
+# the library option "upconv_lowres" (default 1) is the switch, 0 = the upsampling and the convolution as two layers.
+_UPCONV_MIN_PIXELS = 32768     # high-resolution pixels of the launch (8 ROIs at 64 x 64, 32 at 32 x 32) from which the pair takes the
+                               # low-resolution form: where the convolution it replaces runs its 256-row tiles (conv3x3_groupnorm_act)
+_UPCONV_CHUNK_ROWS = 32768     # low-resolution pixels per tap GEMM (32 ROIs at 32 x 32): its [rows, 9 * Cout] result is the workspace,
+                               # 302 MB at Cout = 256 whatever the batch (profiles/upconv_lowres.md)
+
+
+def set_upconv_lowres(min_pixels: int | None = None, chunk_rows: int | None = None) -> None:
+    """A/B and test knobs of the low-resolution form: fewest high-resolution pixels that take it, low-resolution pixels per chunk."""
+    global _UPCONV_MIN_PIXELS, _UPCONV_CHUNK_ROWS
+    if min_pixels is not None:
+        _UPCONV_MIN_PIXELS = int(min_pixels)
+    if chunk_rows is not None:
+        _UPCONV_CHUNK_ROWS = int(chunk_rows)
+
+
+def upsample2x_conv3x3_groupnorm_act(conv: nn.Conv2d, gn: nn.GroupNorm, act: nn.Module | None, x: torch.Tensor):
+    """[UpsamplingBilinear2d(2), Conv2d 3x3/1/1, GroupNorm(, GELU)] on the low-resolution input ``x``: the nine tap products at
+    the low resolution (a quarter of the convolution's matrix work), then a gather that interpolates and sums them and takes
+    the GroupNorm statistics.  Returns None outside the form of ``conv3x3_groupnorm_act`` (or with the library option
+    "upconv_lowres" at 0, or below the minimum size); the caller then runs the layers one by one."""
+    if not (_CONV_GN_FUSED and _CONV_SPLIT and _MLP_GEMM == "split" and enabled_for(x) and isinstance(conv, nn.Conv2d)
+            and isinstance(gn, nn.GroupNorm) and conv.kernel_size == (3, 3) and conv.stride == (1, 1)
+            and conv.padding == (1, 1) and conv.dilation == (1, 1) and conv.groups == 1 and conv.padding_mode == "zeros"
+            and conv.in_channels % 32 == 0 and conv.out_channels % 128 == 0 and gn.affine
+            and gn.num_channels == conv.out_channels and conv.out_channels == 8 * gn.num_groups and gn.num_groups <= 64
+            and conv.out_channels <= 1024 and 256 % (conv.out_channels // 4) == 0 and _exact_gelu_or_none(act)
+            and x.dim() == 4 and x.shape[1] == conv.in_channels and 0 < x.shape[0] <= 65535
+            and 4 * x.shape[0] * x.shape[2] * x.shape[3] >= _UPCONV_MIN_PIXELS and hip_lib.get_option("upconv_lowres")):
+        return None
+    n, _, h, w = x.shape
+    chunk = max(1, _UPCONV_CHUNK_ROWS // (h * w))
+    w_pk, slot = split_weight(module_cache(conv), "upconv", "w_upconv_pk", conv.weight, hip_lib.pack_upconv_weight_f16x2,
+                              hip_lib.pack_upconv_weight_bf16x3, min(n, chunk) * h * w, 9 * conv.out_channels, conv.in_channels,
+                              slot_key="conv")
+    return hip_lib.upsample2x_conv3x3_groupnorm_act(_cl(x), w_pk, conv.bias, gn.weight, gn.bias, gn.num_groups, gn.eps,
+                                                    gelu=act is not None, x3_slot=slot, chunk=chunk)
+
+
 def linear(fc: nn.Linear, x: torch.Tensor, gelu: bool = False) -> torch.Tensor:
     """nn.Linear on a [M, K] activation with few rows and a long K (Patch-PnP fc1: 8192 -> 1024 on one row per ROI):
     hipBLASLt picks a 256x16 macro-tile for it and streams the 33 MB weight at ~70 GB/s (0.49 ms at 128 ROIs); the split-K

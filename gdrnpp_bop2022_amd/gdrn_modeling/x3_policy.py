@@ -122,13 +122,14 @@ def eligible(m: int, n: int, k_linear: int = 0) -> bool:
     return gemm_products() == 3 and hip_lib.split2_tiles_ok(m, n) and m * k_linear * 4 < (1 << 32)
 
 
-def weight_for(cache: dict, key: str, weight: torch.Tensor, pack3, m: int, n: int, k_linear: int = 0):
+def weight_for(cache: dict, key: str, weight: torch.Tensor, pack3, m: int, n: int, k_linear: int = 0, slot_key: str | None = None):
     """-> (packed three-product weight or None, range-word slot).  None = this launch runs the six-product kernel: the shape is
     outside the three-product kernels, the layer was demoted, or its weight has rows below the range (checked once per weight
-    by the pack kernel)."""
+    by the pack kernel).  ``slot_key``: the layer whose slot (and demotion) this launch shares when ``key`` names a second packed
+    form of the same layer's weight."""
     if not eligible(m, n, k_linear):
         return None, 0
-    s_ = slot(cache, key)
+    s_ = slot(cache, slot_key or key)
     if s_ in _X3_DEMOTED:
         return None, s_
     def build():
@@ -147,10 +148,10 @@ def six_product_weight(cache: dict, key: str, weight: torch.Tensor, pack6) -> to
 
 
 def split_weight(cache: dict, key3: str, key6: str, weight: torch.Tensor, pack3, pack6, m: int, n: int, k_linear: int = 0,
-                 allow3: bool = True):
+                 allow3: bool = True, slot_key: str | None = None):
     """-> (packed weight, range-word slot): the three-product image ``weight_for`` grants (``allow3`` False: none asked for),
     else the six-product one."""
-    w_pk, s_ = weight_for(cache, key3, weight, pack3, m, n, k_linear) if allow3 else (None, 0)
+    w_pk, s_ = weight_for(cache, key3, weight, pack3, m, n, k_linear, slot_key) if allow3 else (None, 0)
     if w_pk is None:
         w_pk = six_product_weight(cache, key6, weight, pack6)
     return w_pk, s_

@@ -14,15 +14,15 @@ State that somebody assigns lives in its owner and is assigned there (``hip_lib.
 """
 from . import abi, dispatch, gemm, net, pose, range_words, roi, yolox  # noqa: F401
 from .abi import (LIB_PATH, SIGNATURES, LaunchTimer, check, copy_d2d, current_stream, dev_ptr, gdrnpp_meshes,  # noqa: F401
-                  gdrnpp_roi_table, load, set_launch_timer, set_option, spin)
+                  gdrnpp_roi_table, get_option, load, set_launch_timer, set_option, spin)
 from .dispatch import (set_conv_splitk, shared_min_rows, shared_min_tiles, shared_min_tiles_scope, split2_tiles_ok,  # noqa: F401
                        split_gemm_tiles)
 from .gemm import (A_F16X2_ROWS, C_F16X2_ROWS, X3, conv2d_f32_split, conv3x3_f32_split, conv3x3_groupnorm_act,  # noqa: F401
                    conv_transpose2d_f32_split, conv_transpose2d_groupnorm_act, convnext_mlp_f32_fused, f16x2_rows_decode,
                    linear_f32_split, linear_f32_split_grouped, linear_f32_splitk, mlp_fused_rows_in_range, mlp_fused_supported,
                    pack_conv3x3_weight_bf16x3, pack_conv_weight_bf16x3, pack_conv_weight_f16x2, pack_deconv_weight_bf16x3, pack_deconv_weight_f16x2,
-                   pack_mlp_fused_f16x2, pack_weight_bf16x3, pack_weight_f16x2, packed_rows_in_range, unpack_weight_bf16x3,
-                   unpack_weight_f16x2)
+                   pack_mlp_fused_f16x2, pack_upconv_weight_bf16x3, pack_upconv_weight_f16x2, pack_weight_bf16x3, pack_weight_f16x2,
+                   packed_rows_in_range, unpack_weight_bf16x3, unpack_weight_f16x2, upsample2x_conv3x3_groupnorm_act, upsample2x_conv3x3_raw)
 from .net import (POINT_PNP_TILE, ROT_DIMS, ROT_MODES, T_MODES, bias_act_nhwc_, dwconv7x7_ln, groupnorm_act, head_tail_nhwc,  # noqa: F401
                   layernorm_nhwc, pnp_fc_heads, pnp_fc_heads_pose, point_pnp_fc, point_pnp_pool, stem_conv4x4_ln, upsample_bilinear2x)
 from .pose import (MeshSet, bop_errors, decode_correspondences, depth_refine, epnp_batched, epnp_ransac, flow_forward, fps, nnd_backward,  # noqa: F401

@@ -36,6 +36,7 @@ _P = c_void_p
 SIGNATURES = {
     "gdrnpp_version": (c_int, []),
     "gdrnpp_set_option": (c_int, [c_char_p, c_int]),
+    "gdrnpp_get_option": (c_int, [c_char_p, POINTER(c_int)]),
     "gdrnpp_copy_d2d": (c_int, [_P, _P, c_size_t, _P]),
     "gdrnpp_epnp_ransac_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "gdrnpp_epnp_ransac": (c_int, [_P, _P, _P, c_int, _P, _P, c_int, c_int, c_float, c_double, _P, _P, _P, _P, _P,
@@ -124,6 +125,8 @@ SIGNATURES = {
     "gdrnpp_point_pnp_workspace_bytes": (c_size_t, [c_int, c_int]),
     "gdrnpp_point_pnp_pool": (c_int, [_P, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, _P, c_size_t, _P]),
     "gdrnpp_point_pnp_fc": (c_int, [_P, c_size_t, _P, _P, _P, _P, _P, c_int, c_int, _P]),
+    "gdrnpp_upconv_gather_partials": (c_int, [c_int, c_int, c_int]),
+    "gdrnpp_upconv_gather_gn_nhwc": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
     "gdrnpp_conv3x3_gnstats_partials": (c_int, [c_int, c_int]),
     "gdrnpp_conv3x3_f32_split_gnstats": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
     "gdrnpp_groupnorm_apply_nhwc": (c_int, [_P, _P, c_int, _P, _P, _P, c_int, c_int, c_int, c_int, c_float, c_int, _P]),
@@ -235,6 +238,13 @@ def spin(micros: int) -> None:
 def set_option(name: str, value: int) -> None:
     """Process-wide tuning switch of the library (``gdrnpp_set_option``; the one entry point without a stream)."""
     check(load().gdrnpp_set_option(name.encode(), int(value)), "gdrnpp_set_option")
+
+
+def get_option(name: str) -> int:
+    """Current value of a process-wide tuning switch (``gdrnpp_get_option``)."""
+    value = c_int(0)
+    check(load().gdrnpp_get_option(name.encode(), ctypes.byref(value)), "gdrnpp_get_option")
+    return value.value
 
 
 def dev_ptr(t: torch.Tensor, dtype: torch.dtype, name: str) -> int:

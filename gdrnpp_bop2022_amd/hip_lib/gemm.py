@@ -126,6 +126,18 @@ def pack_deconv_weight_f16x2(weight):
     return pack_weight_f16x2(weight.detach().permute(2, 3, 1, 0).reshape(kh * kw * cout, cin).contiguous())
 
 
+def pack_upconv_weight_bf16x3(weight):
+    """nn.Conv2d weight [Cout, Cin, 3, 3] -> packed tap-GEMM weight with rows (ky, kx, co), K = Cin (``upsample2x_conv3x3_groupnorm_act``)."""
+    cout, cin, kh, kw = weight.shape
+    return pack_weight_bf16x3(weight.detach().permute(2, 3, 0, 1).reshape(kh * kw * cout, cin).contiguous())
+
+
+def pack_upconv_weight_f16x2(weight):
+    """pack_upconv_weight_bf16x3 in the three-product format."""
+    cout, cin, kh, kw = weight.shape
+    return pack_weight_f16x2(weight.detach().permute(2, 3, 0, 1).reshape(kh * kw * cout, cin).contiguous())
+
+
 def _packed_weight(weight_packed, k: int, what: str, contiguous: bool = False):
     """Validate a packed split-GEMM weight with GEMM depth ``k`` (``contiguous``: and that it is contiguous); returns
     (N, True for the three-product fp16x2 format).  ``what`` is the caller's message."""
@@ -294,3 +306,40 @@ def conv3x3_groupnorm_act(x_cl, weight_packed, bias, gamma, beta, groups: int, e
     else:
         launch("gdrnpp_conv3x3_f32_split_gnstats", *args, timed=("conv3x3", flops, nbytes))
     return _groupnorm_apply(y, part, P, gamma, beta, n, h * w, cout, groups, eps, gelu)
+
+
+def upsample2x_conv3x3_raw(x_cl, weight_packed, bias, groups: int, x3_slot: int = 0, chunk: int = 0):
+    """nn.UpsamplingBilinear2d(2) -> conv3x3 (stride 1, zero pad 1) of a channels_last tensor [N,Cin,H,W] without forming the
+    upsampled tensor: per chunk of ``chunk`` images (0 = all at once) the tap GEMM of the LOW-resolution pixels into
+    [n*H*W, 9*Cout] (``weight_packed`` from pack_upconv_weight_f16x2 / _bf16x3; a quarter of the convolution's matrix work), then
+    ``gdrnpp_upconv_gather_gn_nhwc`` interpolates and sums the nine tap planes -> (raw convolution output, channels_last
+    [N,Cout,2H,2W]; GroupNorm(groups) partial sums f64[N,P,groups,2]; P).  Bitwise independent of ``chunk``."""
+    n, cin, h, w = channels_last_f32(x_cl, "upsample2x_conv3x3_raw")
+    cols, _ = _packed_weight(weight_packed, cin, "weight_packed must come from pack_upconv_weight_bf16x3 / pack_upconv_weight_f16x2 with matching Cin",
+                             contiguous=True)
+    if cols % 9:
+        raise ValueError("weight_packed must hold the nine taps of a 3x3 kernel")
+    cout = cols // 9
+    P = load().gdrnpp_upconv_gather_partials(h, w, cout)
+    if P <= 0:
+        raise ValueError(f"upsample2x_conv3x3_raw: shape H={h} W={w} Cout={cout} is outside the gather kernel")
+    y = torch.empty((n, cout, 2 * h, 2 * w), dtype=torch.float32, device=x_cl.device, memory_format=torch.channels_last)
+    part = torch.empty((n, P, groups, 2), dtype=torch.float64, device=x_cl.device)
+    x2d = x_cl.permute(0, 2, 3, 1).reshape(n * h * w, cin)      # a view of the NHWC memory
+    y_nhwc = y.permute(0, 2, 3, 1)
+    step = n if chunk <= 0 else min(int(chunk), n)
+    for n0 in range(0, n, step):
+        n1 = min(n, n0 + step)
+        taps = linear_f32_split(x2d[n0 * h * w:n1 * h * w], weight_packed, None, _kind="upconv_taps", x3_slot=x3_slot)
+        launch("gdrnpp_upconv_gather_gn_nhwc", taps.data_ptr(), opt_f32_ptr(bias, "bias"), y_nhwc[n0:n1].data_ptr(), part[n0:n1].data_ptr(),
+               n1 - n0, h, w, cout, groups, timed=("hbm:upconv_gather", 0.0, 4.0 * (n1 - n0) * h * w * cout * (9 + 4)))
+    return y, part, P
+
+
+def upsample2x_conv3x3_groupnorm_act(x_cl, weight_packed, bias, gamma, beta, groups: int, eps: float = 1e-5, gelu: bool = False,
+                                     x3_slot: int = 0, chunk: int = 0):
+    """nn.UpsamplingBilinear2d(2) -> conv3x3 (stride 1, pad 1) -> GroupNorm(groups) [-> GELU] of a channels_last tensor at the low
+    resolution (``upsample2x_conv3x3_raw``) + ``gdrnpp_groupnorm_apply_nhwc``."""
+    y, part, P = upsample2x_conv3x3_raw(x_cl, weight_packed, bias, groups, x3_slot, chunk)
+    n, cout, oh, ow = y.shape
+    return _groupnorm_apply(y, part, P, gamma, beta, n, oh * ow, cout, groups, eps, gelu)

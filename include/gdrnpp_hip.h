@@ -56,8 +56,13 @@ const char* gdrnpp_last_error(void);
  *                                   through L1 / L2 without LDS (A/B switch: which of two kernels sharing the chip yields is decided by the LDS
  *                                   a workgroup holds, profiles/r06_dwconv_shared.txt; bitwise identical)
  *   "dwconv_lds_pad"   bytes       experiment only: dynamic LDS the no-LDS form allocates without using it (default 0)
+ *   "upconv_lowres"    0 / 1       read by the callers' routing, not by a launch: a 3x3 convolution behind a bilinear x2 upsampling runs
+ *                                   as a tap GEMM at the low resolution + gdrnpp_upconv_gather_gn_nhwc (default 1) or as the upsampling
+ *                                   and the convolution of the high-resolution tensor (0)
  * unknown name -> GDRNPP_EINVAL. */
 int gdrnpp_set_option(const char* name, int value);
+/* the value gdrnpp_set_option left (clamped as that entry point clamps it) or the default */
+int gdrnpp_get_option(const char* name, int* value);
 
 /* ------------------------------------------------------------------------ */
 /* (1) reference-ABI symbols (host pointers)                                 */
@@ -531,6 +536,17 @@ int gdrnpp_deconv_col2im_nhwc(const float* cols, const float* bias, float* y, in
  * (C / G) % 4 == 0, C / 4 divides 256, G <= 64. */
 int gdrnpp_deconv_col2im_gn_nhwc(const float* cols, const float* bias, float* y, double* gn_partials, int N, int H, int W, int C,
                                  int KS, int stride, int pad, int out_pad, int G, void* stream);
+/* [nn.UpsamplingBilinear2d(2), conv3x3 / stride 1 / zero pad 1] of the geometry head (top_down_doublemask_xyz_region_head.py:80-107)
+ * at the LOW resolution: channel mixing and per-channel interpolation commute, so one gdrnpp_linear_f32_split of the NHWC input
+ * [N*H*W, Cin] with the weight reordered to [(ky, kx, co), ci] gives y_taps f32[N, H, W, 9, C] with a quarter of the convolution's
+ * matrix work, and this gather writes out f32 NHWC [N, 2H, 2W, C]: per output pixel bias (may be NULL), then taps 0..8, each the
+ * align_corners=True interpolation of its tap plane at the neighbouring high-resolution position (nothing where that position is
+ * outside 2H x 2W: zero padding applies there).  gn_partials f64[N, P, G, 2], P = gdrnpp_upconv_gather_partials (0 = shape not
+ * supported), holds the GroupNorm(G) sums of the result for gdrnpp_groupnorm_apply_nhwc; an image's result and partials do not
+ * depend on the other images of the launch.  (C / G) % 4 == 0, C / 4 divides 256, G <= 64. */
+int gdrnpp_upconv_gather_partials(int H, int W, int C);
+int gdrnpp_upconv_gather_gn_nhwc(const float* y_taps, const float* bias, float* out, double* gn_partials, int N, int H, int W,
+                                 int C, int G, void* stream);
 int gdrnpp_conv3x3_gnstats_partials(int H, int W);
 int gdrnpp_conv3x3_f32_split_gnstats(const float* x_nhwc, const void* W_packed, const float* bias, float* y_nhwc,
                                      double* gn_partials, int n_img, int H, int W, int Cin, int Cout, int groups,
