@@ -5,14 +5,17 @@ and eval_calc_scores.py:180-276), with the per-pair NumPy arithmetic replaced by
     reference, per error type:   a process per type, per (estimate, ground truth) pair a NumPy pass over the model per symmetry
     here:                        pair every estimate with the ground truths of its object in its image once, then ONE
                                  ``hip_lib.bop_errors`` call (mssd, mspd) and ONE ``hip_lib.pose_errors`` call per ADD / ADI flavour
-                                 (ad, add, adi, re, te, rete, proj) for all pairs; matching and recall stay host code
+                                 (ad, add, adi, re, te, rete, proj) and ONE ``hip_lib.sym_errors`` call (reS, teS, projS: the minima over
+                                 the object's symmetry transformations, csrc/sym_error.hip) for all pairs; matching and recall stay host code
     reference, vsd:              per pair two GL renders and half a dozen full-image NumPy passes
     here, vsd:                   the pairs whose bounding spheres' projections overlap, grouped by image, in ONE ``hip_lib.vsd_errors``
                                  call per chunk of depth images: a tiled render-and-compare kernel (csrc/vsd_error.hip)
 
 VSD needs the split's depth images and the eval models' faces: a ``BopGT`` built with ``depth=`` (``from_bop_dir(with_depth=True)``).
-Without them ``vsd`` raises NotImplementedError, as ``cus``, the ``*S``, ``ABS*`` and ``AUC*`` types always do.  With mspd, mssd and vsd
-all computed the result holds ``bop19_average_recall``, the number a BOP submission is ranked by.  Units are those of a BOP results file:
+Without them ``vsd`` raises NotImplementedError, as ``cus``, ``reteS`` and the ``ABS*`` and ``AUC*`` types always do: the absolute-threshold and
+area-under-curve family of ADD(-S) is deliberately left out as a whole (serving half of it would be worse than none).  ``reS``, ``teS`` and
+``projS`` are computed, so the reference's own config line ``VAL.ERROR_TYPES = "mspd,mssd,vsd,ad,reS,teS"`` is scored as it stands.  With
+mspd, mssd and vsd all computed the result holds ``bop19_average_recall``, the number a BOP submission is ranked by.  Units are those of a BOP results file:
 translations, model vertices and depth in millimetres."""
 from __future__ import annotations
 
@@ -48,7 +51,13 @@ VSD_DELTAS = {"hb": 15, "hbs": 15, "icbin": 15, "icmi": 15, "itodd": 5, "lm": 15
               "ycbv": 15, "hope": 15}
 VSD_NORMALIZED_BY_DIAMETER = True
 VSD_IMAGE_BYTES = 256 << 20         # depth images uploaded per ``hip_lib.vsd_errors`` call
-KNOWN_NOT_IMPLEMENTED = ("vsd", "cus", "reS", "teS", "reteS", "projS", "ABSad", "ABSadd", "ABSadi", "AUCad", "AUCadd", "AUCadi")
+# the symmetry-aware types (eval_pose_results_more.py:136-155; deg, cm, px): kept beside CORRECT_THS, not in it, as the VSD thresholds are
+SYM_CORRECT_THS = {
+    "reS": [[th] for th in [2, 5, 10]],
+    "teS": [[th] for th in [2, 5, 10]],
+    "projS": [[th] for th in [2, 5, 10]],
+}
+KNOWN_NOT_IMPLEMENTED = ("vsd", "cus", "reteS", "ABSad", "ABSadd", "ABSadi", "AUCad", "AUCadd", "AUCadi")
 NORMALIZED_BY_DIAMETER = ("ad", "add", "adi", "mssd")      # eval_calc_scores.py:70-72
 NORMALIZED_BY_IM_WIDTH = ("mspd",)
 
@@ -177,7 +186,7 @@ def _check_types(error_types, gt=None):
             if gt is None or not gt.has_depth or gt.faces is None:
                 raise NotImplementedError("bop19_scores: error type 'vsd' is not computed here without the split's depth images and the eval "
                                           "models' faces: build the BopGT with depth= and faces= (BopGT.from_bop_dir(..., with_depth=True))")
-        elif t not in CORRECT_THS:
+        elif t not in CORRECT_THS and t not in SYM_CORRECT_THS:
             raise NotImplementedError(f"bop19_scores: error type {t!r} is not computed here"
                                       + ("" if t in KNOWN_NOT_IMPLEMENTED else " (and unknown to the BOP toolkit)"))
 
@@ -249,14 +258,22 @@ def calc_errors(records, gt: BopGT, targets, models_info, meshes, error_types, n
             return full
 
         everything, near = np.arange(P), np.nonzero(overlap)[0]
+        if any(t in error_types for t in ("mssd", "mspd", *SYM_CORRECT_THS)):
+            syms = [misc.get_symmetry_transformations(models_info[o], MAX_SYM_DISC_STEP) for o in ids]
+            sym_R, sym_t, sym_off = misc.flatten_symmetry_transformations(syms)
+            sym_R, sym_t = torch.from_numpy(sym_R).to(dev), torch.from_numpy(sym_t).to(dev)
         if "mssd" in error_types or "mspd" in error_types:
             sel = everything if "mspd" in error_types else near
             if len(sel):
-                syms = [misc.get_symmetry_transformations(models_info[o], MAX_SYM_DISC_STEP) for o in ids]
-                sym_R, sym_t, sym_off = misc.flatten_symmetry_transformations(syms)
-                out = hip_lib.bop_errors(meshes, *dev_args(sel), torch.from_numpy(sym_R).to(dev), torch.from_numpy(sym_t).to(dev), sym_off)
+                out = hip_lib.bop_errors(meshes, *dev_args(sel), sym_R, sym_t, sym_off)
                 full = scatter(sel, out, 2)
                 values["mssd"], values["mspd"] = np.where(overlap, full[:, 0], np.inf), full[:, 1]
+        if any(t in error_types for t in SYM_CORRECT_THS):      # eval_calc_errors.py:545-596: every pair, no sphere-overlap cut
+            args = dev_args(everything)
+            if "projS" not in error_types:
+                args[5] = None                                  # no K: nothing runs over the model points
+            full = hip_lib.sym_errors(meshes, *args, sym_R, sym_t, sym_off).cpu().numpy()
+            values["reS"], values["teS"], values["projS"] = full[:, 0], full[:, 1] / 10, full[:, 2]          # teS: mm -> cm
         plain = [t for t in error_types if t in ("add", "re", "te", "rete", "proj")]
         flavours = []                                          # (the types served, pairs, ADI flags)
         if plain:
@@ -380,7 +397,7 @@ def scores_from_errors(errors, records, gt: BopGT, targets, models_info, error_t
             recalls_of[t], obj_recalls_of[t] = recalls, obj_recalls
             final["bop19_average_recall_vsd"] = float(np.mean([r for per_tau in recalls for r in per_tau]))
             continue
-        for th in CORRECT_THS[t]:
+        for th in (CORRECT_THS[t] if t in CORRECT_THS else SYM_CORRECT_THS[t]):
             _, s = score_errors(errors[t], gt, targets, models_info, t, th, n_top, im_width)
             recalls.append(s["recall"])
             obj_recalls.append(s["obj_recalls"])
@@ -389,7 +406,7 @@ def scores_from_errors(errors, records, gt: BopGT, targets, models_info, error_t
     if all(t in error_types for t in ("mspd", "mssd", "vsd")):          # eval_pose_results_more.py:371-378
         final["bop19_average_recall"] = float(np.mean([final[f"bop19_average_recall_{t}"] for t in ("mspd", "mssd", "vsd")]))
     final["bop19_average_time_per_image"] = average_time_per_image(records)
-    final["recalls"] = recalls_of                     # per type: the recall at each threshold of CORRECT_THS; vsd: per tau, per threshold
+    final["recalls"] = recalls_of                     # per type: the recall at each threshold of CORRECT_THS / SYM_CORRECT_THS; vsd: per tau, per threshold
     final["obj_recalls"] = obj_recalls_of             # per type: {obj_id: recall} at each threshold; vsd: nested per tau likewise
     return final
 

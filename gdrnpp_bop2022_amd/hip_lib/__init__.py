@@ -28,7 +28,7 @@ from .net import (POINT_PNP_TILE, ROT_DIMS, ROT_MODES, T_MODES, bias_act_nhwc_, 
 from .pose import (MeshSet, bop_errors, decode_correspondences, depth_refine, epnp_batched, epnp_ransac, flow_forward, fps, nnd_backward,  # noqa: F401
                    nnd_forward, pack_pose_records, paste_masks_rle, pnp_iter_from_correspondences, pose_from_pred,
                    pose_errors, pose_from_pred_centroid_z, refine_kernel_name, refine_to_records, render_depth, set_refine_event_sink,
-                   uncertainty_pnp_batched, vsd_counts, vsd_errors, zoom_K)
+                   sym_errors, uncertainty_pnp_batched, vsd_counts, vsd_errors, zoom_K)
 from .range_words import (X3_NONFINITE, X3_SLOTS, X3_SMALL_ROWS, range_words_of, split2_nonfinite, split2_range_words,  # noqa: F401
                           x3_flag_ptr, x3_flag_scope, x3_flags, x3_launch_count)
 from .roi import ROI_TABLE_COLUMNS, crop_resize_roi, roi_align, roi_pool, roi_table, rois_from_dets  # noqa: F401

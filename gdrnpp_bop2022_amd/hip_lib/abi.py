@@ -74,6 +74,8 @@ SIGNATURES = {
     "gdrnpp_pose_errors": (c_int, [POINTER(gdrnpp_meshes), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, _P, c_size_t, _P]),
     "gdrnpp_bop_errors_workspace_bytes": (c_size_t, [POINTER(gdrnpp_meshes), _P, c_int]),
     "gdrnpp_bop_errors": (c_int, [POINTER(gdrnpp_meshes), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, _P, c_size_t, _P]),
+    "gdrnpp_sym_errors_workspace_bytes": (c_size_t, [POINTER(gdrnpp_meshes), _P, c_int]),
+    "gdrnpp_sym_errors": (c_int, [POINTER(gdrnpp_meshes), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, _P, c_size_t, _P]),
     "gdrnpp_vsd_counts_workspace_bytes": (c_size_t, [POINTER(gdrnpp_meshes), c_int]),
     "gdrnpp_vsd_counts": (c_int, [POINTER(gdrnpp_meshes), _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, _P, c_int, c_float,
                                   c_double, c_double, _P, c_int, _P, c_size_t, _P]),

@@ -249,6 +249,38 @@ def pose_errors(meshes: MeshSet, obj, R_est, t_est, R_gt, t_gt, K, sym_rots=None
     return out
 
 
+def _pair_sym_args(what: str, meshes: MeshSet, obj, R_est, t_est, R_gt, t_gt, K, sym_R, sym_t, sym_off, k_optional: bool = False):
+    """The argument checks ``bop_errors`` and ``sym_errors`` share -> (obj pointer, [R_est, t_est, R_gt, t_gt, K, sym_R, sym_t pointers],
+    sym_off as a contiguous host i32 array: keep it alive across the launch).  ``K`` may be None only where ``k_optional``."""
+    import numpy as np
+
+    b = int(obj.shape[0])
+    op = dev_ptr(obj, torch.int32, "obj")
+    lo, hi = torch.aminmax(obj)
+    if int(lo) < 0 or int(hi) >= meshes.n_obj:
+        raise RuntimeError(f"{what}: obj must lie in [0, {meshes.n_obj}), got [{int(lo)}, {int(hi)}]")
+    ptrs = []
+    for t, name, cols in ((R_est, "R_est", 9), (t_est, "t_est", 3), (R_gt, "R_gt", 9), (t_gt, "t_gt", 3), (K, "K", 9)):
+        if t is None and name == "K" and k_optional:
+            ptrs.append(None)
+            continue
+        ptrs.append(dev_ptr(t, torch.float64, name))
+        if t.numel() != b * cols:
+            raise RuntimeError(f"{what}: {name} must hold {b} x {cols} values, got {tuple(t.shape)}")
+    off = np.ascontiguousarray(sym_off.cpu().numpy() if isinstance(sym_off, torch.Tensor) else sym_off).reshape(-1)
+    if off.dtype.kind not in "iu" or off.size != meshes.n_obj + 1:
+        raise RuntimeError(f"{what}: sym_off must hold n_obj + 1 = {meshes.n_obj + 1} integer offsets")
+    off = off.astype(np.int32)
+    n_sym = int(off[-1])
+    if off[0] != 0 or (np.diff(off) <= 0).any():
+        raise RuntimeError(f"{what}: sym_off must start at 0 and give every object at least one transformation (the identity)")
+    for t, name, cols in ((sym_R, "sym_R", 9), (sym_t, "sym_t", 3)):
+        ptrs.append(dev_ptr(t, torch.float64, name))
+        if t.numel() != n_sym * cols:
+            raise RuntimeError(f"{what}: {name} must hold sym_off[-1] x {cols} = {n_sym} x {cols} values, got {tuple(t.shape)}")
+    return op, ptrs, off
+
+
 def bop_errors(meshes: MeshSet, obj, R_est, t_est, R_gt, t_gt, K, sym_R, sym_t, sym_off) -> torch.Tensor:
     """``gdrnpp_bop_errors``: BOP19 MSSD and MSPD of b (estimate, ground truth) pairs -> f64[b,2] = mssd, mspd (pixels).
     obj i32[b]; R_est, R_gt, K f64[b,3,3|9]; t_est, t_gt f64[b,3], in the unit of the meshes' vertices (millimetres for a BOP results
@@ -256,37 +288,35 @@ def bop_errors(meshes: MeshSet, obj, R_est, t_est, R_gt, t_gt, K, sym_R, sym_t, 
     (``lib.pysixd.misc.get_symmetry_transformations``), object after object; sym_off: n_obj + 1 offsets into them (a sequence, an
     array or a tensor; it is read on the host, where it sizes the launch).  The other arguments are device tensors; ``obj`` is
     checked against the mesh set here (one read-back of two integers)."""
-    import numpy as np
-
     dev = meshes.verts.device
     b = int(obj.shape[0])
     out = torch.empty((b, 2), dtype=torch.float64, device=dev)
     if b == 0:
         return out
-    op = dev_ptr(obj, torch.int32, "obj")
-    lo, hi = torch.aminmax(obj)
-    if int(lo) < 0 or int(hi) >= meshes.n_obj:
-        raise RuntimeError(f"bop_errors: obj must lie in [0, {meshes.n_obj}), got [{int(lo)}, {int(hi)}]")
-    ptrs = []
-    for t, name, cols in ((R_est, "R_est", 9), (t_est, "t_est", 3), (R_gt, "R_gt", 9), (t_gt, "t_gt", 3), (K, "K", 9)):
-        ptrs.append(dev_ptr(t, torch.float64, name))
-        if t.numel() != b * cols:
-            raise RuntimeError(f"bop_errors: {name} must hold {b} x {cols} values, got {tuple(t.shape)}")
-    off = np.ascontiguousarray(sym_off.cpu().numpy() if isinstance(sym_off, torch.Tensor) else sym_off).reshape(-1)
-    if off.dtype.kind not in "iu" or off.size != meshes.n_obj + 1:
-        raise RuntimeError(f"bop_errors: sym_off must hold n_obj + 1 = {meshes.n_obj + 1} integer offsets")
-    off = off.astype(np.int32)
-    n_sym = int(off[-1])
-    if off[0] != 0 or (np.diff(off) <= 0).any():
-        raise RuntimeError("bop_errors: sym_off must start at 0 and give every object at least one transformation (the identity)")
-    for t, name, cols in ((sym_R, "sym_R", 9), (sym_t, "sym_t", 3)):
-        ptrs.append(dev_ptr(t, torch.float64, name))
-        if t.numel() != n_sym * cols:
-            raise RuntimeError(f"bop_errors: {name} must hold sym_off[-1] x {cols} = {n_sym} x {cols} values, got {tuple(t.shape)}")
+    op, ptrs, off = _pair_sym_args("bop_errors", meshes, obj, R_est, t_est, R_gt, t_gt, K, sym_R, sym_t, sym_off)
     offp = off.ctypes.data
     nbytes = load().gdrnpp_bop_errors_workspace_bytes(meshes.c, offp, b)
     ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
     launch("gdrnpp_bop_errors", meshes.c, op, *ptrs, offp, out.data_ptr(), b, ws.data_ptr(), nbytes)
+    return out
+
+
+def sym_errors(meshes: MeshSet, obj, R_est, t_est, R_gt, t_gt, K, sym_R, sym_t, sym_off) -> torch.Tensor:
+    """``gdrnpp_sym_errors``: the symmetry-aware reS, teS and projS of b (estimate, ground truth) pairs -> f64[b,3] = reS (degrees), teS
+    (the unit of the translations), projS (pixels): each the minimum over the object's symmetry transformations of re, te and the mean
+    projected distance of the model points.  Arguments and checks as ``bop_errors``, except that ``K`` may be None: projS is then not
+    computed (the third column is NaN), nothing runs over the model points and the call costs O(symmetries) per pair; the first two
+    columns are the same bits either way."""
+    dev = meshes.verts.device
+    b = int(obj.shape[0])
+    out = torch.empty((b, 3), dtype=torch.float64, device=dev)
+    if b == 0:
+        return out
+    op, ptrs, off = _pair_sym_args("sym_errors", meshes, obj, R_est, t_est, R_gt, t_gt, K, sym_R, sym_t, sym_off, k_optional=True)
+    offp = off.ctypes.data
+    nbytes = load().gdrnpp_sym_errors_workspace_bytes(meshes.c, offp, b)
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    launch("gdrnpp_sym_errors", meshes.c, op, *ptrs, offp, out.data_ptr(), b, ws.data_ptr(), nbytes)
     return out
 
 

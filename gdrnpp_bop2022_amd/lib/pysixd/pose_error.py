@@ -1,7 +1,8 @@
 """``add / adi / re / te / arp_2d`` with the signatures of the reference's lib/pysixd/pose_error.py (:256-296, :359-374, :406-417,
 :440-445): NumPy arrays in, a float out.  Each call runs ``gdrnpp_pose_errors`` (csrc/pose_error.hip) with b = 1 on the current
-device; ``mssd / mspd`` (:131-179) run ``gdrnpp_bop_errors`` (csrc/bop_error.hip) the same way, the entry point
-``gdrn_modeling.bop_eval.bop19_scores`` runs once for a whole results file — the entry point ``GDRN_EvaluatorCustom`` runs once for a whole dataset; use ``hip_lib.pose_errors`` directly for more
+device; ``mssd / mspd`` (:131-179) run ``gdrnpp_bop_errors`` (csrc/bop_error.hip) the same way, and ``re_sym / te_sym / arp_2d_sym /
+proj_sym`` (:377-396, :420-437, :183-217) ``gdrnpp_sym_errors`` (csrc/sym_error.hip), the entry points
+``gdrn_modeling.bop_eval.bop19_scores`` runs once each for a whole results file — the entry point ``GDRN_EvaluatorCustom`` runs once for a whole dataset; use ``hip_lib.pose_errors`` directly for more
 than a handful of poses.  ``pts`` is taken as float32 (what a ``hip_lib.MeshSet`` holds); there is no CPU fallback.
 ``vsd`` (:22-128) runs ``gdrnpp_vsd_counts`` (csrc/vsd_error.hip) with b = 1; its ``renderer`` is a ``VsdRenderer``: the resident meshes
 (with faces) that the kernel renders, in place of the toolkit's GL renderer."""
@@ -62,7 +63,8 @@ def arp_2d(R_est, t_est, R_gt, t_gt, pts, K):
     return float(_errors(R_est, t_est, R_gt, t_gt, pts, K)[3])
 
 
-def _bop_errors(R_est, t_est, R_gt, t_gt, K, pts, syms) -> np.ndarray:
+def _sym_pair(fn, R_est, t_est, R_gt, t_gt, K, pts, syms) -> np.ndarray:
+    """One pair through ``hip_lib.bop_errors`` / ``hip_lib.sym_errors``: a one-object mesh set, ``syms`` flattened, b = 1."""
     if not torch.cuda.is_available():
         raise RuntimeError("pysixd.pose_error: needs a HIP device (no CPU fallback)")
     from ... import hip_lib
@@ -76,9 +78,13 @@ def _bop_errors(R_est, t_est, R_gt, t_gt, K, pts, syms) -> np.ndarray:
     def T(a, n):
         return torch.from_numpy(np.ascontiguousarray(np.asarray(a, np.float64).reshape(-1, n))).to(dev)
 
-    out = hip_lib.bop_errors(mesh, torch.zeros(1, dtype=torch.int32, device=dev), T(R_est, 9), T(t_est, 3), T(R_gt, 9), T(t_gt, 3),
-                             T(K, 9), T(sym_R, 9), T(sym_t, 3), sym_off)
+    out = getattr(hip_lib, fn)(mesh, torch.zeros(1, dtype=torch.int32, device=dev), T(R_est, 9), T(t_est, 3), T(R_gt, 9), T(t_gt, 3),
+                               None if K is None else T(K, 9), T(sym_R, 9), T(sym_t, 3), sym_off)
     return out.cpu().numpy()[0]
+
+
+def _bop_errors(R_est, t_est, R_gt, t_gt, K, pts, syms) -> np.ndarray:
+    return _sym_pair("bop_errors", R_est, t_est, R_gt, t_gt, K, pts, syms)
 
 
 def mssd(R_est, t_est, R_gt, t_gt, pts, syms):
@@ -90,6 +96,30 @@ def mssd(R_est, t_est, R_gt, t_gt, pts, syms):
 def mspd(R_est, t_est, R_gt, t_gt, K, pts, syms):
     """Maximum Symmetry-Aware Projection Distance: as ``mssd``, between the projections by ``K``, in pixels."""
     return float(_bop_errors(R_est, t_est, R_gt, t_gt, K, pts, syms)[1])
+
+
+def re_sym(R_est, R_gt, syms):
+    """Rotational error in degrees against the closest of the symmetric ground-truth rotations ``R_gt . sym["R"]``."""
+    R_est, R_gt = np.asarray(R_est), np.asarray(R_gt)
+    assert R_est.shape == R_gt.shape == (3, 3)
+    return float(_sym_pair("sym_errors", R_est, _ZERO, R_gt, _ZERO, None, _ONE_POINT, syms)[0])
+
+
+def te_sym(t_est, t_gt, R_gt, syms):
+    """Translational error against the closest of the symmetric ground-truth translations ``R_gt . sym["t"] + t_gt``."""
+    t_est, t_gt = np.asarray(t_est).flatten(), np.asarray(t_gt).flatten()
+    assert t_est.size == t_gt.size == 3
+    return float(_sym_pair("sym_errors", _EYE, t_est, R_gt, t_gt, None, _ONE_POINT, syms)[1])
+
+
+def arp_2d_sym(R_est, t_est, R_gt, t_gt, pts, K, syms):
+    """Average re-projection error in pixels, the smallest over the symmetry transformations (the same as ``proj_sym``)."""
+    return float(_sym_pair("sym_errors", R_est, t_est, R_gt, t_gt, K, pts, syms)[2])
+
+
+def proj_sym(R_est, t_est, R_gt, t_gt, K, pts, syms):
+    """Average distance of the projections of the model points in pixels (Brachmann et al., CVPR'16), the smallest over ``syms``."""
+    return float(_sym_pair("sym_errors", R_est, t_est, R_gt, t_gt, K, pts, syms)[2])
 
 
 class VsdRenderer:

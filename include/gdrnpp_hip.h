@@ -359,6 +359,23 @@ int gdrnpp_bop_errors(const gdrnpp_meshes* models, const int* obj, const double*
                       const double* R_gt, const double* t_gt, const double* K, const double* sym_R, const double* sym_t,
                       const int* sym_off, double* out, int b, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- symmetry-aware reS / teS / projS — lib/pysixd/pose_error.py:377-396 (re_sym), :420-437 (te_sym), :183-217 (arp_2d_sym =
+ * proj_sym), the errors eval_calc_errors.py:545-596 computes for every pair: each the minimum over the object's symmetry
+ * transformations, of the rotation error (degrees), of the translation error, and of the MEAN over the model points of the projected
+ * distance (pixels; z is not clamped) --------------------------------------------------------------------------------------------
+ * Arguments as gdrnpp_bop_errors (sym_off is a HOST array, starts at 0, no empty range), except that K may be NULL: projS is then
+ * not wanted, no work over the model points is launched and the call is O(symmetries) per pair.  out f64[b,3] = reS, teS (unit of
+ * t), projS (NaN without K, and for an empty model); an obj outside [0, n_obj) gives a NaN row.  Columns 0 and 1 do not depend on
+ * whether K was given.  fp64 throughout; every sum has a fixed order and there are no floating-point atomics: two calls give
+ * bit-equal output, and a pair's result does not depend on the other pairs of the call.  workspace:
+ * gdrnpp_sym_errors_workspace_bytes(models, sym_off, b) = round_up(4 (n_obj + 1), 16) + 24 * b * ceil(max symmetries of an object
+ * / 8) bytes (0 for arguments that gdrnpp_sym_errors refuses), with or without K.  Argument errors return GDRNPP_EINVAL /
+ * GDRNPP_ELIMIT and launch nothing. */
+size_t gdrnpp_sym_errors_workspace_bytes(const gdrnpp_meshes* models, const int* sym_off, int b);
+int gdrnpp_sym_errors(const gdrnpp_meshes* models, const int* obj, const double* R_est, const double* t_est,
+                      const double* R_gt, const double* t_gt, const double* K, const double* sym_R, const double* sym_t,
+                      const int* sym_off, double* out, int b, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- BOP19 VSD — lib/pysixd/pose_error.py:22-128 (cost_type "step") with visibility.py:9-74 ("bop19") and misc.py:604-647, the error
  * eval_calc_errors.py:376-395 computes per (estimate, ground truth) pair from two full-image depth renders and the test depth image.
  * Device pointers: obj i32[b] class index into `models` (which need faces; used as gdrnpp_render_depth uses them); im_idx i32[b]
