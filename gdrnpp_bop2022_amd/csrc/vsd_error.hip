@@ -44,21 +44,15 @@
 // the call reaches 0.26 / 0.05 of those bounds at 512 pairs: one wave per SIMD per workgroup (101 VGPRs) does not hide the dependent loads
 // of the face walk and of the compare loop.
 #include "common.hpp"
-#include "raster.hpp"
+#include "tile_raster.hpp"
 #include <climits>
 
 namespace {
 
 using namespace gdrnpp;
+using namespace gdrnpp::tiles;   // tile_raster.hpp: kThreads, kTile, kVtx ..., the staging and the face walk shared with gt_visib.hip
 
-constexpr int kThreads = 256;   // 4 waves
-constexpr int kWaves = kThreads / 64;
-constexpr int kTile = 64;       // tile edge in pixels; a thread's column inside the tile is tid & 63
-constexpr int kTilePix = kTile * kTile;
 constexpr int kMaxTau = 16;
-constexpr int kVtx = 5;         // staged doubles per vertex: h0, h1, h2, u, v
-constexpr int kLargeArea = 32;  // candidate centres above which a face is rasterised by its whole wave
-constexpr unsigned kInfBits = 0x7f800000u;
 
 struct VsdArgs {
   const float* verts; const int* faces; const int* vert_off; const int* face_off; int n_obj, max_verts;
@@ -80,12 +74,6 @@ __device__ __forceinline__ bool pair_ok(const VsdArgs& a, size_t pair, int& o) {
   if (im < 0 || im >= a.n_im) return false;
   const int nv = a.vert_off[o + 1] - a.vert_off[o], nf = a.face_off[o + 1] - a.face_off[o];
   return nv > 0 && nv <= a.max_verts && nf > 0;
-}
-
-__device__ __forceinline__ void render_K(const double* __restrict__ Kp, double* K) {
-  K[0] = Kp[0]; K[1] = 0.0; K[2] = Kp[2];
-  K[3] = 0.0; K[4] = Kp[4]; K[5] = Kp[5];
-  K[6] = 0.0; K[7] = 0.0; K[8] = 1.0;
 }
 
 __global__ __launch_bounds__(kThreads) void vsd_project(const VsdArgs a) {
@@ -112,50 +100,7 @@ __global__ __launch_bounds__(kThreads) void vsd_project(const VsdArgs a) {
   for (int k = 0; k < 3; ++k) t[k] = tp[k];
   double* hv = a.hv + ((2 * pair + pose) * (size_t)a.max_verts) * kVtx;
   const float* mv = a.verts + 3 * (size_t)v0;
-  // projections of the vertices at or beyond z_near, and the z range of all of them
-  double umin = 1e300, umax = -1e300, vmin = 1e300, vmax = -1e300, zmin = 1e300, zmax = -1e300;
-  for (int v = tid; v < nv; v += kThreads) {
-    double h[3];
-    project_vertex(mv + 3 * (size_t)v, K, R, t, h);
-    const double pu = h[0] / h[2], pv = h[1] / h[2];
-    double* dst = hv + (size_t)v * kVtx;
-    dst[0] = h[0]; dst[1] = h[1]; dst[2] = h[2]; dst[3] = pu; dst[4] = pv;
-    zmin = fmin(zmin, h[2]); zmax = fmax(zmax, h[2]);
-    if (h[2] >= a.z_near) { umin = fmin(umin, pu); umax = fmax(umax, pu); vmin = fmin(vmin, pv); vmax = fmax(vmax, pv); }
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    umin = fmin(umin, __shfl_xor(umin, off, 64)); umax = fmax(umax, __shfl_xor(umax, off, 64));
-    vmin = fmin(vmin, __shfl_xor(vmin, off, 64)); vmax = fmax(vmax, __shfl_xor(vmax, off, 64));
-    zmin = fmin(zmin, __shfl_xor(zmin, off, 64)); zmax = fmax(zmax, __shfl_xor(zmax, off, 64));
-  }
-  if ((tid & 63) == 0) {
-    double* r = s_red[tid >> 6];
-    r[0] = umin; r[1] = umax; r[2] = vmin; r[3] = vmax; r[4] = zmin; r[5] = zmax;
-  }
-  __syncthreads();
-  if (tid == 0) {
-    for (int w = 1; w < kWaves; ++w) {
-      umin = fmin(umin, s_red[w][0]); umax = fmax(umax, s_red[w][1]); vmin = fmin(vmin, s_red[w][2]);
-      vmax = fmax(vmax, s_red[w][3]); zmin = fmin(zmin, s_red[w][4]); zmax = fmax(zmax, s_red[w][5]);
-    }
-    int b0 = 1, b1 = 0, b2 = 1, b3 = 0;
-    if (!(zmax < a.z_near || zmin > a.z_far || !(umin <= umax) || !(vmin <= vmax))) {
-      if (zmin < a.z_near) {  // a face may cross the near plane: its clipped outline is not bounded by the vertices in front
-        b0 = 0; b1 = a.W - 1; b2 = 0; b3 = a.H - 1;
-      } else {                // every covered centre lies in a face's box (triangle_bbox), every face's box in this one
-        b0 = clampi(ceil(umin - 0.5 - 1e-6), 0, a.W); b1 = clampi(floor(umax - 0.5 + 1e-6), -1, a.W - 1);
-        b2 = clampi(ceil(vmin - 0.5 - 1e-6), 0, a.H); b3 = clampi(floor(vmax - 0.5 + 1e-6), -1, a.H - 1);
-      }
-    }
-    box[0] = b0; box[1] = b1; box[2] = b2; box[3] = b3;
-  }
-}
-
-__device__ __forceinline__ int wave_sum(int v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
+  stage_vertices_and_box(mv, nv, K, R, t, hv, a.z_near, a.z_far, a.W, a.H, s_red, box);
 }
 
 __global__ __launch_bounds__(kThreads) void vsd_tiles(const VsdArgs a, int tiles_x, int ntiles) {
@@ -195,63 +140,7 @@ __global__ __launch_bounds__(kThreads) void vsd_tiles(const VsdArgs a, int tiles
     const int ci0 = c[pose][0], ci1 = c[pose][1], cj0 = c[pose][2], cj1 = c[pose][3];
     const double* hv = a.hv + ((2 * pair + pose) * (size_t)a.max_verts) * kVtx;
     unsigned* z = zb[pose];
-    for (int f0 = 0; f0 < nfaces; f0 += kThreads) {
-      const int f = f0 + tid;
-      bool large = false;
-      TriSetup s;
-#pragma unroll
-      for (int k = 0; k < 3; ++k) s.e0[k] = s.e1[k] = s.e2[k] = 0.0;
-      s.D = 0.0; s.i_lo = 1; s.i_hi = 0; s.j_lo = 1; s.j_hi = 0;
-      if (f < nfaces) {
-        const int i0 = mfaces[3 * f], i1 = mfaces[3 * f + 1], i2 = mfaces[3 * f + 2];
-        if ((unsigned)i0 < (unsigned)nv && (unsigned)i1 < (unsigned)nv && (unsigned)i2 < (unsigned)nv) {
-          const double* p0 = hv + (size_t)i0 * kVtx;
-          const double* p1 = hv + (size_t)i1 * kVtx;
-          const double* p2 = hv + (size_t)i2 * kVtx;
-          const double uv0[2] = {p0[3], p0[4]}, uv1[2] = {p1[3], p1[4]}, uv2[2] = {p2[3], p2[4]};
-          const double z0 = p0[2], z1 = p1[2], z2 = p2[2];
-          // a face wholly in front whose projected box (widened as triangle_bbox widens it) holds no centre of tile & box has no
-          // candidate here; the comparisons are written so that a NaN passes on to the exact test
-          bool cand = true;
-          if (fmin(z0, fmin(z1, z2)) >= zn) {
-            const double ulo = fmin(uv0[0], fmin(uv1[0], uv2[0])), uhi = fmax(uv0[0], fmax(uv1[0], uv2[0]));
-            const double vlo = fmin(uv0[1], fmin(uv1[1], uv2[1])), vhi = fmax(uv0[1], fmax(uv1[1], uv2[1]));
-            cand = !(uhi + 1e-6 < (double)ci0 + 0.5 || ulo - 1e-6 > (double)ci1 + 0.5 || vhi + 1e-6 < (double)cj0 + 0.5 ||
-                     vlo - 1e-6 > (double)cj1 + 0.5);
-          }
-          if (cand) {
-            const double h0[3] = {p0[0], p0[1], z0}, h1[3] = {p1[0], p1[1], z1}, h2[3] = {p2[0], p2[1], z2};
-            if (triangle_bbox(h0, h1, h2, uv0, uv1, uv2, W, H, zn, zf, s)) {
-              s.i_lo = max(s.i_lo, ci0); s.i_hi = min(s.i_hi, ci1); s.j_lo = max(s.j_lo, cj0); s.j_hi = min(s.j_hi, cj1);
-              if (s.i_lo <= s.i_hi && s.j_lo <= s.j_hi && triangle_edges(h0, h1, h2, s)) {
-                if ((s.i_hi - s.i_lo + 1) * (s.j_hi - s.j_lo + 1) > kLargeArea) large = true;
-                else
-                  for (int j = s.j_lo; j <= s.j_hi; ++j)
-                    for (int i = s.i_lo; i <= s.i_hi; ++i) {
-                      double Z;
-                      if (sample_triangle(s, i, j, zn, zf, Z, nullptr))
-                        atomicMin(&z[(j - ty0) * kTile + (i - tx0)], __float_as_uint((float)Z));
-                    }
-              }
-            }
-          }
-        }
-      }
-      // faces that cover much of the tile: all 64 lanes of the wave rasterise one (the trip count f0 is workgroup-uniform)
-      unsigned long long bal = __ballot(large);
-      while (bal) {
-        const int src = __ffsll((long long)bal) - 1;
-        bal &= bal - 1;
-        const TriSetup s2 = shfl_setup(s, src);
-        const int bw = s2.i_hi - s2.i_lo + 1, bh = s2.j_hi - s2.j_lo + 1;  // inside the tile: bw * bh <= 4096
-        for (int p = lane; p < bw * bh; p += 64) {
-          const int j = s2.j_lo + p / bw, i = s2.i_lo + p % bw;
-          double Z;
-          if (sample_triangle(s2, i, j, zn, zf, Z, nullptr))
-            atomicMin(&z[(j - ty0) * kTile + (i - tx0)], __float_as_uint((float)Z));
-        }
-      }
-    }
+    raster_faces_tile(hv, mfaces, nfaces, nv, ci0, ci1, cj0, cj1, tx0, ty0, W, H, zn, zf, z);
   }
   __syncthreads();
 

@@ -125,12 +125,19 @@ class BopGT:
     @classmethod
     def from_bop_dir(cls, dataset_dir, split="test", targets_filename="test_targets_bop19.json", models_dir="models_eval",
                      symmetric_obj_ids=(), im_width=640, obj_ids=None, scene_ids=None, with_depth=False, im_size=None, dataset=None,
-                     vsd_delta=None):
+                     vsd_delta=None, gt_info="file", device="cuda"):
         """The standard BOP layout: ``<dataset_dir>/<models_dir>/models_info.json`` + ``obj_{id:06d}.ply``,
         ``<dataset_dir>/<targets_filename>`` and ``<dataset_dir>/<split>/{scene_id:06d}/scene_gt.json | scene_gt_info.json |
         scene_camera.json`` for the scenes the targets name.  with_depth: also the faces of the eval models and, for the images the targets
         name, the paths ``<split>/{scene_id:06d}/depth/{im_id:06d}.png`` (read when VSD asks for them); dataset defaults to the directory's
-        name when ``VSD_DELTAS`` knows it."""
+        name when ``VSD_DELTAS`` knows it.  gt_info: where ``scene_gt_info`` comes from.  "file" reads ``scene_gt_info.json``; "compute" renders
+        every ground truth of the scenes with the models of ``models_dir`` against the depth images ``<split>/{scene_id:06d}/depth/
+        {im_id:06d}.png`` (needed whether or not ``with_depth`` is set; im_size defaults to the first image's) on ``device`` and takes
+        ``bop_gt_info.calc_gt_info``'s records, with the tolerance ``vsd_tolerance()`` would give; "auto" reads the file where it exists
+        and computes where it does not."""
+        if gt_info not in ("file", "compute", "auto"):
+            raise ValueError(f"BopGT.from_bop_dir: gt_info must be 'file', 'compute' or 'auto', got {gt_info!r}")
+
         def load(*parts):
             with open(os.path.join(dataset_dir, *parts)) as f:
                 return json.load(f)
@@ -140,16 +147,36 @@ class BopGT:
         plys = {o: inout.load_ply(os.path.join(dataset_dir, models_dir, f"obj_{o:06d}.ply")) for o in models_info}
         vertices = {o: m["pts"] for o, m in plys.items()}
         per_scene = {name: {} for name in ("scene_gt", "scene_gt_info", "scene_camera")}
+        computed = []
         for s in sorted({int(t["scene_id"]) for t in targets}):
+            have = gt_info == "file" or (gt_info == "auto" and os.path.exists(os.path.join(dataset_dir, split, f"{s:06d}", "scene_gt_info.json")))
             for name in per_scene:
+                if name == "scene_gt_info" and not have:
+                    computed.append(s)
+                    continue
                 per_scene[name][s] = load(split, f"{s:06d}", name + ".json")
+        name = os.path.basename(os.path.normpath(str(dataset_dir)))
+        if computed:
+            from . import bop_gt_info
+
+            probe = cls({}, {}, {}, [], models_info, (), {}, im_width, dataset=dataset if dataset is not None else name, vsd_delta=vsd_delta)
+            delta = probe.vsd_tolerance()
+            ids = sorted(models_info)
+            meshes = hip_lib.MeshSet([np.asarray(plys[o]["pts"], np.float32) for o in ids], [np.asarray(plys[o]["faces"], np.int32) for o in ids],
+                                     device=device)
+            for s in computed:
+                paths = {int(i): os.path.join(dataset_dir, split, f"{s:06d}", "depth", f"{int(i):06d}.png") for i in per_scene["scene_gt"][s]}
+                size = im_size
+                if size is None and paths:
+                    size = inout.load_depth(paths[min(paths)]).shape[::-1]
+                per_scene["scene_gt_info"][s] = bop_gt_info.calc_gt_info(per_scene["scene_gt"][s], {int(i): c for i, c in per_scene["scene_camera"][s].items()},
+                                                                         paths, meshes, ids, size, delta)
         extra = {}
         if with_depth:
             depth = {}
             for t in targets:
                 s, i = int(t["scene_id"]), int(t["im_id"])
                 depth.setdefault(s, {})[i] = os.path.join(dataset_dir, split, f"{s:06d}", "depth", f"{i:06d}.png")
-            name = os.path.basename(os.path.normpath(str(dataset_dir)))
             extra = dict(faces={o: m["faces"] for o, m in plys.items()}, depth=depth, im_size=im_size,
                          dataset=dataset if dataset is not None else (name if name in VSD_DELTAS else None), vsd_delta=vsd_delta)
         return cls(per_scene["scene_gt"], per_scene["scene_gt_info"], per_scene["scene_camera"], targets, models_info, symmetric_obj_ids,

@@ -79,6 +79,9 @@ SIGNATURES = {
     "gdrnpp_vsd_counts_workspace_bytes": (c_size_t, [POINTER(gdrnpp_meshes), c_int]),
     "gdrnpp_vsd_counts": (c_int, [POINTER(gdrnpp_meshes), _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, _P, c_int, c_float,
                                   c_double, c_double, _P, c_int, _P, c_size_t, _P]),
+    "gdrnpp_gt_visibility_workspace_bytes": (c_size_t, [POINTER(gdrnpp_meshes), c_int]),
+    "gdrnpp_gt_visibility": (c_int, [POINTER(gdrnpp_meshes), _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_float, c_double,
+                                     c_double, _P, _P, _P, c_int, _P, c_size_t, _P]),
     "gdrnpp_pose_from_pred": (c_int, [_P, c_int, _P, c_int, _P, _P, _P, _P, _P, _P, c_int, c_int, _P]),
     "gdrnpp_debug_refine_profile": (c_int, [_P]),
     "gdrnpp_pack_weight_bf16x3": (c_int, [_P, _P, c_int, c_int, _P]),

@@ -378,6 +378,58 @@ def vsd_errors(meshes: MeshSet, obj, im_idx, R_est, t_est, R_gt, t_gt, K, diamet
     return torch.where(union < 0, torch.full_like(e, float("nan")), e)
 
 
+GT_INFO_COLUMNS = ("px_count_all", "px_count_valid", "px_count_visib", "obj_x_min", "obj_y_min", "obj_x_max", "obj_y_max",
+                   "visib_x_min", "visib_y_min", "visib_x_max", "visib_y_max")
+
+
+def gt_visibility(meshes: MeshSet, obj, im_idx, R, t, K, depth, delta, *, canvas_offset=(0, 0), want_masks: bool = False,
+                  z_near: float = 1.0, z_far: float = 1e6, workspace_budget: int = VSD_WORKSPACE_BUDGET):
+    """``gdrnpp_gt_visibility``: what calc_gt_info.py / calc_gt_masks.py compute for n ground-truth poses -> (info i32[n,11], mask,
+    mask_visib).  info columns are ``GT_INFO_COLUMNS``: the three pixel counts, then the inclusive extents of the whole silhouette and of
+    its visible part in image coordinates (empty: INT_MAX, INT_MAX, INT_MIN, INT_MIN; a row of -1 for a pose whose obj or im_idx is out of
+    range or whose object has no faces).  mask, mask_visib: u8[n,H,W] of 0 / 255 when ``want_masks``, else None.  obj, im_idx i32[n]; R, K
+    f64[n,3,3|9]; t f64[n,3] in the unit of the meshes' vertices (mm); depth f32[n_im,H,W] in mm, 0 = missing: all device tensors.
+    canvas_offset (ox, oy): the render covers (W + 2 ox) x (H + 2 oy) pixels around the image — (W, H) is calc_gt_info.py's canvas, on
+    which px_count_all and the silhouette's extents include the truncated part.  A launch stages 40 bytes per vertex of the largest model
+    per pose, so the poses run in chunks that keep that workspace under ``workspace_budget`` bytes, on the current stream."""
+    dev = meshes.verts.device
+    n = int(obj.shape[0])
+    if depth.dim() != 3:
+        raise RuntimeError(f"gt_visibility: depth must be f32[n_im,H,W], got {tuple(depth.shape)}")
+    n_im, H, W = (int(s) for s in depth.shape)
+    ox, oy = (int(v) for v in canvas_offset)
+    info = torch.empty((n, 11), dtype=torch.int32, device=dev)
+    mask = torch.empty((n, H, W), dtype=torch.uint8, device=dev) if want_masks else None
+    mask_visib = torch.empty((n, H, W), dtype=torch.uint8, device=dev) if want_masks else None
+    if n == 0:
+        return info, mask, mask_visib
+    dp = f32_ptr(depth, "depth")
+    ints = [(obj, "obj"), (im_idx, "im_idx")]
+    for x, name in ints:
+        dev_ptr(x, torch.int32, name)
+        if x.numel() != n:
+            raise RuntimeError(f"gt_visibility: {name} must hold {n} values, got {tuple(x.shape)}")
+    f64s = [(R, "R", 9), (t, "t", 3), (K, "K", 9)]
+    for x, name, cols in f64s:
+        dev_ptr(x, torch.float64, name)
+        if x.numel() != n * cols:
+            raise RuntimeError(f"gt_visibility: {name} must hold {n} x {cols} values, got {tuple(x.shape)}")
+    lib = load()
+    per_pose = lib.gdrnpp_gt_visibility_workspace_bytes(meshes.c, 1)
+    if per_pose == 0:
+        raise RuntimeError("gt_visibility: the mesh set does not say its largest vertex count")
+    chunk = max(1, min(n, int(workspace_budget) // per_pose))
+    nbytes = lib.gdrnpp_gt_visibility_workspace_bytes(meshes.c, chunk)
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    for i0 in range(0, n, chunk):                          # stream order keeps one workspace safe across the chunks
+        m = min(chunk, n - i0)
+        launch("gdrnpp_gt_visibility", meshes.c, *[x.reshape(-1)[i0:i0 + m].data_ptr() for x, _ in ints],
+               *[x.reshape(-1)[cols * i0:cols * (i0 + m)].data_ptr() for x, _, cols in f64s], dp, n_im, H, W, ox, oy, float(delta),
+               float(z_near), float(z_far), info[i0:i0 + m].data_ptr(), mask[i0:i0 + m].data_ptr() if want_masks else None,
+               mask_visib[i0:i0 + m].data_ptr() if want_masks else None, m, ws.data_ptr(), nbytes)
+    return info, mask, mask_visib
+
+
 def pnp_iter_from_correspondences(img_pts, mdl_pts, count, K, R_net, t_net, return_info: bool = False):
     """Net-initialised iterative PnP (gdrn_evaluator.py:241-371, pnp_type="iter") for all ROIs at once."""
     b, stride, _ = img_pts.shape

@@ -394,6 +394,28 @@ int gdrnpp_vsd_counts(const gdrnpp_meshes* models, const int* obj, const int* im
                       int n_im, int H, int W, const double* taus, int n_tau, float delta, double z_near, double z_far, int* counts,
                       int b, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- BOP ground-truth info and masks — lib/pysixd/scripts/calc_gt_info.py:98-173 and calc_gt_masks.py:83-111 with visibility.py:9-54
+ * ("bop19") and misc.py:628-647: per ground-truth pose one full-canvas depth render compared with the scene's depth image.
+ * Device pointers: obj i32[n] class index into `models` (which need faces); im_idx i32[n] index into depth f32[n_im,H,W] (millimetres,
+ * 0 = missing); R, K f64[n,9] (of K only fx, fy, cx, cy are used); t f64[n,3] in the unit of the vertices.  (ox, oy) >= 0 is the canvas
+ * offset: the render covers (W + 2 ox) x (H + 2 oy) pixels with the principal point at (cx + ox, cy + oy), and the image is the window
+ * [ox, ox + W) x [oy, oy + H) of it — (W, H) for calc_gt_info.py's 3W x 3H canvas, (0, 0) for calc_gt_masks.py's plain image.  delta:
+ * the visibility tolerance; only fragments with 0 < z_near <= Z <= z_far are rendered.  info i32[n,11] = px_count_all (canvas),
+ * px_count_valid, px_count_visib (window), then the inclusive extents x_min, y_min, x_max, y_max of the canvas silhouette and of the
+ * visible part, in image coordinates (canvas index minus offset; they may be negative or reach beyond the image); empty extents are
+ * INT_MAX, INT_MAX, INT_MIN, INT_MIN (x_min > x_max).  mask, mask_visib u8[n,H,W] or NULL: the silhouette and its visible part in the
+ * window as bytes 0 / 255; the call clears them on `stream` before it renders.  What only the device can see — an obj outside
+ * [0, n_obj), an im_idx outside [0, n_im), an object without faces or vertices, or with more vertices than models->max_verts — gives
+ * that pose's whole row -1 and leaves its mask planes zero.  Integer sums, minima, maxima and bytes with one owner only: two calls give
+ * bit-equal output.  models->max_verts must be set (> 0).  workspace: gdrnpp_gt_visibility_workspace_bytes(models, n) = n * (max_verts
+ * * 40 + 16) bytes (the projected vertices and the pixel boxes).  n = 0 succeeds and touches nothing.  Argument errors return
+ * GDRNPP_EINVAL / GDRNPP_ELIMIT, launch nothing and touch no output. */
+size_t gdrnpp_gt_visibility_workspace_bytes(const gdrnpp_meshes* models, int n);
+int gdrnpp_gt_visibility(const gdrnpp_meshes* models, const int* obj, const int* im_idx, const double* R, const double* t,
+                         const double* K, const float* depth, int n_im, int H, int W, int ox, int oy, float delta, double z_near,
+                         double z_far, int* info, unsigned char* mask, unsigned char* mask_visib, int n, void* workspace,
+                         size_t workspace_bytes, void* stream);
+
 /* device-to-device copy into a raw device pointer on `stream` — the transfer CppEGLRenderer::map_tensor performs with
  * cudaMemcpy2DFromArray in the reference (lib/egl_renderer/cpp/egl_renderer.cpp:262-298): attachment -> caller's tensor */
 int gdrnpp_copy_d2d(void* dst, const void* src, size_t bytes, void* stream);
