@@ -24,9 +24,11 @@
 // Workgroups beyond a pair's own point count exit; non-symmetric pairs skip the search on a workgroup-uniform branch.
 // Roofline: the search is compute-side, 6.5 fp32 VALU operations per (query, target) (3 sub, 3 fma, half a min3); the O(n) part is
 // ~60 fp64 operations per point.  Algorithmic HBM bytes: 12 n per model (L2-resident across the pairs of a class) + 16 per workgroup written.
-#include "common.hpp"
+#include "pair_error.hpp"
 #include <cfloat>
-#include <cmath>
+
+using gdrnpp::pairs::re_deg;          // the trace form sym_error.hip takes its reS from
+using gdrnpp::pairs::wave_sum_fixed;
 
 namespace {
 
@@ -38,16 +40,6 @@ constexpr int kTile = 1024;     // targets per LDS tile (16 KiB as float4)
 constexpr int kUnroll = 4;    // targets per trip of the scan loop (a tile and a wave's share of it are multiples)
 constexpr int kPro = 24;        // doubles per pair of the prologue record
 // prologue record: [0..8] R_gt_sym, [9..17] Rrel, [18..20] trel, [21] re (deg), [22] te, [23] unused
-
-__device__ __forceinline__ double re_deg(const double* __restrict__ Re, const double* Rg) {
-  // trace(R_est R_gt^T) = sum_ik R_est[i][k] R_gt[i][k]   (pose_error.py:367-372)
-  double tr = 0.0;
-#pragma unroll
-  for (int i = 0; i < 3; ++i) tr += (Re[3 * i] * Rg[3 * i] + Re[3 * i + 1] * Rg[3 * i + 1]) + Re[3 * i + 2] * Rg[3 * i + 2];
-  tr = tr <= 3.0 ? tr : 3.0;
-  const double c = fmin(1.0, fmax(-1.0, 0.5 * (tr - 1.0)));
-  return acos(c) * (180.0 / 3.14159265358979323846);
-}
 
 __global__ __launch_bounds__(64) void pose_error_prologue(
     const int* __restrict__ obj, int n_obj, const double* __restrict__ R_est, const double* __restrict__ t_est,
@@ -94,13 +86,6 @@ __global__ __launch_bounds__(64) void pose_error_prologue(
   P[21] = re;
   P[22] = sqrt((d0 * d0 + d1 * d1) + d2 * d2);
   P[23] = 0.0;
-}
-
-__device__ __forceinline__ double wave_sum_fixed(double v) {
-  // fixed tree over the 64 lanes: the same order in every run
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;
 }
 
 __global__ __launch_bounds__(kPts) void pose_error_points(

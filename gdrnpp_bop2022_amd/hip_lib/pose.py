@@ -212,6 +212,25 @@ def pack_pose_records(R, t_refined, t_net, score, obj_id, roi_id):
     return rec
 
 
+def _pair_args(what: str, meshes: MeshSet, obj, R_est, t_est, R_gt, t_gt, K, k_optional: bool = False):
+    """The checks every pair-error wrapper makes -> (obj pointer, [R_est, t_est, R_gt, t_gt, K pointers]): obj is i32 and lies in the
+    mesh set (the read-back of two integers), each tensor is f64 and holds b x cols values.  ``K`` may be None only where ``k_optional``."""
+    b = int(obj.shape[0])
+    op = dev_ptr(obj, torch.int32, "obj")
+    lo, hi = torch.aminmax(obj)
+    if int(lo) < 0 or int(hi) >= meshes.n_obj:
+        raise RuntimeError(f"{what}: obj must lie in [0, {meshes.n_obj}), got [{int(lo)}, {int(hi)}]")
+    ptrs = []
+    for t, name, cols in ((R_est, "R_est", 9), (t_est, "t_est", 3), (R_gt, "R_gt", 9), (t_gt, "t_gt", 3), (K, "K", 9)):
+        if t is None and name == "K" and k_optional:
+            ptrs.append(None)
+            continue
+        ptrs.append(dev_ptr(t, torch.float64, name))
+        if t.numel() != b * cols:
+            raise RuntimeError(f"{what}: {name} must hold {b} x {cols} values, got {tuple(t.shape)}")
+    return op, ptrs
+
+
 def pose_errors(meshes: MeshSet, obj, R_est, t_est, R_gt, t_gt, K, sym_rots=None, sym_off=None, symmetric=None) -> torch.Tensor:
     """``gdrnpp_pose_errors``: the custom evaluator's errors of b (estimate, ground truth) pairs -> f64[b,4] = ad (ADD, or ADI for
     a class flagged in ``symmetric``), re (degrees, against the closest symmetric ground-truth rotation), te, proj (pixels).
@@ -223,15 +242,7 @@ def pose_errors(meshes: MeshSet, obj, R_est, t_est, R_gt, t_gt, K, sym_rots=None
     out = torch.empty((b, 4), dtype=torch.float64, device=dev)
     if b == 0:
         return out
-    op = dev_ptr(obj, torch.int32, "obj")
-    lo, hi = torch.aminmax(obj)
-    if int(lo) < 0 or int(hi) >= meshes.n_obj:
-        raise RuntimeError(f"pose_errors: obj must lie in [0, {meshes.n_obj}), got [{int(lo)}, {int(hi)}]")
-    ptrs = []
-    for t, name, cols in ((R_est, "R_est", 9), (t_est, "t_est", 3), (R_gt, "R_gt", 9), (t_gt, "t_gt", 3), (K, "K", 9)):
-        ptrs.append(dev_ptr(t, torch.float64, name))
-        if t.numel() != b * cols:
-            raise RuntimeError(f"pose_errors: {name} must hold {b} x {cols} values, got {tuple(t.shape)}")
+    op, ptrs = _pair_args("pose_errors", meshes, obj, R_est, t_est, R_gt, t_gt, K)
     if (sym_rots is None) != (sym_off is None):
         raise RuntimeError("pose_errors: sym_rots and sym_off come together")
     sp = so = fp = None
@@ -249,36 +260,33 @@ def pose_errors(meshes: MeshSet, obj, R_est, t_est, R_gt, t_gt, K, sym_rots=None
     return out
 
 
-def _pair_sym_args(what: str, meshes: MeshSet, obj, R_est, t_est, R_gt, t_gt, K, sym_R, sym_t, sym_off, k_optional: bool = False):
-    """The argument checks ``bop_errors`` and ``sym_errors`` share -> (obj pointer, [R_est, t_est, R_gt, t_gt, K, sym_R, sym_t pointers],
-    sym_off as a contiguous host i32 array: keep it alive across the launch).  ``K`` may be None only where ``k_optional``."""
+def _pair_sym_errors(what: str, cols: int, k_optional: bool, meshes: MeshSet, obj, R_est, t_est, R_gt, t_gt, K, sym_R, sym_t, sym_off):
+    """``bop_errors`` and ``sym_errors``: the checks, the host copy of sym_off, the workspace and the launch of ``gdrnpp_<what>``
+    -> f64[b,cols]."""
     import numpy as np
 
+    dev = meshes.verts.device
     b = int(obj.shape[0])
-    op = dev_ptr(obj, torch.int32, "obj")
-    lo, hi = torch.aminmax(obj)
-    if int(lo) < 0 or int(hi) >= meshes.n_obj:
-        raise RuntimeError(f"{what}: obj must lie in [0, {meshes.n_obj}), got [{int(lo)}, {int(hi)}]")
-    ptrs = []
-    for t, name, cols in ((R_est, "R_est", 9), (t_est, "t_est", 3), (R_gt, "R_gt", 9), (t_gt, "t_gt", 3), (K, "K", 9)):
-        if t is None and name == "K" and k_optional:
-            ptrs.append(None)
-            continue
-        ptrs.append(dev_ptr(t, torch.float64, name))
-        if t.numel() != b * cols:
-            raise RuntimeError(f"{what}: {name} must hold {b} x {cols} values, got {tuple(t.shape)}")
+    out = torch.empty((b, cols), dtype=torch.float64, device=dev)
+    if b == 0:
+        return out
+    op, ptrs = _pair_args(what, meshes, obj, R_est, t_est, R_gt, t_gt, K, k_optional)
     off = np.ascontiguousarray(sym_off.cpu().numpy() if isinstance(sym_off, torch.Tensor) else sym_off).reshape(-1)
     if off.dtype.kind not in "iu" or off.size != meshes.n_obj + 1:
         raise RuntimeError(f"{what}: sym_off must hold n_obj + 1 = {meshes.n_obj + 1} integer offsets")
-    off = off.astype(np.int32)
+    off = off.astype(np.int32)          # a contiguous host array, alive across the launch
     n_sym = int(off[-1])
     if off[0] != 0 or (np.diff(off) <= 0).any():
         raise RuntimeError(f"{what}: sym_off must start at 0 and give every object at least one transformation (the identity)")
-    for t, name, cols in ((sym_R, "sym_R", 9), (sym_t, "sym_t", 3)):
+    for t, name, c in ((sym_R, "sym_R", 9), (sym_t, "sym_t", 3)):
         ptrs.append(dev_ptr(t, torch.float64, name))
-        if t.numel() != n_sym * cols:
-            raise RuntimeError(f"{what}: {name} must hold sym_off[-1] x {cols} = {n_sym} x {cols} values, got {tuple(t.shape)}")
-    return op, ptrs, off
+        if t.numel() != n_sym * c:
+            raise RuntimeError(f"{what}: {name} must hold sym_off[-1] x {c} = {n_sym} x {c} values, got {tuple(t.shape)}")
+    offp = off.ctypes.data
+    nbytes = getattr(load(), f"gdrnpp_{what}_workspace_bytes")(meshes.c, offp, b)
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    launch(f"gdrnpp_{what}", meshes.c, op, *ptrs, offp, out.data_ptr(), b, ws.data_ptr(), nbytes)
+    return out
 
 
 def bop_errors(meshes: MeshSet, obj, R_est, t_est, R_gt, t_gt, K, sym_R, sym_t, sym_off) -> torch.Tensor:
@@ -288,17 +296,7 @@ def bop_errors(meshes: MeshSet, obj, R_est, t_est, R_gt, t_gt, K, sym_R, sym_t, 
     (``lib.pysixd.misc.get_symmetry_transformations``), object after object; sym_off: n_obj + 1 offsets into them (a sequence, an
     array or a tensor; it is read on the host, where it sizes the launch).  The other arguments are device tensors; ``obj`` is
     checked against the mesh set here (one read-back of two integers)."""
-    dev = meshes.verts.device
-    b = int(obj.shape[0])
-    out = torch.empty((b, 2), dtype=torch.float64, device=dev)
-    if b == 0:
-        return out
-    op, ptrs, off = _pair_sym_args("bop_errors", meshes, obj, R_est, t_est, R_gt, t_gt, K, sym_R, sym_t, sym_off)
-    offp = off.ctypes.data
-    nbytes = load().gdrnpp_bop_errors_workspace_bytes(meshes.c, offp, b)
-    ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
-    launch("gdrnpp_bop_errors", meshes.c, op, *ptrs, offp, out.data_ptr(), b, ws.data_ptr(), nbytes)
-    return out
+    return _pair_sym_errors("bop_errors", 2, False, meshes, obj, R_est, t_est, R_gt, t_gt, K, sym_R, sym_t, sym_off)
 
 
 def sym_errors(meshes: MeshSet, obj, R_est, t_est, R_gt, t_gt, K, sym_R, sym_t, sym_off) -> torch.Tensor:
@@ -307,20 +305,35 @@ def sym_errors(meshes: MeshSet, obj, R_est, t_est, R_gt, t_gt, K, sym_R, sym_t, 
     projected distance of the model points.  Arguments and checks as ``bop_errors``, except that ``K`` may be None: projS is then not
     computed (the third column is NaN), nothing runs over the model points and the call costs O(symmetries) per pair; the first two
     columns are the same bits either way."""
-    dev = meshes.verts.device
-    b = int(obj.shape[0])
-    out = torch.empty((b, 3), dtype=torch.float64, device=dev)
-    if b == 0:
-        return out
-    op, ptrs, off = _pair_sym_args("sym_errors", meshes, obj, R_est, t_est, R_gt, t_gt, K, sym_R, sym_t, sym_off, k_optional=True)
-    offp = off.ctypes.data
-    nbytes = load().gdrnpp_sym_errors_workspace_bytes(meshes.c, offp, b)
-    ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
-    launch("gdrnpp_sym_errors", meshes.c, op, *ptrs, offp, out.data_ptr(), b, ws.data_ptr(), nbytes)
-    return out
+    return _pair_sym_errors("sym_errors", 3, True, meshes, obj, R_est, t_est, R_gt, t_gt, K, sym_R, sym_t, sym_off)
 
 
 VSD_WORKSPACE_BUDGET = 256 << 20        # bytes of projected vertices one ``gdrnpp_vsd_counts`` launch may stage
+
+
+def _launch_chunked(what: str, meshes: MeshSet, count: int, ints, f64s, workspace_budget: int, rest) -> None:
+    """Launch ``gdrnpp_<what>`` over ``count`` items in chunks whose workspace (``gdrnpp_<what>_workspace_bytes``) stays under
+    ``workspace_budget`` bytes, on the current stream.  ints: (tensor, name) i32[count]; f64s: (tensor, name, cols) f64[count,cols]: both
+    are checked here and passed as each chunk's slice.  ``rest(i0, n)``: the arguments between those pointers and the chunk's n."""
+    for t, name in ints:
+        dev_ptr(t, torch.int32, name)
+        if t.numel() != count:
+            raise RuntimeError(f"{what}: {name} must hold {count} values, got {tuple(t.shape)}")
+    for t, name, cols in f64s:
+        dev_ptr(t, torch.float64, name)
+        if t.numel() != count * cols:
+            raise RuntimeError(f"{what}: {name} must hold {count} x {cols} values, got {tuple(t.shape)}")
+    query = getattr(load(), f"gdrnpp_{what}_workspace_bytes")
+    per_item = query(meshes.c, 1)
+    if per_item == 0:
+        raise RuntimeError(f"{what}: the mesh set does not say its largest vertex count")
+    chunk = max(1, min(count, int(workspace_budget) // per_item))
+    nbytes = query(meshes.c, chunk)
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=meshes.verts.device)
+    for i0 in range(0, count, chunk):                      # stream order keeps one workspace safe across the chunks
+        n = min(chunk, count - i0)
+        launch(f"gdrnpp_{what}", meshes.c, *[t.reshape(-1)[i0:i0 + n].data_ptr() for t, _ in ints],
+               *[t.reshape(-1)[cols * i0:cols * (i0 + n)].data_ptr() for t, _, cols in f64s], *rest(i0, n), n, ws.data_ptr(), nbytes)
 
 
 def vsd_counts(meshes: MeshSet, obj, im_idx, R_est, t_est, R_gt, t_gt, K, diameter, depth_test, taus, delta, z_near: float = 1.0,
@@ -342,28 +355,10 @@ def vsd_counts(meshes: MeshSet, obj, im_idx, R_est, t_est, R_gt, t_gt, K, diamet
         raise RuntimeError(f"vsd_counts: depth_test must be f32[n_im,H,W], got {tuple(depth_test.shape)}")
     n_im, H, W = (int(s) for s in depth_test.shape)
     dp = f32_ptr(depth_test, "depth_test")
-    ints = [(obj, "obj"), (im_idx, "im_idx")]
-    for t, name in ints:
-        dev_ptr(t, torch.int32, name)
-        if t.numel() != b:
-            raise RuntimeError(f"vsd_counts: {name} must hold {b} values, got {tuple(t.shape)}")
-    f64s = [(R_est, "R_est", 9), (t_est, "t_est", 3), (R_gt, "R_gt", 9), (t_gt, "t_gt", 3), (K, "K", 9), (diameter, "diameter", 1)]
-    for t, name, cols in f64s:
-        dev_ptr(t, torch.float64, name)
-        if t.numel() != b * cols:
-            raise RuntimeError(f"vsd_counts: {name} must hold {b} x {cols} values, got {tuple(t.shape)}")
-    lib = load()
-    per_pair = lib.gdrnpp_vsd_counts_workspace_bytes(meshes.c, 1)
-    if per_pair == 0:
-        raise RuntimeError("vsd_counts: the mesh set does not say its largest vertex count")
-    chunk = max(1, min(b, int(workspace_budget) // per_pair))
-    nbytes = lib.gdrnpp_vsd_counts_workspace_bytes(meshes.c, chunk)
-    ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
-    for i0 in range(0, b, chunk):                          # stream order keeps one workspace safe across the chunks
-        n = min(chunk, b - i0)
-        launch("gdrnpp_vsd_counts", meshes.c, *[t.reshape(-1)[i0:i0 + n].data_ptr() for t, _ in ints],
-               *[t.reshape(-1)[cols * i0:cols * (i0 + n)].data_ptr() for t, _, cols in f64s], dp, n_im, H, W, tau_t.data_ptr(), n_tau,
-               float(delta), float(z_near), float(z_far), out[i0:i0 + n].data_ptr(), n, ws.data_ptr(), nbytes)
+    _launch_chunked("vsd_counts", meshes, b, [(obj, "obj"), (im_idx, "im_idx")],
+                    [(R_est, "R_est", 9), (t_est, "t_est", 3), (R_gt, "R_gt", 9), (t_gt, "t_gt", 3), (K, "K", 9), (diameter, "diameter", 1)],
+                    workspace_budget, lambda i0, n: (dp, n_im, H, W, tau_t.data_ptr(), n_tau, float(delta), float(z_near), float(z_far),
+                                                     out[i0:i0 + n].data_ptr()))
     return out
 
 
@@ -404,29 +399,10 @@ def gt_visibility(meshes: MeshSet, obj, im_idx, R, t, K, depth, delta, *, canvas
     if n == 0:
         return info, mask, mask_visib
     dp = f32_ptr(depth, "depth")
-    ints = [(obj, "obj"), (im_idx, "im_idx")]
-    for x, name in ints:
-        dev_ptr(x, torch.int32, name)
-        if x.numel() != n:
-            raise RuntimeError(f"gt_visibility: {name} must hold {n} values, got {tuple(x.shape)}")
-    f64s = [(R, "R", 9), (t, "t", 3), (K, "K", 9)]
-    for x, name, cols in f64s:
-        dev_ptr(x, torch.float64, name)
-        if x.numel() != n * cols:
-            raise RuntimeError(f"gt_visibility: {name} must hold {n} x {cols} values, got {tuple(x.shape)}")
-    lib = load()
-    per_pose = lib.gdrnpp_gt_visibility_workspace_bytes(meshes.c, 1)
-    if per_pose == 0:
-        raise RuntimeError("gt_visibility: the mesh set does not say its largest vertex count")
-    chunk = max(1, min(n, int(workspace_budget) // per_pose))
-    nbytes = lib.gdrnpp_gt_visibility_workspace_bytes(meshes.c, chunk)
-    ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
-    for i0 in range(0, n, chunk):                          # stream order keeps one workspace safe across the chunks
-        m = min(chunk, n - i0)
-        launch("gdrnpp_gt_visibility", meshes.c, *[x.reshape(-1)[i0:i0 + m].data_ptr() for x, _ in ints],
-               *[x.reshape(-1)[cols * i0:cols * (i0 + m)].data_ptr() for x, _, cols in f64s], dp, n_im, H, W, ox, oy, float(delta),
-               float(z_near), float(z_far), info[i0:i0 + m].data_ptr(), mask[i0:i0 + m].data_ptr() if want_masks else None,
-               mask_visib[i0:i0 + m].data_ptr() if want_masks else None, m, ws.data_ptr(), nbytes)
+    _launch_chunked("gt_visibility", meshes, n, [(obj, "obj"), (im_idx, "im_idx")], [(R, "R", 9), (t, "t", 3), (K, "K", 9)], workspace_budget,
+                    lambda i0, m: (dp, n_im, H, W, ox, oy, float(delta), float(z_near), float(z_far), info[i0:i0 + m].data_ptr(),
+                                   mask[i0:i0 + m].data_ptr() if want_masks else None,
+                                   mask_visib[i0:i0 + m].data_ptr() if want_masks else None))
     return info, mask, mask_visib
 
 
