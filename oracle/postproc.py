@@ -300,12 +300,15 @@ def pose_from_predictions_test(pred_rots, pred_centroids, pred_z_vals, roi_cams,
 
 
 def depth_refine_roi(xyz_i, mask_i, roi_depth_256, K_crop, rot_est, trans_est, verts, faces, iters=2, threshold=0.8,
-                     use_coor_z=False, crop_res=64, z_near=0.1, z_far=100.0, return_debug=False):
+                     use_coor_z=False, crop_res=64, z_near=0.1, z_far=100.0, return_debug=False, stats=None):
     """gdrn_evaluator.py:485-561 for ONE ROI (demo/predictor_gdrn.py:228-284 is the runnable twin).
 
     xyz_i f32[res,res,3] normalised maps (HWC), mask_i f32[res,res] normalised soft mask,
     roi_depth_256 f32[4res,4res], K_crop f32[3,3], rot_est f32[3,3], trans_est f32[3].
     Returns the refined translation (float64[3], or the float32 input values if no iteration applied).
+    stats: a list that receives one dict per iteration (the return value does not change): rendered (pixels), norm_sum, stepped
+    (a translation step was taken), and where one was: qmax, nsel, median, diffs (the selected depth differences, row-major) and
+    margin = min |q - thr| / qmax over all pixels — how far the closest pixel is from changing sides of the threshold.
     """
     f32 = np.float32
     xyz_i = np.asarray(xyz_i, f32)
@@ -333,6 +336,8 @@ def depth_refine_roi(xyz_i, mask_i, roi_depth_256, K_crop, rot_est, trans_est, v
             query_img_norm = query_img_norm * ren_mask * depth_sensor_mask_crop
         query_img_norm = query_img_norm.astype(f32)
         norm_sum = query_img_norm.sum()
+        if stats is not None:
+            stats.append(dict(rendered=int(ren_mask.sum()), norm_sum=float(norm_sum), stepped=False))
         if norm_sum == 0:
             continue
         query_img_norm = query_img_norm / norm_sum
@@ -340,6 +345,12 @@ def depth_refine_roi(xyz_i, mask_i, roi_depth_256, K_crop, rot_est, trans_est, v
         yy, xx = np.argwhere(norm_mask).T
         depth_diff = depth_sensor_crop[yy, xx] - ren_dp[yy, xx]
         depth_adjustment = np.median(depth_diff)
+        if stats is not None:
+            qmax = query_img_norm.max()
+            with np.errstate(invalid="ignore"):
+                margin = np.abs(query_img_norm - qmax * f32(threshold)) / qmax
+            stats[-1].update(stepped=True, qmax=float(qmax), nsel=int(norm_mask.sum()), median=float(depth_adjustment),
+                             diffs=depth_diff.copy(), margin=float(margin.min()), closest=int(margin.argmin()))
 
         yx_coords = np.meshgrid(np.arange(crop_res), np.arange(crop_res))
         yx_coords = np.stack(yx_coords[::-1], axis=-1)

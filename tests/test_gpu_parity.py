@@ -371,7 +371,8 @@ def test_decode_and_refine_sigmoid_mask_type(hip):
 
 
 def test_fallback_refine_kernel_for_large_meshes(hip):
-    """Meshes above the LDS staging limit (4096 vertices) take the non-staged kernel: same results."""
+    """Meshes above the LDS staging limit (kMaxStagedVerts = 2688 vertices) take the non-staged kernel: same results.  The limit
+    itself is tests/test_gpu_refine_edges.py's."""
     b = 4
     verts, faces, det, maps = make_case(b=b, seed=13, subdiv=5, num_classes=2)   # 10242 V / 20480 F
     assert len(verts[0]) > 4096
