@@ -25,8 +25,8 @@ from .gemm import (A_F16X2_ROWS, C_F16X2_ROWS, X3, conv2d_f32_split, conv3x3_f32
                    packed_rows_in_range, unpack_weight_bf16x3, unpack_weight_f16x2, upsample2x_conv3x3_groupnorm_act, upsample2x_conv3x3_raw)
 from .net import (POINT_PNP_TILE, ROT_DIMS, ROT_MODES, T_MODES, bias_act_nhwc_, dwconv7x7_ln, groupnorm_act, head_tail_nhwc,  # noqa: F401
                   layernorm_nhwc, pnp_fc_heads, pnp_fc_heads_pose, point_pnp_fc, point_pnp_pool, stem_conv4x4_ln, upsample_bilinear2x)
-from .pose import (GT_INFO_COLUMNS, MeshSet, bop_errors, decode_correspondences, depth_refine, epnp_batched, epnp_ransac, flow_forward, fps,  # noqa: F401
-                   gt_visibility, nnd_backward, nnd_forward, pack_pose_records, paste_masks_rle, pnp_iter_from_correspondences, pose_from_pred,
+from .pose import (GT_INFO_COLUMNS, XYZ_CROP_COLUMNS, MeshSet, bop_errors, decode_correspondences, depth_refine, epnp_batched, epnp_ransac,  # noqa: F401
+                   flow_forward, fps, gt_visibility, gt_xyz_crops, nnd_backward, nnd_forward, pack_pose_records, paste_masks_rle, pnp_iter_from_correspondences, pose_from_pred,
                    pose_errors, pose_from_pred_centroid_z, refine_kernel_name, refine_to_records, render_depth, set_refine_event_sink,
                    sym_errors, uncertainty_pnp_batched, vsd_counts, vsd_errors, zoom_K)
 from .range_words import (X3_NONFINITE, X3_SLOTS, X3_SMALL_ROWS, range_words_of, split2_nonfinite, split2_range_words,  # noqa: F401

@@ -4,7 +4,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_long, c_size_t, c_void_p
+from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_long, c_longlong, c_size_t, c_void_p
 
 import torch
 
@@ -82,6 +82,9 @@ SIGNATURES = {
     "gdrnpp_gt_visibility_workspace_bytes": (c_size_t, [POINTER(gdrnpp_meshes), c_int]),
     "gdrnpp_gt_visibility": (c_int, [POINTER(gdrnpp_meshes), _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_float, c_double,
                                      c_double, _P, _P, _P, c_int, _P, c_size_t, _P]),
+    "gdrnpp_gt_xyz_crop_workspace_bytes": (c_size_t, [POINTER(gdrnpp_meshes), c_int]),
+    "gdrnpp_gt_xyz_crop": (c_int, [POINTER(gdrnpp_meshes), _P, _P, _P, _P, c_int, c_int, c_double, c_double, _P, c_longlong, _P, _P, c_int,
+                                   _P, c_size_t, _P]),
     "gdrnpp_pose_from_pred": (c_int, [_P, c_int, _P, c_int, _P, _P, _P, _P, _P, _P, c_int, c_int, _P]),
     "gdrnpp_debug_refine_profile": (c_int, [_P]),
     "gdrnpp_pack_weight_bf16x3": (c_int, [_P, _P, c_int, c_int, _P]),

@@ -406,6 +406,90 @@ def gt_visibility(meshes: MeshSet, obj, im_idx, R, t, K, depth, delta, *, canvas
     return info, mask, mask_visib
 
 
+XYZ_CROP_COLUMNS = ("status", "px_count", "x1", "y1", "x2", "y2", "box_x1", "box_x2", "box_y1", "box_y2", "offset")
+XYZ_CROP_CAPACITY_PX = 4 << 20          # pixels (6 bytes each) of the packed buffer one ``gdrnpp_gt_xyz_crop`` launch may fill by default
+_XYZ_ROW = 12                           # i32 per pose on the device: the eleven columns, the offset in two words
+_XYZ_PX_PER_POSE = {}                   # (W, H) -> the largest share of the packed buffer a pose has used: sizes the next call's first copy
+
+
+def gt_xyz_crops(meshes: MeshSet, obj, R, t, K, im_size, *, z_near: float = 0.01, z_far: float = 6.5, capacity_px: int | None = None,
+                 out: torch.Tensor | None = None, workspace_budget: int = VSD_WORKSPACE_BUDGET):
+    """``gdrnpp_gt_xyz_crop``: the xyz_crop targets of n ground-truth poses, what the reference's ``*_1_gen_xyz.py`` tools compute per pose
+    -> (packed f16[total_px,3] host array, table i64[n,11] host array).  table columns are ``XYZ_CROP_COLUMNS``: status (0, or -1 for a pose
+    whose obj is out of range or whose object has no faces: the whole row is -1), the covered-pixel count, the inclusive extents of coverage
+    (empty: INT_MAX, INT_MAX, INT_MIN, INT_MIN), the conservative box the pose occupies in ``packed`` (inclusive; empty when box_x1 >
+    box_x2) and its offset there in pixels: pixel (x, y) of the box is ``packed[offset + (y - box_y1) * (box_x2 - box_x1 + 1) + (x - box_x1)]``,
+    zeros where it is not covered.  obj i32[n]; R, K f64[n,3,3|9]; t f64[n,3] in the unit of the meshes' vertices (the tools: metres): device
+    tensors.  im_size (W, H).
+
+    The poses run in launches of at most ``workspace_budget`` bytes of staged vertices (40 per vertex of the largest model per pose) and
+    ``capacity_px`` packed pixels (>= W * H; default ``XYZ_CROP_CAPACITY_PX`` or one image per pose, whichever is less).  A launch defers
+    the poses that do not fit; the next one starts at the first of them.  The rows and the packed pixels of a launch share one device
+    allocation and come back in ONE device-to-host copy; its length is a guess (the whole capacity for the first launch at an image
+    size in this process, then twice the largest share a pose has used so far) and only a launch that used more costs a second copy
+    for the rest.  ``out``: a caller's f16 device
+    buffer of at least 3 * capacity_px elements to render into (then the rows come in a copy of their own); nothing at or beyond the
+    pixels a launch used is written there."""
+    import numpy as np
+
+    what = "gt_xyz_crop"
+    dev = meshes.verts.device
+    n = int(obj.shape[0])
+    W, H = int(im_size[0]), int(im_size[1])
+    dev_ptr(obj, torch.int32, "obj")
+    for x, name, cols in ((R, "R", 9), (t, "t", 3), (K, "K", 9)):
+        dev_ptr(x, torch.float64, name)
+        if x.numel() != n * cols:
+            raise RuntimeError(f"{what}: {name} must hold {n} x {cols} values, got {tuple(x.shape)}")
+    if n == 0:
+        return np.zeros((0, 3), np.float16), np.zeros((0, len(XYZ_CROP_COLUMNS)), np.int64)
+    query = load().gdrnpp_gt_xyz_crop_workspace_bytes
+    per_item = query(meshes.c, 1)
+    if per_item == 0:
+        raise RuntimeError(f"{what}: the mesh set does not say its largest vertex count")
+    chunk = max(1, min(n, int(workspace_budget) // per_item))
+    if capacity_px is None:
+        capacity_px = out.numel() // 3 if out is not None else max(H * W, min(chunk * H * W, XYZ_CROP_CAPACITY_PX))
+    capacity_px = int(capacity_px)
+    if out is not None:
+        dev_ptr(out, torch.float16, "out")
+        if out.numel() < 3 * capacity_px:
+            raise RuntimeError(f"{what}: out must hold 3 x capacity_px = {3 * capacity_px} values, got {out.numel()}")
+    nbytes = query(meshes.c, chunk)
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    head = (16 + 4 * _XYZ_ROW * chunk + 15) // 16 * 16                      # totals i64[2], rows i32[chunk,12]; then the packed pixels
+    buf = torch.empty((head + (0 if out is not None else 6 * capacity_px),), dtype=torch.uint8, device=dev)
+    out_ptr = out.data_ptr() if out is not None else buf.data_ptr() + head
+    obj1, R1, t1, K1 = obj.reshape(-1), R.reshape(-1), t.reshape(-1), K.reshape(-1)
+    tables, packs, i0, total, per_pose = [], [], 0, 0, _XYZ_PX_PER_POSE.get((W, H))
+    while i0 < n:                                                           # the copy below waits for the launch: one workspace serves all
+        m = min(chunk, n - i0)
+        launch("gdrnpp_gt_xyz_crop", meshes.c, obj1[i0:i0 + m].data_ptr(), R1[9 * i0:9 * (i0 + m)].data_ptr(), t1[3 * i0:3 * (i0 + m)].data_ptr(),
+               K1[9 * i0:9 * (i0 + m)].data_ptr(), H, W, float(z_near), float(z_far), out_ptr, capacity_px, buf.data_ptr() + 16, buf.data_ptr(),
+               m, ws.data_ptr(), nbytes)
+        guess = 0 if out is not None else capacity_px if per_pose is None else min(capacity_px, 2 * per_pose * m)
+        host = buf[:head + 6 * guess].cpu().numpy()
+        n_done, used = (int(v) for v in host[:16].view(np.int64))
+        if n_done <= 0:
+            raise RuntimeError(f"{what}: a launch served no pose (capacity {capacity_px} px, image {W} x {H})")
+        rows = host[16:16 + 4 * _XYZ_ROW * m].view(np.int32).reshape(m, _XYZ_ROW)[:n_done].astype(np.int64)
+        if out is not None:
+            pixels = out.reshape(-1)[:3 * used].cpu().numpy()
+        elif used <= guess:
+            pixels = host[head:head + 6 * used].view(np.float16)
+        else:
+            pixels = np.concatenate([host[head:], buf[head + 6 * guess:head + 6 * used].cpu().numpy()]).view(np.float16)
+        table = rows[:, :len(XYZ_CROP_COLUMNS)].copy()
+        table[:, 10] = np.where(rows[:, 0] == 0, (rows[:, 10] & 0xffffffff) | (rows[:, 11] << 32), 0) + total
+        table[rows[:, 0] < 0] = -1
+        tables.append(table)
+        packs.append(pixels.reshape(-1, 3))
+        per_pose = _XYZ_PX_PER_POSE[(W, H)] = max(per_pose or 0, -(-used // n_done))
+        total += used
+        i0 += n_done
+    return (packs[0] if len(packs) == 1 else np.concatenate(packs)), np.concatenate(tables)
+
+
 def pnp_iter_from_correspondences(img_pts, mdl_pts, count, K, R_net, t_net, return_info: bool = False):
     """Net-initialised iterative PnP (gdrn_evaluator.py:241-371, pnp_type="iter") for all ROIs at once."""
     b, stride, _ = img_pts.shape

@@ -416,6 +416,28 @@ int gdrnpp_gt_visibility(const gdrnpp_meshes* models, const int* obj, const int*
                          double z_far, int* info, unsigned char* mask, unsigned char* mask_visib, int n, void* workspace,
                          size_t workspace_bytes, void* stream);
 
+/* ---- xyz_crop training targets — core/gdrn_modeling/tools/tless/tless_pbr_1_gen_xyz.py:95-187 (and its lm, tudl, icbin, itodd
+ * siblings) with lib/pysixd/misc.py:381-409 (calc_xyz_bp_torch): per ground-truth pose one render of the plain W x H image, the covered
+ * pixels back-projected to object space in float32 and stored as float16, only the pose's pixel box written, pose after pose.
+ * Device pointers: obj i32[n] class index into `models` (which need faces); R, K f64[n,9] (of K only fx, fy, cx, cy are used); t
+ * f64[n,3] in the unit of the vertices.  Only fragments with 0 < z_near <= Z <= z_far are rendered.  rows i32[n,12] = status (0 served,
+ * 1 deferred, -1 refused), the covered-pixel count, the inclusive extents x1, y1, x2, y2 of coverage (empty: INT_MAX, INT_MAX, INT_MIN,
+ * INT_MIN), the conservative box i_lo, i_hi, j_lo, j_hi (inclusive, empty when lo > hi; it contains the extents) and the pose's offset
+ * into `out` in pixels (low word, high word).  out: fp16 bits, capacity_px x 3; pixel (x, y) of a served pose's box is at
+ * out[(offset + (y - j_lo) (i_hi - i_lo + 1) + (x - i_lo)) 3 + c], three +0 where the pixel is not covered.  Every element of a served
+ * pose's box is written exactly once and nothing at or beyond totals[1] pixels is touched: `out` needs no clearing.  The first pose whose
+ * box would end beyond capacity_px and every pose after it are deferred (status 1, nothing written): totals i64[2] = the number of poses
+ * in front of them, the pixels those use.  capacity_px >= H W, so a call serves at least its first pose; call again from pose
+ * totals[0].  What only the device can see — an obj outside [0, n_obj), an object without faces or vertices, or with more vertices
+ * than models->max_verts — gives that pose's whole row -1 and no space.  Fixed fp32 expressions, one owner per element, integer sums,
+ * minima and maxima: two calls give bit-equal output.  models->max_verts must be set (> 0).  workspace:
+ * gdrnpp_gt_xyz_crop_workspace_bytes(models, n) = n * max_verts * 40 bytes (the projected vertices).  n = 0 succeeds and touches
+ * nothing.  Argument errors return GDRNPP_EINVAL / GDRNPP_ELIMIT, launch nothing and touch no output. */
+size_t gdrnpp_gt_xyz_crop_workspace_bytes(const gdrnpp_meshes* models, int n);
+int gdrnpp_gt_xyz_crop(const gdrnpp_meshes* models, const int* obj, const double* R, const double* t, const double* K, int H, int W,
+                       double z_near, double z_far, unsigned short* out, long long capacity_px, int* rows, long long* totals, int n,
+                       void* workspace, size_t workspace_bytes, void* stream);
+
 /* device-to-device copy into a raw device pointer on `stream` — the transfer CppEGLRenderer::map_tensor performs with
  * cudaMemcpy2DFromArray in the reference (lib/egl_renderer/cpp/egl_renderer.cpp:262-298): attachment -> caller's tensor */
 int gdrnpp_copy_d2d(void* dst, const void* src, size_t bytes, void* stream);
