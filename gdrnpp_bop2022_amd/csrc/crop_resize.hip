@@ -16,120 +16,11 @@
 // of source pixels under the ROI, read through L2).  The coord_2d source map is never materialised: its value at
 // integer (x, y) is the analytic float32(x * (1/W)) of get_2d_coord_np (data_utils.py:304-323).
 #include "common.hpp"
+#include "warp_affine.hpp"
 
 namespace {
 
 constexpr int kPixPerThread = 16;  // 4096 pixels per workgroup: the per-ROI LU prologue is amortised over 16 rows
-constexpr int AB_BITS = 10, AB_SCALE = 1 << AB_BITS, INTER_BITS = 5, INTER_TAB_SIZE = 1 << INTER_BITS;
-
-__device__ __forceinline__ int cv_round(double v) { return __double2int_rn(v); }
-__device__ __forceinline__ int sat_short(int v) { return v < -32768 ? -32768 : (v > 32767 ? 32767 : v); }
-
-// cv::LUImpl, 6x6, one right-hand side (getAffineTransform).  Every index is a compile-time constant after unrolling (the
-// pivot row is applied as a chain of predicated swaps), so the system lives in registers: with a run-time row index the
-// arrays went to scratch memory and the solve took 20 us on the one lane that does it.  Same operations in the same order
-// as the loop form (first maximal pivot, `>` comparison).
-__device__ __forceinline__ bool lu_solve6(double (&A)[36], double (&b)[6]) {
-  constexpr int m = 6;
-#pragma unroll
-  for (int i = 0; i < m; i++) {
-    int k = i;
-    double best = fabs(A[i * m + i]);
-#pragma unroll
-    for (int j = i + 1; j < m; j++) {
-      const double v = fabs(A[j * m + i]);
-      if (v > best) { best = v; k = j; }
-    }
-    if (best < 2.220446049250313e-16 * 100) return false;
-#pragma unroll
-    for (int r = i + 1; r < m; r++) {
-      const bool sw = k == r;
-#pragma unroll
-      for (int j = i; j < m; j++) {
-        const double ai = A[i * m + j], ar = A[r * m + j];
-        A[i * m + j] = sw ? ar : ai;
-        A[r * m + j] = sw ? ai : ar;
-      }
-      const double bi = b[i], br = b[r];
-      b[i] = sw ? br : bi;
-      b[r] = sw ? bi : br;
-    }
-    const double d = -1 / A[i * m + i];
-#pragma unroll
-    for (int j = i + 1; j < m; j++) {
-      const double alpha = A[j * m + i] * d;
-#pragma unroll
-      for (int kk = i + 1; kk < m; kk++) A[j * m + kk] += alpha * A[i * m + kk];
-      b[j] += alpha * b[i];
-    }
-  }
-#pragma unroll
-  for (int i = m - 1; i >= 0; i--) {
-    double s = b[i];
-#pragma unroll
-    for (int k = i + 1; k < m; k++) s -= A[i * m + k] * b[k];
-    b[i] = s / A[i * m + i];
-  }
-  return true;
-}
-
-// get_affine_transform(center, scale, rot=0, (out,out)) -> inverse map M (dst -> src) as warpAffine forms it
-__device__ void inverse_affine(double cx, double cy, double scale, int out, double* M) {
-  float src[3][2], dst[3][2];
-  const double src_dir1 = 0.0 * 0.0 + (scale * -0.5) * 1.0;
-  const double src_dir0 = 0.0 * 1.0 - (scale * -0.5) * 0.0;
-  src[0][0] = (float)(cx + scale * 0.0); src[0][1] = (float)(cy + scale * 0.0);
-  src[1][0] = (float)(cx + src_dir0 + scale * 0.0); src[1][1] = (float)(cy + src_dir1 + scale * 0.0);
-  dst[0][0] = (float)(out * 0.5); dst[0][1] = (float)(out * 0.5);
-  dst[1][0] = (float)(out * 0.5) + 0.f; dst[1][1] = (float)(out * 0.5) + (float)(out * -0.5);
-  float dx = src[0][0] - src[1][0], dy = src[0][1] - src[1][1];
-  src[2][0] = src[1][0] + (-dy); src[2][1] = src[1][1] + dx;
-  dx = dst[0][0] - dst[1][0]; dy = dst[0][1] - dst[1][1];
-  dst[2][0] = dst[1][0] + (-dy); dst[2][1] = dst[1][1] + dx;
-  double a[36], b[6];
-#pragma unroll
-  for (int i = 0; i < 3; i++) {
-    const int j = i * 12, k = i * 12 + 6;
-    a[j] = a[k + 3] = src[i][0];
-    a[j + 1] = a[k + 4] = src[i][1];
-    a[j + 2] = a[k + 5] = 1;
-    a[j + 3] = a[j + 4] = a[j + 5] = 0;
-    a[k] = a[k + 1] = a[k + 2] = 0;
-    b[i * 2] = dst[i][0];
-    b[i * 2 + 1] = dst[i][1];
-  }
-  if (!lu_solve6(a, b)) {
-#pragma unroll
-    for (int i = 0; i < 6; ++i) b[i] = 0.0;
-  }
-#pragma unroll
-  for (int i = 0; i < 6; ++i) M[i] = b[i];
-  double D = M[0] * M[4] - M[1] * M[3];
-  D = D != 0 ? 1. / D : 0;
-  const double A11 = M[4] * D, A22 = M[0] * D;
-  M[0] = A11; M[1] *= -D;
-  M[3] *= -D; M[4] = A22;
-  const double b1 = -M[0] * M[2] - M[1] * M[5];
-  const double b2 = -M[3] * M[2] - M[4] * M[5];
-  M[2] = b1; M[5] = b2;
-}
-
-__device__ __forceinline__ void src_coord(const double* M, int x, int y, bool nearest, int& sx, int& sy, int& alpha) {
-  const int adelta = cv_round(M[0] * x * AB_SCALE), bdelta = cv_round(M[3] * x * AB_SCALE);
-  const int round_delta = nearest ? AB_SCALE / 2 : AB_SCALE / INTER_TAB_SIZE / 2;
-  const int X0 = cv_round((M[1] * y + M[2]) * AB_SCALE) + round_delta;
-  const int Y0 = cv_round((M[4] * y + M[5]) * AB_SCALE) + round_delta;
-  if (nearest) {
-    sx = sat_short((X0 + adelta) >> AB_BITS);
-    sy = sat_short((Y0 + bdelta) >> AB_BITS);
-    alpha = 0;
-  } else {
-    const int X = (X0 + adelta) >> (AB_BITS - INTER_BITS), Y = (Y0 + bdelta) >> (AB_BITS - INTER_BITS);
-    sx = sat_short(X >> INTER_BITS);
-    sy = sat_short(Y >> INTER_BITS);
-    alpha = (Y & (INTER_TAB_SIZE - 1)) * INTER_TAB_SIZE + (X & (INTER_TAB_SIZE - 1));
-  }
-}
 
 struct Norm3 {
   double mean[3], stdv[3];

@@ -31,7 +31,8 @@ from .pose import (GT_INFO_COLUMNS, XYZ_CROP_COLUMNS, MeshSet, bop_errors, decod
                    sym_errors, uncertainty_pnp_batched, vsd_counts, vsd_errors, zoom_K)
 from .range_words import (X3_NONFINITE, X3_SLOTS, X3_SMALL_ROWS, range_words_of, split2_nonfinite, split2_range_words,  # noqa: F401
                           x3_flag_ptr, x3_flag_scope, x3_flags, x3_launch_count)
-from .roi import ROI_TABLE_COLUMNS, crop_resize_roi, roi_align, roi_pool, roi_table, rois_from_dets  # noqa: F401
+from .roi import (ROI_BIN_MASKS, ROI_TABLE_COLUMNS, ROI_TARGET_KEYS, crop_resize_roi, roi_align, roi_pool, roi_table, roi_train_targets,  # noqa: F401
+                  rois_from_dets)
 from .yolox import (CONV_ACTS, conv_bias_act_f32, letterbox_sizes, pack_conv_weight_kmajor, spp_maxpool_5_9_13,  # noqa: F401
                     upsample_nearest2x_slice, yolox_focus, yolox_letterbox, yolox_postprocess)
 

@@ -85,6 +85,8 @@ SIGNATURES = {
     "gdrnpp_gt_xyz_crop_workspace_bytes": (c_size_t, [POINTER(gdrnpp_meshes), c_int]),
     "gdrnpp_gt_xyz_crop": (c_int, [POINTER(gdrnpp_meshes), _P, _P, _P, _P, c_int, c_int, c_double, c_double, _P, c_longlong, _P, _P, c_int,
                                    _P, c_size_t, _P]),
+    "gdrnpp_roi_train_targets": (c_int, [_P, c_longlong, _P, _P, _P, c_int, _P, _P, _P, c_int, c_int, _P, _P, _P, _P, c_int, _P, c_int, c_int,
+                                         c_int, c_int, _P, _P, _P, _P, _P, _P, _P, c_int, _P]),
     "gdrnpp_pose_from_pred": (c_int, [_P, c_int, _P, c_int, _P, _P, _P, _P, _P, _P, c_int, c_int, _P]),
     "gdrnpp_debug_refine_profile": (c_int, [_P]),
     "gdrnpp_pack_weight_bf16x3": (c_int, [_P, _P, c_int, c_int, _P]),

@@ -1,5 +1,5 @@
-"""ROI preparation: crop + resize of the detections' boxes, ROIAlign / RoIPool, and the device-side ROI table filled from
-detections."""
+"""ROI preparation: crop + resize of the detections' boxes, ROIAlign / RoIPool, the device-side ROI table filled from
+detections, and the per-ROI training targets."""
 from __future__ import annotations
 
 import ctypes
@@ -101,3 +101,144 @@ def rois_from_dets(dets, count, ratio: float, H: int, W: int, cam, extents, dzi_
            f32_ptr(extents, "extents"), float(score_thr), int(top_k_per_obj), int(cap), ctypes.byref(ctab), cnt, cnt + 4,
            ws.data_ptr(), nbytes)
     return table, counts
+
+
+# key -> (torch dtype, channels or None): the reference's names of read_data_train's targets, batched along dim 0
+ROI_TARGET_KEYS = {
+    "roi_mask_obj": (torch.float32, None), "roi_mask_visib": (torch.float32, None), "roi_mask_trunc": (torch.float32, None),
+    "roi_mask_full": (torch.float32, None), "roi_region": (torch.int32, None), "roi_xyz": (torch.float32, 3),
+    "roi_xyz_bin": (torch.uint8, 3),
+}
+ROI_BIN_MASKS = ("trunc", "visib", "obj", "full")        # LOSS_CFG.XYZ_LOSS_MASK_GT -> bin_mask of gdrnpp_roi_train_targets
+ROI_MAX_FPS = 256
+
+
+def _host_i64(x, n, name, what):
+    import numpy as np
+
+    a = np.asarray(x.cpu() if isinstance(x, torch.Tensor) else x)
+    if a.shape != (n,) or (n and a.dtype.kind not in "iu"):
+        raise RuntimeError(f"{what}: {name} must hold {n} integers, got shape {a.shape} of {a.dtype}")
+    return a.astype(np.int64)
+
+
+def roi_train_targets(packed, table, centers, scales, im_size, *, src=None, masks=None, visib_idx=None, trunc_idx=None, full_idx=None,
+                      obj=None, extents=None, fps=None, out_res: int = 64, n_bin: int = 0, bin_mask="visib", want=None, out=None) -> dict:
+    """``gdrnpp_roi_train_targets``: the per-ROI targets of read_data_train (data_loader.py:448-612, TRAIN.VIS off) for n ROIs in one
+    launch -> {key: device tensor} under the reference's keys (``ROI_TARGET_KEYS``): roi_mask_obj / _visib / _trunc / _full f32[n,o,o],
+    roi_region i32[n,o,o], roi_xyz f32[n,3,o,o], roi_xyz_bin u8[n,3,o,o].
+
+    packed f16[px,3] on the device and table i64[m,11] on the host: ``hip_lib.gt_xyz_crops``'s pair (render with ``out=`` to keep the
+    pixels on the device; ``XYZ_CROP_COLUMNS``).  src: per ROI the table row it crops (host integers; None: ROI k crops row k).
+    centers f64[n,2], scales f64[n], im_size (W, H).  masks u8[n_masks,H,W] on the device with the host columns visib_idx (-1: visib =
+    obj), trunc_idx (-1: trunc = visib), full_idx (-1: roi_mask_full is 0); a column left None is all -1.  obj: host integers into extents
+    f32[n_obj,3] and fps f64[n_obj,F,3] (device).  n_bin > 0 asks for bins under ``bin_mask`` (a name of ``ROI_BIN_MASKS`` or its index)
+    and clips roi_xyz as the reference does.  want: the keys to compute; None = the masks (roi_mask_full when full_idx is given), roi_region
+    when fps is given, roi_xyz when extents is given, roi_xyz_bin when n_bin > 0.  out: {key: tensor} to write into instead of allocating.
+    Everything the kernel indexes with is checked here on the host, before it is uploaded in one copy."""
+    import numpy as np
+
+    what = "roi_train_targets"
+    W, H = int(im_size[0]), int(im_size[1])
+    dev = packed.device
+    ppx = dev_ptr(packed, torch.float16, "packed")
+    if packed.numel() % 3:
+        raise RuntimeError(f"{what}: packed must hold 3 values per pixel, got {tuple(packed.shape)}")
+    n_px = packed.numel() // 3
+    table = np.asarray(table.cpu() if isinstance(table, torch.Tensor) else table)
+    if table.ndim != 2 or table.shape[1] != 11 or table.dtype.kind not in "iu":
+        raise RuntimeError(f"{what}: table must be the i64[m,11] of gt_xyz_crops, got {table.shape} of {table.dtype}")
+    table = table.astype(np.int64)
+    n = int(scales.shape[0])
+    src = np.arange(n, dtype=np.int64) if src is None else _host_i64(src, n, "src", what)
+    if n and (src.min() < 0 or src.max() >= len(table)):
+        raise RuntimeError(f"{what}: src must index the {len(table)} rows of table")
+    rows = table[src]
+    if (rows[:, 0] != 0).any():
+        raise RuntimeError(f"{what}: table row {int(src[np.nonzero(rows[:, 0])[0][0]])} is not a served pose (status != 0)")
+    bx1, bx2, by1, by2, off = (rows[:, c] for c in (6, 7, 8, 9, 10))
+    some = (bx2 >= bx1) & (by2 >= by1)
+    box_px = np.where(some, (bx2 - bx1 + 1) * (by2 - by1 + 1), 0)
+    if (some & ((bx1 < 0) | (by1 < 0) | (bx2 >= W) | (by2 >= H))).any():
+        raise RuntimeError(f"{what}: a pose's box leaves the {W} x {H} image")
+    if (some & ((off < 0) | (off + box_px > n_px))).any():
+        raise RuntimeError(f"{what}: a pose's box ends beyond the {n_px} pixels of packed")
+    n_masks = 0
+    if masks is not None:
+        dev_ptr(masks, torch.uint8, "masks")
+        if masks.dim() != 3 or tuple(masks.shape[1:]) != (H, W):
+            raise RuntimeError(f"{what}: masks must be u8[n_masks,{H},{W}], got {tuple(masks.shape)}")
+        n_masks = int(masks.shape[0])
+    cols = []
+    for name, x in (("visib_idx", visib_idx), ("trunc_idx", trunc_idx), ("full_idx", full_idx)):
+        c = np.full((n,), -1, np.int64) if x is None else _host_i64(x, n, name, what)
+        if n and (c.min() < -1 or c.max() >= n_masks):
+            raise RuntimeError(f"{what}: {name} must be -1 or index the {n_masks} masks")
+        cols.append(c)
+    if isinstance(bin_mask, str):
+        if bin_mask not in ROI_BIN_MASKS:
+            raise RuntimeError(f"{what}: bin_mask must be one of {ROI_BIN_MASKS}, got {bin_mask!r}")
+        bin_mask = ROI_BIN_MASKS.index(bin_mask)
+    n_obj, F = 0, 0
+    if extents is not None:
+        f32_ptr(extents, "extents")
+        if extents.dim() != 2 or extents.shape[1] != 3:
+            raise RuntimeError(f"{what}: extents must be f32[n_obj,3], got {tuple(extents.shape)}")
+        n_obj = int(extents.shape[0])
+    if fps is not None:
+        dev_ptr(fps, torch.float64, "fps")
+        if fps.dim() != 3 or fps.shape[2] != 3 or (extents is not None and fps.shape[0] != n_obj):
+            raise RuntimeError(f"{what}: fps must be f64[n_obj,F,3] with the n_obj of extents, got {tuple(fps.shape)}")
+        n_obj, F = int(fps.shape[0]), int(fps.shape[1])
+        if F > ROI_MAX_FPS:
+            raise RuntimeError(f"{what}: F = {F} points per object exceeds {ROI_MAX_FPS}")
+    if want is None:
+        want = ["roi_mask_obj", "roi_mask_visib", "roi_mask_trunc"] + (["roi_mask_full"] if full_idx is not None else [])
+        want += (["roi_region"] if F > 0 else []) + (["roi_xyz"] if extents is not None else []) + (["roi_xyz_bin"] if n_bin > 0 else [])
+    want = list(want)
+    for k in want:
+        if k not in ROI_TARGET_KEYS:
+            raise RuntimeError(f"{what}: unknown output {k!r}; the keys are {tuple(ROI_TARGET_KEYS)}")
+    if "roi_region" in want and F == 0:
+        raise RuntimeError(f"{what}: roi_region needs fps with F > 0")
+    if ("roi_xyz" in want or "roi_xyz_bin" in want) and extents is None:
+        raise RuntimeError(f"{what}: roi_xyz / roi_xyz_bin need extents")
+    if "roi_xyz_bin" in want and not 0 < int(n_bin) <= 255:
+        raise RuntimeError(f"{what}: roi_xyz_bin needs 0 < n_bin <= 255, got {n_bin}")
+    obj_col = np.zeros((n,), np.int64)
+    if any(k in want for k in ("roi_region", "roi_xyz", "roi_xyz_bin")):
+        if obj is None:
+            raise RuntimeError(f"{what}: obj is needed for roi_region / roi_xyz / roi_xyz_bin")
+        obj_col = _host_i64(obj, n, "obj", what)
+        if n and (obj_col.min() < 0 or obj_col.max() >= n_obj):
+            raise RuntimeError(f"{what}: obj must index the {n_obj} objects of extents / fps")
+    o = int(out_res)
+    res = {}
+    for k in want:
+        dt, ch = ROI_TARGET_KEYS[k]
+        shape = (n, o, o) if ch is None else (n, ch, o, o)
+        if out is not None and k in out:
+            dev_ptr(out[k], dt, f"out[{k!r}]")
+            if tuple(out[k].shape) != shape:
+                raise RuntimeError(f"{what}: out[{k!r}] must have shape {shape}, got {tuple(out[k].shape)}")
+            res[k] = out[k]
+        else:
+            res[k] = torch.empty(shape, dtype=dt, device=dev)
+    for x, name, cnt in ((centers, "centers", 2 * n), (scales, "scales", n)):
+        dev_ptr(x, torch.float64, name)
+        if x.numel() != cnt:
+            raise RuntimeError(f"{what}: {name} must hold {cnt} values, got {tuple(x.shape)}")
+    if n == 0:
+        return res
+    # one upload: the offsets i64[n], then as i32 the boxes [n,4] and the columns visib, trunc, full, obj [n] each
+    i32 = np.concatenate([np.stack([bx1, by1, bx2, by2], 1).reshape(-1), *cols, obj_col]).astype(np.int32)
+    host = np.concatenate([np.where(some, off, 0), i32.view(np.int64)])
+    idx = torch.from_numpy(host).to(dev)
+    p_i32 = idx.data_ptr() + 8 * n
+    ptr = lambda k: res[k].data_ptr() if k in res else None                                    # noqa: E731
+    launch("gdrnpp_roi_train_targets", ppx if n_px else None, n_px, idx.data_ptr(), p_i32, masks.data_ptr() if masks is not None else None, n_masks,
+           p_i32 + 16 * n, p_i32 + 20 * n, p_i32 + 24 * n, H, W, centers.data_ptr(), scales.data_ptr(), p_i32 + 28 * n,
+           extents.data_ptr() if extents is not None else None, n_obj, fps.data_ptr() if fps is not None else None, F, o, int(n_bin),
+           int(bin_mask), ptr("roi_mask_obj"), ptr("roi_mask_visib"), ptr("roi_mask_trunc"), ptr("roi_mask_full"), ptr("roi_region"),
+           ptr("roi_xyz"), ptr("roi_xyz_bin"), n)
+    return res

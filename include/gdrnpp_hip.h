@@ -438,6 +438,36 @@ int gdrnpp_gt_xyz_crop(const gdrnpp_meshes* models, const int* obj, const double
                        double z_near, double z_far, unsigned short* out, long long capacity_px, int* rows, long long* totals, int n,
                        void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- per-ROI training targets — GDRN_DatasetFromList.read_data_train, core/gdrn_modeling/datasets/data_loader.py:448-612 with
+ * TRAIN.VIS off, for n ROIs over images of H x W in one launch.  Device pointers; outputs contiguous; an output passed as NULL is
+ * not wanted.  centers f64[n,2], scales f64[n], out_res: the convention of gdrnpp_crop_resize_roi; every crop is a nearest-neighbour
+ * fetch at OpenCV's source pixel, border 0.
+ *   The xyz source is what gdrnpp_gt_xyz_crop packs: xyz_packed f16 bits [xyz_px,3]; per ROI xyz_off i64 (in pixels) and
+ * xyz_box i32[n,4] = x1, y1, x2, y2 inclusive in image space, row pitch x2 - x1 + 1.  A source pixel outside the box is (0, 0, 0); a
+ * box with x2 < x1 or y2 < y1 is an instance without a covered pixel.  masks u8[n_masks,H,W] (a byte counts as 1 if it is not 0), per ROI
+ * visib_idx (-1: visib = obj), trunc_idx (-1: trunc = visib, the reference's `mask_trunc is None`), full_idx (-1: roi_mask_full all 0);
+ * masks == NULL stands for three columns of -1.  obj i32[n] indexes extents f32[n_obj,3] and fps f64[n_obj,F,3]; F = 0: no region
+ * output; F > 256 is refused (GDRNPP_ELIMIT).  n_bin = 0: no bins; bin_mask selects the mask of the bins: 0 trunc, 1 visib, 2 obj, 3 full.
+ *   roi_mask_obj f32[n,o,o] (o = out_res) = 1 where the fetched xyz has a non-zero component; roi_mask_visib = visib byte x obj;
+ * roi_mask_trunc = trunc byte x that; roi_mask_full = full byte.  roi_region i32[n,o,o] = xyz_to_region (core/utils/data_utils.py:
+ * 267-280): 1 + argmin over the object's F points of the fp64 distance sqrt((dx dx + dy dy) + dz dz), the differences taken in fp64
+ * from the float32 value of the fp16 source, nothing contracted, first index on ties, times the obj mask.  roi_xyz f32[n,3,o,o] =
+ * x / extent[c] + 0.5 in float32 (one IEEE division, one addition; the background holds 0.5).  roi_xyz_bin u8[n,3,o,o] (n_bin > 0) =
+ * trunc(clip(roi_xyz, 0, float32(0.999999)) x n_bin), n_bin where the selected mask is 0; with n_bin > 0 roi_xyz holds the clipped values,
+ * as in the reference, where the clipping works on a view of it (:579-592).  Every element of every wanted output of the n ROIs is
+ * written once, nothing else is touched, the inputs are only read: two calls are bit-equal.  Indices are device data the host cannot
+ * see: a mask index >= n_masks reads as a byte of 0, an offset outside [0, xyz_px) as a zero pixel, and a ROI whose obj is outside
+ * [0, n_obj) gets region, xyz and bins of 0.  n = 0 succeeds and launches nothing.  Refused, naming the argument, with nothing launched:
+ * n < 0, H or W <= 0 (GDRNPP_EINVAL) or >= 32767 (GDRNPP_ELIMIT), out_res <= 0 or > 4096 (ELIMIT), F < 0, n_bin outside [0, 255],
+ * bin_mask outside 0..3, bin_mask = 3 with bins wanted and masks NULL, n > 65535 (ELIMIT), and a NULL among centers, scales, xyz_packed,
+ * xyz_off, xyz_box, the three index columns when masks is given, and obj / extents / fps when an output needs them. */
+int gdrnpp_roi_train_targets(const unsigned short* xyz_packed, long long xyz_px, const long long* xyz_off, const int* xyz_box,
+                             const unsigned char* masks, int n_masks, const int* visib_idx, const int* trunc_idx, const int* full_idx,
+                             int H, int W, const double* centers, const double* scales, const int* obj, const float* extents, int n_obj,
+                             const double* fps, int F, int out_res, int n_bin, int bin_mask, float* roi_mask_obj, float* roi_mask_visib,
+                             float* roi_mask_trunc, float* roi_mask_full, int* roi_region, float* roi_xyz, unsigned char* roi_xyz_bin,
+                             int n, void* stream);
+
 /* device-to-device copy into a raw device pointer on `stream` — the transfer CppEGLRenderer::map_tensor performs with
  * cudaMemcpy2DFromArray in the reference (lib/egl_renderer/cpp/egl_renderer.cpp:262-298): attachment -> caller's tensor */
 int gdrnpp_copy_d2d(void* dst, const void* src, size_t bytes, void* stream);
