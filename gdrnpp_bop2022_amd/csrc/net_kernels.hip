@@ -74,6 +74,34 @@ __device__ __forceinline__ float group_sum_dpp(float s, int width, int lane) {
   }
   return __shfl(s, lane | (width - 1), 64);
 }
+// The same sums for the P pixels of a tile at a compile-time width of 32 or 64, one tree stage over all P chains at a time: a
+// DPP operand may not be read in the two issue slots after its VGPR was written, and the other pixels' adds fill those slots.
+// The totals are those of group_sum_dpp bit for bit (same tree, same operand order); they come back through v_readlane
+// (lane 31 / 63 hold them), not through the LDS crossbar.
+template <int WIDTH, int P>
+__device__ __forceinline__ void group_sum_dpp_tile(float (&s)[P], int lane) {
+  static_assert(WIDTH == 32 || WIDTH == 64, "group_sum_dpp_tile: one or two groups per wave");
+#pragma unroll
+  for (int p = 0; p < P; ++p) s[p] = dpp_add<0x111, 0xf>(s[p]);
+#pragma unroll
+  for (int p = 0; p < P; ++p) s[p] = dpp_add<0x112, 0xf>(s[p]);
+#pragma unroll
+  for (int p = 0; p < P; ++p) s[p] = dpp_add<0x114, 0xf>(s[p]);
+#pragma unroll
+  for (int p = 0; p < P; ++p) s[p] = dpp_add<0x118, 0xf>(s[p]);
+#pragma unroll
+  for (int p = 0; p < P; ++p) s[p] = dpp_add<0x142, 0xa>(s[p]);
+  if (WIDTH == 64) {
+#pragma unroll
+    for (int p = 0; p < P; ++p) s[p] = dpp_add<0x143, 0xc>(s[p]);
+  }
+#pragma unroll
+  for (int p = 0; p < P; ++p) {
+    const int hi = __builtin_amdgcn_readlane(__builtin_bit_cast(int, s[p]), 63);
+    const int lo = WIDTH == 64 ? hi : __builtin_amdgcn_readlane(__builtin_bit_cast(int, s[p]), 31);
+    s[p] = __builtin_bit_cast(float, (lane & 32) ? hi : lo);
+  }
+}
 
 #ifndef DW_WPE
 #define DW_WPE 2
@@ -92,17 +120,28 @@ __device__ __forceinline__ f4 fma4s(f4 a, f4 b, f4 c) {
 #else
 #define DW_FMA(a, b, c) fma4s(a, b, c)
 #endif
-template <bool FUSE_LN, bool LDS_W, int TH, int TW>
+// workgroup size of a launch: 512 threads where the LDS weight image (49 * 16 B per channel quad) allows only one workgroup per CU
+constexpr int dw_threads(int quads, bool lds_w) { return lds_w && 49 * 16 * quads > 52 * 1024 ? 512 : 256; }
+// QC: the channel-quad count C / 4 as a compile-time constant (32 / 64 / 128 / 256: the four ConvNeXt-B widths), or 0 for any
+// other C.  With QC != 0 the quad count, the workgroup size, the tiles per workgroup, the LayerNorm group width, the waves per
+// pixel and 1 / C are constants, and the LayerNorm tail is straight-line code (group_sum_dpp_tile); QC = 0 reads them from the
+// arguments.  Both forms give the same bits (tests/test_gpu_dwconv_specialised.py); option "dwconv_specialise" = 0 launches
+// QC = 0 at every width.  Measured (profiles/dwconv_ln_specialised.md): <true, true, 2, 8> at C = 512 has 1 592 instead of 4 844
+// static instructions behind the row loop; 54.0 -> 41.5 us per stage-2 launch alone (its LayerNorm 15.8 -> 4.9 us), 2.55 -> 2.13 ms
+// per step, +1.5 % ROIs/s at 128 ROIs.
+template <bool FUSE_LN, bool LDS_W, int TH, int TW, int QC>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(DW_WPE))) void dwconv7_ln_kernel(const float* __restrict__ x, const float* __restrict__ w49c,
                                                          const float* __restrict__ bias,
                                                          const float* __restrict__ ln_w,
                                                          const float* __restrict__ ln_b, float* __restrict__ y, int N,
-                                                         int H, int W, int C, float eps, int buf_rows, int y_rows) {
+                                                         int H, int W, int C_arg, float eps, int buf_rows, int y_rows) {
   __shared__ float red[TH * TW * 8];  // FUSE_LN: per-wave partials when a pixel spans several waves
   extern __shared__ float4 wlds[];    // LDS_W: [49][C/4]
   const f4* wldsv = reinterpret_cast<const f4*>(wlds);
+  const int C = QC ? 4 * QC : C_arg;
   const int Q = C >> 2;                       // channel quads per pixel
-  const int tiles_per_block = blockDim.x / Q; // >= 1 (host guarantees Q <= 256 and blockDim % Q == 0)
+  const unsigned n_threads = QC ? (unsigned)dw_threads(QC, LDS_W) : blockDim.x;
+  const int tiles_per_block = n_threads / Q;  // >= 1 (host guarantees Q <= 256 and blockDim % Q == 0)
   const int q = threadIdx.x % Q;
   const int tl = threadIdx.x / Q;
   const int tiles_x = (W + TW - 1) / TW, tiles_y = (H + TH - 1) / TH;
@@ -113,20 +152,20 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(DW_WPE))) v
     // trip: ~12 us per workgroup, the whole launch at the reference's batch sizes)
     constexpr int WMAX = 13;                  // 49 * C / 4 slots over >= 256 threads: <= 12.25 per thread for C <= 512
     const int n_slots = 49 * Q;
-    if (n_slots <= WMAX * (int)blockDim.x) {
+    if (n_slots <= WMAX * (int)n_threads) {
       float4 wtmp[WMAX];
 #pragma unroll
       for (int k = 0; k < WMAX; ++k) {
-        const int i = threadIdx.x + k * blockDim.x;
+        const int i = threadIdx.x + k * n_threads;
         if (i < n_slots) wtmp[k] = ld4(w49c + 4 * (size_t)i);
       }
 #pragma unroll
       for (int k = 0; k < WMAX; ++k) {
-        const int i = threadIdx.x + k * blockDim.x;
+        const int i = threadIdx.x + k * n_threads;
         if (i < n_slots) wlds[i] = wtmp[k];
       }
     } else {
-      for (int i = threadIdx.x; i < n_slots; i += blockDim.x) wlds[i] = ld4(w49c + 4 * (size_t)i);
+      for (int i = threadIdx.x; i < n_slots; i += n_threads) wlds[i] = ld4(w49c + 4 * (size_t)i);
     }
     __syncthreads();
   }
@@ -249,13 +288,16 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(DW_WPE))) v
           const float dx = v.x - mean[p], dy = v.y - mean[p], dz = v.z - mean[p], dw = v.w - mean[p];
           s = (dx * dx + dy * dy) + (dz * dz + dw * dw);
         }
-        if (width >= 16) {
+        if (QC >= 32) {
+          // summed below, all pixels together
+        } else if (width >= 16) {
           s = group_sum_dpp(s, width, lane);
         } else {
           for (int off = width >> 1; off >= 1; off >>= 1) s += __shfl_xor(s, off, 64);
         }
         part[p] = s;
       }
+      if constexpr (QC >= 32) group_sum_dpp_tile<(QC < 64 ? QC : 64)>(part, lane);
       if (wpt > 1) {
         __syncthreads();  // red[] of the previous round / previous tile group has been consumed by every wave
         if (lane == 0) {
@@ -291,13 +333,26 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(DW_WPE))) v
   }
   if (active) {
     float* yn = y + (size_t)n * H * W * C + 4 * q;
+    // "f16x2 rows" output (split2_common.hpp): threads q = 2k / 2k + 1 of a pixel are neighbouring lanes.  QC != 0 converts all
+    // pixels ahead of the stores: one branch per tile, and the pixels' conversions fill each other's DPP wait slots
+    constexpr bool rows_ahead = QC != 0;
+    if (rows_ahead && y_rows) {
+#pragma unroll
+      for (int i = 0; i < TH; ++i)
+#pragma unroll
+        for (int j = 0; j < TW; ++j) {
+          const f4 o = acc[i][j];
+          const uint4 u = gdrnpp::split2::f16x2_rows_quad(o.x, o.y, o.z, o.w, q & 1);
+          acc[i][j] = f4{__uint_as_float(u.x), __uint_as_float(u.y), __uint_as_float(u.z), __uint_as_float(u.w)};
+        }
+    }
 #pragma unroll
     for (int i = 0; i < TH; ++i)
 #pragma unroll
       for (int j = 0; j < TW; ++j) {
         const int oy = ty0 + i, ox = tx0 + j;
         f4 o = acc[i][j];
-        if (y_rows) {   // "f16x2 rows" output (split2_common.hpp): threads q = 2k / 2k + 1 of a pixel are neighbouring lanes
+        if (!rows_ahead && y_rows) {
           const uint4 u = gdrnpp::split2::f16x2_rows_quad(o.x, o.y, o.z, o.w, q & 1);
           o = f4{__uint_as_float(u.x), __uint_as_float(u.y), __uint_as_float(u.z), __uint_as_float(u.w)};
         }
@@ -865,9 +920,9 @@ __global__ __launch_bounds__(256) void head_tail_kernel(const float* __restrict_
   }
 }
 
-template <int TH, int TW>
-int launch_dwconv(const float* x, const float* w49c, const float* bias, const float* ln_w, const float* ln_b, float* y, int N,
-                  int H, int W, int C, float eps, int y_rows, hipStream_t st) {
+template <int TH, int TW, int QC>
+int launch_dwconv_q(const float* x, const float* w49c, const float* bias, const float* ln_w, const float* ln_b, float* y, int N,
+                    int H, int W, int C, float eps, int y_rows, hipStream_t st) {
   const int Q = C / 4;
   const long n_tiles = (long)N * ((H + TH - 1) / TH) * ((W + TW - 1) / TW);
   // buffer-load rows need the image (n) and tile row of a wave to be uniform: one tile per wave or more (Q >= 64), or the
@@ -876,62 +931,79 @@ int launch_dwconv(const float* x, const float* w49c, const float* bias, const fl
   const int buf_rows = ((Q >= 64) || (tiles_x % (64 / Q) == 0)) && (long)W * C * 4 < (1l << 31) ? 1 : 0;
   const size_t wbytes = (size_t)49 * C * sizeof(float);
   const bool fuse = ln_w && ln_b;
-  if (wbytes <= 112 * 1024 && gdrnpp::option_dwconv_lds_w()) {
-    // weights in LDS, persistent workgroups: 512 threads when the weight set allows only one workgroup per CU
-    const int threads = wbytes > 52 * 1024 ? 512 : 256;
-    const long n_groups = (n_tiles + threads / Q - 1) / (threads / Q);
-    // CU count, LDS attribute and occupancy are per (device, kernel, launch shape): looked up once, not per launch
-    struct Cfg { int dev; bool fuse; int threads; size_t wbytes; int n_cu, per_cu; };
-    static std::mutex mu;   // one cache per (TH, TW) instantiation
-    static Cfg cache[16];
-    static int n_cached = 0;
-    int dev = 0, n_cu = 0, per_cu = 1;
-    GDRNPP_HIP_TRY(hipGetDevice(&dev));
-    {
-      std::lock_guard<std::mutex> lock(mu);
-      const Cfg* hit = nullptr;
-      for (int i = 0; i < n_cached; ++i)
-        if (cache[i].dev == dev && cache[i].fuse == fuse && cache[i].threads == threads && cache[i].wbytes == wbytes) hit = &cache[i];
-      if (!hit) {
-        Cfg c{dev, fuse, threads, wbytes, 0, 1};
-        GDRNPP_HIP_TRY(hipDeviceGetAttribute(&c.n_cu, hipDeviceAttributeMultiprocessorCount, dev));
-        const void* fn = fuse ? (const void*)dwconv7_ln_kernel<true, true, TH, TW> : (const void*)dwconv7_ln_kernel<false, true, TH, TW>;
-        if (int rc = gdrnpp::ensure_dynamic_lds(fn, 112 * 1024)) return rc;
-        GDRNPP_HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&c.per_cu, fn, threads, wbytes));
-        if (c.per_cu < 1) c.per_cu = 1;
-        cache[n_cached < 16 ? n_cached++ : 15] = c;
-        hit = &cache[n_cached - 1 < 15 ? n_cached - 1 : 15];
+  // a specialised width whose weights never fit the LDS has no LDS_W instantiation
+  if constexpr (QC == 0 || 49 * 16 * QC <= 112 * 1024) {
+    if (wbytes <= 112 * 1024 && gdrnpp::option_dwconv_lds_w()) {
+      // weights in LDS, persistent workgroups: 512 threads when the weight set allows only one workgroup per CU
+      const int threads = dw_threads(Q, true);
+      const long n_groups = (n_tiles + threads / Q - 1) / (threads / Q);
+      // CU count, LDS attribute and occupancy are per (device, kernel, launch shape): looked up once, not per launch
+      struct Cfg { int dev; bool fuse; int threads; size_t wbytes; int n_cu, per_cu; };
+      static std::mutex mu;   // one cache per (TH, TW, QC) instantiation
+      static Cfg cache[16];
+      static int n_cached = 0;
+      int dev = 0, n_cu = 0, per_cu = 1;
+      GDRNPP_HIP_TRY(hipGetDevice(&dev));
+      {
+        std::lock_guard<std::mutex> lock(mu);
+        const Cfg* hit = nullptr;
+        for (int i = 0; i < n_cached; ++i)
+          if (cache[i].dev == dev && cache[i].fuse == fuse && cache[i].threads == threads && cache[i].wbytes == wbytes) hit = &cache[i];
+        if (!hit) {
+          Cfg c{dev, fuse, threads, wbytes, 0, 1};
+          GDRNPP_HIP_TRY(hipDeviceGetAttribute(&c.n_cu, hipDeviceAttributeMultiprocessorCount, dev));
+          const void* fn = fuse ? (const void*)dwconv7_ln_kernel<true, true, TH, TW, QC> : (const void*)dwconv7_ln_kernel<false, true, TH, TW, QC>;
+          if (int rc = gdrnpp::ensure_dynamic_lds(fn, 112 * 1024)) return rc;
+          GDRNPP_HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&c.per_cu, fn, threads, wbytes));
+          if (c.per_cu < 1) c.per_cu = 1;
+          cache[n_cached < 16 ? n_cached++ : 15] = c;
+          hit = &cache[n_cached - 1 < 15 ? n_cached - 1 : 15];
+        }
+        n_cu = hit->n_cu;
+        per_cu = hit->per_cu;
       }
-      n_cu = hit->n_cu;
-      per_cu = hit->per_cu;
-    }
-    long blocks = (long)n_cu * per_cu;
-    if (blocks > n_groups) blocks = n_groups;
-    if (fuse) {
-      hipLaunchKernelGGL((dwconv7_ln_kernel<true, true, TH, TW>), dim3((unsigned)blocks), dim3(threads), wbytes, st, x, w49c, bias,
-                         ln_w, ln_b, y, N, H, W, C, eps, buf_rows, y_rows);
-    } else {
-      hipLaunchKernelGGL((dwconv7_ln_kernel<false, true, TH, TW>), dim3((unsigned)blocks), dim3(threads), wbytes, st, x, w49c, bias,
-                         nullptr, nullptr, y, N, H, W, C, eps, buf_rows, y_rows);
-    }
-  } else {
-    const int tiles_per_block = 256 / Q;
-    const long blocks = (n_tiles + tiles_per_block - 1) / tiles_per_block;
-    GDRNPP_REQUIRE(blocks < (1l << 31), GDRNPP_ELIMIT, "gdrnpp_dwconv7x7_ln_nhwc: grid too large");
-    const size_t pad = (size_t)gdrnpp::option_dwconv_lds_pad();      // experiment only (0 in the product): LDS the workgroup holds without using it
-    if (pad > 64 * 1024) {
-      const void* fn = fuse ? (const void*)dwconv7_ln_kernel<true, false, TH, TW> : (const void*)dwconv7_ln_kernel<false, false, TH, TW>;
-      if (int rc = gdrnpp::ensure_dynamic_lds(fn, 112 * 1024)) return rc;
-    }
-    if (fuse) {
-      hipLaunchKernelGGL((dwconv7_ln_kernel<true, false, TH, TW>), dim3((unsigned)blocks), dim3(256), pad, st, x, w49c, bias, ln_w,
-                         ln_b, y, N, H, W, C, eps, buf_rows, y_rows);
-    } else {
-      hipLaunchKernelGGL((dwconv7_ln_kernel<false, false, TH, TW>), dim3((unsigned)blocks), dim3(256), pad, st, x, w49c, bias,
-                         nullptr, nullptr, y, N, H, W, C, eps, buf_rows, y_rows);
+      long blocks = (long)n_cu * per_cu;
+      if (blocks > n_groups) blocks = n_groups;
+      if (fuse) {
+        hipLaunchKernelGGL((dwconv7_ln_kernel<true, true, TH, TW, QC>), dim3((unsigned)blocks), dim3(threads), wbytes, st, x, w49c,
+                           bias, ln_w, ln_b, y, N, H, W, C, eps, buf_rows, y_rows);
+      } else {
+        hipLaunchKernelGGL((dwconv7_ln_kernel<false, true, TH, TW, QC>), dim3((unsigned)blocks), dim3(threads), wbytes, st, x, w49c,
+                           bias, nullptr, nullptr, y, N, H, W, C, eps, buf_rows, y_rows);
+      }
+      return gdrnpp::check_launch("gdrnpp_dwconv7x7_ln_nhwc");
     }
   }
+  const int tiles_per_block = 256 / Q;
+  const long blocks = (n_tiles + tiles_per_block - 1) / tiles_per_block;
+  GDRNPP_REQUIRE(blocks < (1l << 31), GDRNPP_ELIMIT, "gdrnpp_dwconv7x7_ln_nhwc: grid too large");
+  const size_t pad = (size_t)gdrnpp::option_dwconv_lds_pad();      // experiment only (0 in the product): LDS the workgroup holds without using it
+  if (pad > 64 * 1024) {
+    const void* fn = fuse ? (const void*)dwconv7_ln_kernel<true, false, TH, TW, QC> : (const void*)dwconv7_ln_kernel<false, false, TH, TW, QC>;
+    if (int rc = gdrnpp::ensure_dynamic_lds(fn, 112 * 1024)) return rc;
+  }
+  if (fuse) {
+    hipLaunchKernelGGL((dwconv7_ln_kernel<true, false, TH, TW, QC>), dim3((unsigned)blocks), dim3(256), pad, st, x, w49c, bias, ln_w,
+                       ln_b, y, N, H, W, C, eps, buf_rows, y_rows);
+  } else {
+    hipLaunchKernelGGL((dwconv7_ln_kernel<false, false, TH, TW, QC>), dim3((unsigned)blocks), dim3(256), pad, st, x, w49c, bias,
+                       nullptr, nullptr, y, N, H, W, C, eps, buf_rows, y_rows);
+  }
   return gdrnpp::check_launch("gdrnpp_dwconv7x7_ln_nhwc");
+}
+
+// the four ConvNeXt-B widths run the kernel compiled for their quad count; every other C, and every C under option
+// "dwconv_specialise" = 0, runs the run-time form (QC = 0)
+template <int TH, int TW>
+int launch_dwconv(const float* x, const float* w49c, const float* bias, const float* ln_w, const float* ln_b, float* y, int N,
+                  int H, int W, int C, float eps, int y_rows, hipStream_t st) {
+  if (gdrnpp::option_dwconv_specialise()) {
+    if (C == 128) return launch_dwconv_q<TH, TW, 32>(x, w49c, bias, ln_w, ln_b, y, N, H, W, C, eps, y_rows, st);
+    if (C == 256) return launch_dwconv_q<TH, TW, 64>(x, w49c, bias, ln_w, ln_b, y, N, H, W, C, eps, y_rows, st);
+    if (C == 512) return launch_dwconv_q<TH, TW, 128>(x, w49c, bias, ln_w, ln_b, y, N, H, W, C, eps, y_rows, st);
+    if (C == 1024) return launch_dwconv_q<TH, TW, 256>(x, w49c, bias, ln_w, ln_b, y, N, H, W, C, eps, y_rows, st);
+  }
+  return launch_dwconv_q<TH, TW, 0>(x, w49c, bias, ln_w, ln_b, y, N, H, W, C, eps, y_rows, st);
 }
 
 

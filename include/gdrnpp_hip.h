@@ -55,7 +55,9 @@ const char* gdrnpp_last_error(void);
  *   "dwconv_lds_w"     0 / 1       depthwise 7x7 + LayerNorm: [49][C] weights in LDS with persistent workgroups where they fit (default 1) or
  *                                   through L1 / L2 without LDS (A/B switch: which of two kernels sharing the chip yields is decided by the LDS
  *                                   a workgroup holds, profiles/r06_dwconv_shared.txt; bitwise identical)
- *   "dwconv_lds_pad"   bytes       experiment only: dynamic LDS the no-LDS form allocates without using it (default 0)
+ *   "dwconv_specialise" 0 / 1      depthwise 7x7 + LayerNorm: C = 128 / 256 / 512 / 1024 run the kernel compiled for that width (default 1) or
+ *                                   every C runs the run-time-width form (A/B switch; bitwise identical)
+ *   "dwconv_lds_pad"   bytes      experiment only: dynamic LDS the no-LDS form allocates without using it (default 0)
  *   "upconv_lowres"    0 / 1       read by the callers' routing, not by a launch: a 3x3 convolution behind a bilinear x2 upsampling runs
  *                                   as a tap GEMM at the low resolution + gdrnpp_upconv_gather_gn_nhwc (default 1) or as the upsampling
  *                                   and the convolution of the high-resolution tensor (0)
