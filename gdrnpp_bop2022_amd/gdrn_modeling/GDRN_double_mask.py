@@ -12,7 +12,10 @@ the schedule re-designed for MI355X:
 * rot6d -> R, centroid/z -> t and allocentric -> egocentric run in one HIP kernel on the device
   (``gdrnpp_pose_from_pred_centroid_z``) instead of the reference's D2H sync + per-ROI NumPy loop
   (pose_from_pred_centroid_z.py:118-154), so ``forward`` never synchronises with the host.
-  Consequence: ``out["rot"]`` is a DEVICE tensor (the reference returns a CPU tensor).
+  Consequence: ``out["rot"]`` is a DEVICE tensor (the reference returns a CPU tensor);
+* ``forward(do_loss=True)`` returns the reference's ``(out_dict, loss_dict)``: the network on PyTorch operators under autograd, the
+  pose in a differentiable torch form and the losses on the kernels of ``losses.py`` (``forward_loss``).  The optimiser is not
+  built: ``build_model_optimizer(is_test=False)`` still raises.
 """
 from __future__ import annotations
 
@@ -243,9 +246,14 @@ class GDRN_DoubleMask(nn.Module):
     def forward(self, x, gt_xyz=None, gt_xyz_bin=None, gt_mask_trunc=None, gt_mask_visib=None, gt_mask_obj=None,
                 gt_mask_full=None, gt_region=None, gt_ego_rot=None, gt_points=None, sym_infos=None, gt_trans=None,
                 gt_trans_ratio=None, roi_classes=None, roi_coord_2d=None, roi_coord_2d_rel=None, roi_cams=None,
-                roi_centers=None, roi_whs=None, roi_extents=None, resize_ratios=None, do_loss=False):
+                roi_centers=None, roi_whs=None, roi_extents=None, resize_ratios=None, do_loss=False, gt_tables=None):
         if do_loss:
-            raise NotImplementedError("training losses are out of scope of this build (SURVEY.md §2.1)")
+            return self.forward_loss(x, gt_xyz=gt_xyz, gt_xyz_bin=gt_xyz_bin, gt_mask_trunc=gt_mask_trunc, gt_mask_visib=gt_mask_visib,
+                                     gt_mask_obj=gt_mask_obj, gt_mask_full=gt_mask_full, gt_region=gt_region, gt_ego_rot=gt_ego_rot,
+                                     gt_points=gt_points, sym_infos=sym_infos, gt_trans=gt_trans, gt_trans_ratio=gt_trans_ratio,
+                                     roi_classes=roi_classes, roi_coord_2d=roi_coord_2d, roi_coord_2d_rel=roi_coord_2d_rel, roi_cams=roi_cams,
+                                     roi_centers=roi_centers, roi_whs=roi_whs, roi_extents=roi_extents, resize_ratios=resize_ratios,
+                                     gt_tables=gt_tables)
         cfg = self.cfg
         pnp_net_cfg = cfg.MODEL.POSE_NET.PNP_NET
         bs = x.shape[0]
@@ -287,6 +295,47 @@ class GDRN_DoubleMask(nn.Module):
         if cfg.TEST.USE_PNP or cfg.TEST.SAVE_RESULTS_ONLY or cfg.TEST.USE_DEPTH_REFINE:
             out_dict.update(maps)
         return out_dict
+
+    def forward_loss(self, x, *, gt_xyz=None, gt_xyz_bin=None, gt_mask_trunc=None, gt_mask_visib=None, gt_mask_obj=None, gt_mask_full=None,
+                     gt_region=None, gt_ego_rot=None, gt_points=None, sym_infos=None, gt_trans=None, gt_trans_ratio=None, roi_classes=None,
+                     roi_coord_2d=None, roi_coord_2d_rel=None, roi_cams=None, roi_centers=None, roi_whs=None, roi_extents=None,
+                     resize_ratios=None, gt_tables=None):
+        """``forward(do_loss=True)`` (GDRN_double_mask.py:215-284): -> (out_dict, loss_dict) with an empty out_dict, as the reference
+        returns them.  The pose is formed by ``losses.pose_from_pred_train`` (differentiable; ``hip_lib.pose_from_pred`` has no
+        gradient), the losses by ``losses.gdrn_loss``.  gt_points / sym_infos / roi_extents are the reference's per-ROI arguments;
+        ``gt_tables`` = dict(points f32[n_obj,P,3], sym = ``losses.sym_tables(...)``, extents f32[n_obj,3]) hands the loss per-object
+        tables indexed by ``roi_classes`` instead, without per-ROI copies.  Not carried: compute_mean_re_te, the ``vis/...`` scalars
+        (they read values back to the host) and the event storage."""
+        from . import losses
+
+        pnp_net_cfg = self.cfg.MODEL.POSE_NET.PNP_NET
+        rot_type = pnp_net_cfg.ROT_TYPE
+        if rot_type not in ("allo_rot6d", "ego_rot6d"):
+            raise NotImplementedError(f"PNP_NET.ROT_TYPE={rot_type} with do_loss: the differentiable pose covers allo_rot6d and ego_rot6d")
+        if pnp_net_cfg.TRANS_TYPE != "centroid_z":
+            raise NotImplementedError(f"PNP_NET.TRANS_TYPE={pnp_net_cfg.TRANS_TYPE} with do_loss: the differentiable pose covers centroid_z")
+        if pnp_net_cfg.Z_TYPE not in ("REL", "ABS"):
+            raise NotImplementedError(f"PNP_NET.Z_TYPE={pnp_net_cfg.Z_TYPE}")
+        assert gt_trans is not None and gt_trans_ratio is not None and gt_region is not None and (gt_xyz is not None or gt_xyz_bin is not None)
+        if torch.is_grad_enabled():
+            self._sliced_w = None       # an eval-mode slice cached without a graph would cut the output layer off from the loss
+        pred_rot_, pred_t_, maps = self.forward_maps(x, roi_classes, roi_coord_2d, roi_coord_2d_rel, roi_extents, None)
+        if torch.is_grad_enabled():
+            self._sliced_w = None       # and this call's slice carries a graph that a later forward must not reuse
+        bs = x.shape[0]
+        pred_ego_rot, pred_trans = losses.pose_from_pred_train(pred_rot_, pred_t_, roi_cams.reshape(bs, 3, 3), roi_centers, roi_whs, resize_ratios,
+                                                               z_type=pnp_net_cfg.Z_TYPE, is_allo="allo" in rot_type)
+        if gt_tables is not None:
+            assert roi_classes is not None
+            tables = dict(gt_points=gt_tables["points"], sym_infos=gt_tables.get("sym"), extents=gt_tables.get("extents"), roi_classes=roi_classes)
+        else:
+            tables = dict(gt_points=gt_points, sym_infos=sym_infos, extents=roi_extents)
+        loss_dict = losses.gdrn_loss(self.cfg, out_mask_vis=maps["mask"], out_mask_full=maps.get("full_mask"), gt_mask_trunc=gt_mask_trunc,
+                                     gt_mask_visib=gt_mask_visib, gt_mask_obj=gt_mask_obj, gt_mask_full=gt_mask_full, out_x=maps["coor_x"],
+                                     out_y=maps["coor_y"], out_z=maps["coor_z"], gt_xyz=gt_xyz, gt_xyz_bin=gt_xyz_bin, out_region=maps["region"],
+                                     gt_region=gt_region, out_rot=pred_ego_rot, gt_rot=gt_ego_rot, out_trans=pred_trans, gt_trans=gt_trans,
+                                     out_centroid=pred_t_[:, :2], out_trans_z=pred_t_[:, 2], gt_trans_ratio=gt_trans_ratio, **tables)
+        return {}, loss_dict
 
 
 def build_model_optimizer(cfg, is_test=True, model_cls=None):

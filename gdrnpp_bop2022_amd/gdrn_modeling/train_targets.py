@@ -14,7 +14,7 @@ Out of scope, each left to its owner or not carried:
   * background replacement (``replace_bg``; its truncation mask comes in as a mask like any other), colour and depth augmentation;
   * ``INPUT.SMOOTH_XYZ`` (must be off);
   * ``TRAIN.VIS``'s bilinear masks (must be off: every crop is nearest-neighbour);
-  * the losses.
+  * the losses: they consume these targets in ``gdrn_modeling.losses`` (``gdrn_loss``).
 ``MODEL.BBOX_CROP_SYN`` / ``BBOX_CROP_REAL`` are taken as off: the visible box is the record's ``xyxy``, as :468-470 overrides it."""
 from __future__ import annotations
 

@@ -150,6 +150,14 @@ SIGNATURES = {
     "gdrnpp_pack_mlp_fused_f16x2_bytes": (c_size_t, [c_int, c_int]),
     "gdrnpp_pack_mlp_fused_f16x2": (c_int, [_P, _P, _P, c_int, c_int, _P]),
     "gdrnpp_convnext_mlp_f32_fused": (c_int, [_P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, _P, _P, _P]),
+    "gdrnpp_gdrn_dense_losses_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "gdrnpp_gdrn_dense_losses": (c_int, [_P, _P, _P, c_int, _P, _P, _P, c_int, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int,
+                                         c_int, c_int, c_int, _P, _P, _P, c_size_t, _P]),
+    "gdrnpp_gdrn_dense_losses_backward": (c_int, [_P, _P, _P, c_int, _P, _P, _P, c_int, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int,
+                                                  c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "gdrnpp_gdrn_pose_losses_workspace_bytes": (c_size_t, [c_int]),
+    "gdrnpp_gdrn_pose_losses": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, _P, _P, c_int, _P, _P, _P, _P, c_int, c_int, c_int, c_int,
+                                        c_double, c_int, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
 }
 
 

@@ -1,10 +1,10 @@
 """Network-side layers outside the split GEMMs: the ConvNeXt NHWC kernels (tensors are logically NCHW with channels_last strides),
-the geometry head's tail and the Patch-PnP / point-PnP heads."""
+the geometry head's tail, the Patch-PnP / point-PnP heads and the training losses over the network's outputs."""
 from __future__ import annotations
 
 import torch
 
-from .abi import channels_last_f32, f32_ptr, launch, load, nhwc_ptr, opt_f32_ptr
+from .abi import channels_last_f32, dev_ptr, f32_ptr, launch, load, nhwc_ptr, opt_f32_ptr
 
 
 def dwconv7x7_ln(x, w49c, bias, ln_w=None, ln_b=None, eps: float = 1e-6, y_rows: bool = False):
@@ -145,3 +145,176 @@ def point_pnp_fc(ws, w_fc1, b_fc1, w_fc2, b_fc2, b: int, hw: int):
     launch("gdrnpp_point_pnp_fc", f32_ptr(ws, "workspace"), ws.numel() * 4, f32_ptr(w_fc1, "w_fc1"), f32_ptr(b_fc1, "b_fc1"), f32_ptr(w_fc2, "w_fc2"),
            f32_ptr(b_fc2, "b_fc2"), feat.data_ptr(), b, hw)
     return feat
+
+
+# ---- GDRN's training losses (csrc/gdrn_loss.hip) ----------------------------------------------------------------------------------------
+LOSS_MASKS = ("trunc", "visib", "obj", "full")     # LOSS_CFG.*_MASK_GT / MASK_LOSS_GT -> the kernels' mask selector (roi.ROI_BIN_MASKS's order)
+DENSE_XYZ_TYPES = {"L1": 0, "CE_coor": 1}
+DENSE_MASK_TYPES = {"L1": 0, "BCE": 1}
+PM_TYPES = {"L1": 0, "Smooth_L1": 1, "MSE": 2}
+DENSE_SUMS = ("x", "y", "z", "mask", "mask_full", "region", "n_xyz", "n_region")      # the f64[8] of gdrn_dense_losses
+
+
+def _dense_args(what, out_x, out_y, out_z, out_mask, out_mask_full, out_region, gt_xyz, gt_xyz_bin, gt_region, masks, xyz_type, xyz_mask,
+                mask_type, mask_gt, full_type, region_mask):
+    """The checks and the argument tuple that ``gdrn_dense_losses`` and its backward share -> (args, B, o, Cx, Cr)."""
+    for name, table, v in (("xyz_type", DENSE_XYZ_TYPES, xyz_type), ("mask_type", DENSE_MASK_TYPES, mask_type), ("full_type", DENSE_MASK_TYPES, full_type)):
+        if v not in table:
+            raise RuntimeError(f"{what}: {name} must be one of {tuple(table)}, got {v!r}")
+    for name, v in (("xyz_mask", xyz_mask), ("mask_gt", mask_gt), ("region_mask", region_mask)):
+        if v not in LOSS_MASKS:
+            raise RuntimeError(f"{what}: {name} must be one of {LOSS_MASKS}, got {v!r}")
+    maps = [("out_x", out_x), ("out_y", out_y), ("out_z", out_z), ("out_mask", out_mask), ("out_mask_full", out_mask_full), ("out_region", out_region)]
+    first = next((t for _, t in maps if t is not None), None)
+    if first is None or first.dim() != 4 or first.shape[2] != first.shape[3]:
+        raise RuntimeError(f"{what}: needs at least one map, f32[B,C,o,o]")
+    B, o = int(first.shape[0]), int(first.shape[2])
+    masks = dict(masks)
+    unknown = set(masks) - set(LOSS_MASKS)
+    if unknown:
+        raise RuntimeError(f"{what}: unknown masks {sorted(unknown)}; the names are {LOSS_MASKS}")
+    mp = []
+    for k in LOSS_MASKS:
+        m = masks.get(k)
+        if m is not None and tuple(m.shape) != (B, o, o):
+            raise RuntimeError(f"{what}: mask {k!r} must be f32[{B},{o},{o}], got {tuple(m.shape)}")
+        mp.append(opt_f32_ptr(m, f"masks[{k!r}]"))
+
+    def need_mask(term, k):
+        if masks.get(k) is None:
+            raise RuntimeError(f"{what}: the {term} term selects mask {k!r}, which is missing")
+
+    Cx = Cr = 0
+    if (out_x is None) != (out_y is None) or (out_x is None) != (out_z is None):
+        raise RuntimeError(f"{what}: out_x, out_y and out_z come together")
+    p_gt_xyz = p_gt_bin = p_gt_region = None
+    if out_x is not None:
+        Cx = int(out_x.shape[1])
+        for name, t in maps[:3]:
+            if tuple(t.shape) != (B, Cx, o, o):
+                raise RuntimeError(f"{what}: {name} must be f32[{B},{Cx},{o},{o}], got {tuple(t.shape)}")
+        need_mask("xyz", xyz_mask)
+        if xyz_type == "L1":
+            if Cx != 1:
+                raise RuntimeError(f"{what}: the L1 xyz term takes one channel per axis, got C = {Cx}")
+            if gt_xyz is None or tuple(gt_xyz.shape) != (B, 3, o, o):
+                raise RuntimeError(f"{what}: gt_xyz must be f32[{B},3,{o},{o}]")
+            p_gt_xyz = f32_ptr(gt_xyz, "gt_xyz")
+        else:
+            if not 2 <= Cx <= 256:
+                raise RuntimeError(f"{what}: the CE_coor xyz term takes 2 <= C <= 256 channels, got C = {Cx}")
+            if gt_xyz_bin is None or tuple(gt_xyz_bin.shape) != (B, 3, o, o):
+                raise RuntimeError(f"{what}: gt_xyz_bin must be u8[{B},3,{o},{o}]")
+            p_gt_bin = dev_ptr(gt_xyz_bin, torch.uint8, "gt_xyz_bin")
+    for name, t, k in (("out_mask", out_mask, mask_gt), ("out_mask_full", out_mask_full, "full")):
+        if t is not None:
+            if tuple(t.shape) != (B, 1, o, o):
+                raise RuntimeError(f"{what}: {name} must be f32[{B},1,{o},{o}], got {tuple(t.shape)}")
+            need_mask(name[4:], k)
+    if out_region is not None:
+        Cr = int(out_region.shape[1])
+        if Cr < 2 or tuple(out_region.shape) != (B, Cr, o, o):
+            raise RuntimeError(f"{what}: out_region must be f32[{B},C,{o},{o}] with C >= 2, got {tuple(out_region.shape)}")
+        if gt_region is None or tuple(gt_region.shape) != (B, o, o):
+            raise RuntimeError(f"{what}: gt_region must be i32[{B},{o},{o}]")
+        p_gt_region = dev_ptr(gt_region, torch.int32, "gt_region")
+        need_mask("region", region_mask)
+    args = (opt_f32_ptr(out_x, "out_x"), opt_f32_ptr(out_y, "out_y"), opt_f32_ptr(out_z, "out_z"), Cx, opt_f32_ptr(out_mask, "out_mask"),
+            opt_f32_ptr(out_mask_full, "out_mask_full"), opt_f32_ptr(out_region, "out_region"), Cr, p_gt_xyz, p_gt_bin, p_gt_region, *mp,
+            DENSE_XYZ_TYPES[xyz_type], LOSS_MASKS.index(xyz_mask), DENSE_MASK_TYPES[mask_type], LOSS_MASKS.index(mask_gt),
+            DENSE_MASK_TYPES[full_type], LOSS_MASKS.index(region_mask), B, o)
+    return args, B, o, Cx, Cr
+
+
+def gdrn_dense_losses(out_x, out_y, out_z, out_mask, out_mask_full, out_region, *, gt_xyz=None, gt_xyz_bin=None, gt_region=None, masks,
+                      xyz_type: str = "L1", xyz_mask: str = "visib", mask_type: str = "L1", mask_gt: str = "trunc", full_type: str = "BCE",
+                      region_mask: str = "visib"):
+    """``gdrnpp_gdrn_dense_losses``: gdrn_loss's terms over the head's maps in one pass -> (sums f64[8] in the order of ``DENSE_SUMS``,
+    bad i32[1] = targets outside [0, C), which are left out).  out_x / out_y / out_z f32[B,C,o,o] (C = 1 for "L1", n_bin + 1 for "CE_coor"),
+    out_mask / out_mask_full f32[B,1,o,o], out_region f32[B,C,o,o]; a map given as None has no term.  gt_xyz f32[B,3,o,o] or gt_xyz_bin
+    u8[B,3,o,o], gt_region i32[B,o,o], masks {name of ``LOSS_MASKS``: f32[B,o,o]}: the dtypes of ``roi_train_targets``."""
+    what = "gdrn_dense_losses"
+    args, B, o, _, _ = _dense_args(what, out_x, out_y, out_z, out_mask, out_mask_full, out_region, gt_xyz, gt_xyz_bin, gt_region, masks, xyz_type,
+                                   xyz_mask, mask_type, mask_gt, full_type, region_mask)
+    dev = next(t for t in (out_x, out_mask, out_mask_full, out_region) if t is not None).device
+    nbytes = load().gdrnpp_gdrn_dense_losses_workspace_bytes(B, o)
+    if nbytes == 0:
+        raise RuntimeError(f"{what}: B = {B}, o = {o}: too many pixels for one launch")
+    ws = torch.empty((nbytes // 8,), dtype=torch.float64, device=dev)
+    sums = torch.empty((8,), dtype=torch.float64, device=dev)
+    bad = torch.empty((1,), dtype=torch.int32, device=dev)
+    launch("gdrnpp_gdrn_dense_losses", *args, sums.data_ptr(), bad.data_ptr(), ws.data_ptr(), nbytes)
+    return sums, bad
+
+
+def gdrn_dense_losses_backward(out_x, out_y, out_z, out_mask, out_mask_full, out_region, sums, scale, *, want, gt_xyz=None, gt_xyz_bin=None,
+                               gt_region=None, masks, xyz_type: str = "L1", xyz_mask: str = "visib", mask_type: str = "L1",
+                               mask_gt: str = "trunc", full_type: str = "BCE", region_mask: str = "visib"):
+    """``gdrnpp_gdrn_dense_losses_backward``: the gradients of sum_k scale[k] * term_k with respect to the maps, recomputed from the forward's
+    inputs -> (g_x, g_y, g_z, g_mask, g_mask_full, g_region), None where ``want`` (six flags in that order) is false: no tensor is
+    allocated or written for it.  sums f64[8]: ``gdrn_dense_losses``'s result; scale f32[6] = grad_output * weight per term (x, y, z, mask,
+    full mask, region).  Both stay on the device."""
+    what = "gdrn_dense_losses_backward"
+    maps = (out_x, out_y, out_z, out_mask, out_mask_full, out_region)
+    want = tuple(bool(w) for w in want)
+    if len(want) != 6 or any(w and t is None for w, t in zip(want, maps)):
+        raise RuntimeError(f"{what}: want must hold six flags and name only maps that are given")
+    args, B, o, _, _ = _dense_args(what, out_x, out_y, out_z, out_mask, out_mask_full, out_region, gt_xyz, gt_xyz_bin, gt_region, masks, xyz_type,
+                                   xyz_mask, mask_type, mask_gt, full_type, region_mask)
+    if sums.numel() != 8 or scale.numel() != 6:
+        raise RuntimeError(f"{what}: sums f64[8] and scale f32[6], got {tuple(sums.shape)} and {tuple(scale.shape)}")
+    grads = tuple(torch.empty_like(t) if w else None for w, t in zip(want, maps))
+    launch("gdrnpp_gdrn_dense_losses_backward", *args, dev_ptr(sums, torch.float64, "sums"), f32_ptr(scale, "scale"),
+           *(g.data_ptr() if g is not None else None for g in grads))
+    return grads
+
+
+def gdrn_pose_losses(R_pred, R_gt, obj, points, *, t_pred=None, t_gt=None, sym_rots=None, sym_off=None, extents=None, pred_t_=None,
+                     gt_trans_ratio=None, gt_trans=None, symmetric: bool = False, r_only: bool = True, z_type: str = "REL",
+                     pm_type: str = "L1", beta: float = 1.0):
+    """``gdrnpp_gdrn_pose_losses``: the per-ROI terms in fp64 -> (sums f64[3] = the PM, centroid and z sums, R_gt' f32[B,3,3] = the closest
+    symmetric ground truth, dR f32[B,3,3] and dt f32[B,3] = d sums[0] / d R_pred, t_pred, dpt f32[B,3] = d sums[1] / d pred_t_[:, :2] and
+    d sums[2] / d pred_t_[:, 2]; dpt is None without pred_t_).  R_pred, R_gt f32[B,3,3|9]; obj i32[B] into points f32[n_obj,P,3], extents
+    f32[n_obj,3] (given = PM_NORM_BY_EXTENT) and sym_off i32[n_obj+1] into sym_rots f64[n_sym,3,3|9] (``pose_errors``'s layout; an empty
+    range is an asymmetric object).  t_pred / t_gt f32[B,3] are needed unless r_only; pred_t_, gt_trans_ratio, gt_trans f32[B,3]."""
+    what = "gdrn_pose_losses"
+    B = int(R_pred.shape[0])
+    if R_pred.numel() != 9 * B or R_gt.numel() != 9 * B or obj.numel() != B or B == 0:
+        raise RuntimeError(f"{what}: R_pred, R_gt f32[B,3,3] and obj i32[B] with B > 0, got {tuple(R_pred.shape)}, {tuple(R_gt.shape)}, {tuple(obj.shape)}")
+    if points.dim() != 3 or points.shape[2] != 3 or points.shape[0] == 0 or points.shape[1] == 0:
+        raise RuntimeError(f"{what}: points must be f32[n_obj,P,3], got {tuple(points.shape)}")
+    n_obj, P = int(points.shape[0]), int(points.shape[1])
+    if pm_type not in PM_TYPES or z_type not in ("REL", "ABS"):
+        raise RuntimeError(f"{what}: pm_type one of {tuple(PM_TYPES)}, z_type REL or ABS; got {pm_type!r}, {z_type!r}")
+    for name, t in (("t_pred", t_pred), ("t_gt", t_gt), ("pred_t_", pred_t_), ("gt_trans_ratio", gt_trans_ratio), ("gt_trans", gt_trans)):
+        if t is not None and tuple(t.shape) != (B, 3):
+            raise RuntimeError(f"{what}: {name} must be f32[{B},3], got {tuple(t.shape)}")
+    if not r_only and (t_pred is None or t_gt is None):
+        raise RuntimeError(f"{what}: r_only=False needs t_pred and t_gt")
+    if pred_t_ is not None and (gt_trans_ratio is None or (z_type == "ABS" and gt_trans is None)):
+        raise RuntimeError(f"{what}: pred_t_ needs gt_trans_ratio, and gt_trans with z_type ABS")
+    if extents is not None and tuple(extents.shape) != (n_obj, 3):
+        raise RuntimeError(f"{what}: extents must be f32[{n_obj},3], got {tuple(extents.shape)}")
+    sp = so = None
+    n_sym = 0
+    if symmetric:
+        if sym_rots is None or sym_off is None:
+            raise RuntimeError(f"{what}: symmetric needs sym_rots and sym_off")
+        if sym_off.numel() != n_obj + 1 or sym_rots.numel() % 9:
+            raise RuntimeError(f"{what}: sym_off must hold n_obj + 1 = {n_obj + 1} offsets into sym_rots f64[n_sym,9]")
+        n_sym = sym_rots.numel() // 9
+        sp, so = dev_ptr(sym_rots, torch.float64, "sym_rots") if n_sym else None, dev_ptr(sym_off, torch.int32, "sym_off")
+    dev = R_pred.device
+    sums = torch.empty((3,), dtype=torch.float64, device=dev)
+    R_sel = torch.empty((B, 3, 3), dtype=torch.float32, device=dev)
+    dR = torch.empty((B, 3, 3), dtype=torch.float32, device=dev)
+    dt = torch.empty((B, 3), dtype=torch.float32, device=dev)
+    dpt = torch.empty((B, 3), dtype=torch.float32, device=dev) if pred_t_ is not None else None
+    nbytes = load().gdrnpp_gdrn_pose_losses_workspace_bytes(B)
+    ws = torch.empty((nbytes // 8,), dtype=torch.float64, device=dev)
+    launch("gdrnpp_gdrn_pose_losses", f32_ptr(R_pred, "R_pred"), f32_ptr(R_gt, "R_gt"), opt_f32_ptr(t_pred, "t_pred"), opt_f32_ptr(t_gt, "t_gt"),
+           dev_ptr(obj, torch.int32, "obj"), f32_ptr(points, "points"), n_obj, P, sp, so, n_sym, opt_f32_ptr(extents, "extents"),
+           opt_f32_ptr(pred_t_, "pred_t_"), opt_f32_ptr(gt_trans_ratio, "gt_trans_ratio"), opt_f32_ptr(gt_trans, "gt_trans"),
+           1 if symmetric else 0, 1 if r_only else 0, 0 if z_type == "REL" else 1, PM_TYPES[pm_type], float(beta), B, sums.data_ptr(),
+           R_sel.data_ptr(), dR.data_ptr(), dt.data_ptr(), dpt.data_ptr() if dpt is not None else None, ws.data_ptr(), nbytes)
+    return sums, R_sel, dR, dt, dpt

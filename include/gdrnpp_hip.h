@@ -828,6 +828,59 @@ int gdrnpp_pack_pose_records(const float* R, const double* t_refined,
                              const int* obj_id, const int* roi_id, float* rec,
                              int b, void* stream);
 
+/* ---- GDRN's training losses (csrc/gdrn_loss.hip) — gdrn_loss of core/gdrn_modeling/models/GDRN_double_mask.py:287-536 ----
+ * gdrnpp_gdrn_dense_losses: the terms over the geometry head's maps, one pass.  All maps contiguous NCHW float:
+ * out_x / out_y / out_z f32[B,Cx,o,o] (Cx = 1 with xyz_type 0 = L1, 2 <= Cx <= 256 with xyz_type 1 = CE_coor; all three or none),
+ * out_mask, out_mask_full f32[B,1,o,o], out_region f32[B,Cr,o,o] (Cr >= 2); a null map = its term is absent (its sum is 0).
+ * gt_xyz f32[B,3,o,o] (L1) or gt_xyz_bin u8[B,3,o,o] (CE_coor), gt_region i32[B,o,o], the masks f32[B,o,o] of 0 / 1 (a mask that
+ * no selector names may be null).  xyz_mask, mask_gt, region_mask: 0 trunc, 1 visib, 2 obj, 3 full; mask_type, full_type: 0 = L1,
+ * 1 = BCE with logits; the full-mask term is always taken against mask_full.
+ * sums f64[8] = the numerators of x, y, z, mask, full mask, region, then the pixel counts of the xyz and the region mask:
+ *   xyz L1      sum |out m - gt m|                      xyz CE_coor / region   sum of CE(out m, target (long) m) over ALL pixels
+ *   mask L1     sum |out - gt|                          mask BCE               sum of max(x,0) - x z + log(1 + exp(-|x|))
+ * Per-pixel terms in fp32, accumulation in fp64; per-workgroup partials go to the workspace and are added in workgroup order (no
+ * floating-point atomics: equal bits on every run).  A pixel whose mask is 0 contributes log C (its logits are out * 0) and its
+ * maps are not read.  bad_targets i32[1] receives the number of (pixel, term) pairs whose masked target lies outside [0, C): such a
+ * pixel is left out of the sum.  Argument errors return GDRNPP_EINVAL / GDRNPP_ELIMIT and launch nothing. */
+size_t gdrnpp_gdrn_dense_losses_workspace_bytes(int B, int o);
+int gdrnpp_gdrn_dense_losses(const float* out_x, const float* out_y, const float* out_z, int Cx, const float* out_mask,
+                             const float* out_mask_full, const float* out_region, int Cr, const float* gt_xyz,
+                             const unsigned char* gt_xyz_bin, const int* gt_region, const float* mask_trunc, const float* mask_visib,
+                             const float* mask_obj, const float* mask_full, int xyz_type, int xyz_mask, int mask_type, int mask_gt,
+                             int full_type, int region_mask, int B, int o, double* sums, int* bad_targets, void* workspace,
+                             size_t workspace_bytes, void* stream);
+
+/* gdrnpp_gdrn_dense_losses_backward: recomputes from the inputs of the forward and writes, for every non-null grad_*, the gradient of
+ *   scale[0..2] x, y, z numerators / max(sums[6], 1) + scale[3] mask / (B o o) + scale[4] full mask / (B o o) + scale[5] region / max(sums[7], 1)
+ * with respect to that map (same shape).  sums f64[8]: the forward's result, scale f32[6]: both read on the device.
+ * L1: sign(out m - gt m) m s with sign(0) = 0; CE: (softmax - onehot) m s, 0 at a pixel with a target outside [0, C);
+ * BCE: (sigmoid(x) - z) s; mask L1: sign(out - gt) s. */
+int gdrnpp_gdrn_dense_losses_backward(const float* out_x, const float* out_y, const float* out_z, int Cx, const float* out_mask,
+                                      const float* out_mask_full, const float* out_region, int Cr, const float* gt_xyz,
+                                      const unsigned char* gt_xyz_bin, const int* gt_region, const float* mask_trunc,
+                                      const float* mask_visib, const float* mask_obj, const float* mask_full, int xyz_type, int xyz_mask,
+                                      int mask_type, int mask_gt, int full_type, int region_mask, int B, int o, const double* sums,
+                                      const float* scale, float* grad_x, float* grad_y, float* grad_z, float* grad_mask,
+                                      float* grad_mask_full, float* grad_region, void* stream);
+
+/* gdrnpp_gdrn_pose_losses: the per-ROI terms, one workgroup per ROI, fp64 inside.  R_pred, R_gt f32[B,9]; t_pred, t_gt f32[B,3]
+ * (needed with r_only = 0); obj i32[B] into points f32[n_obj,P,3], extents f32[n_obj,3] (null: no PM_NORM_BY_EXTENT) and sym_off
+ * i32[n_obj+1] into sym_rots f64[n_sym_total,9] (an empty range: an asymmetric object); pred_t_, gt_trans_ratio, gt_trans f32[B,3]
+ * (pred_t_ null: no centroid / z term).  symmetric: R_gt of a ROI is replaced by R_gt S_k of the symmetry with the smallest
+ * re(R_pred, R_gt S_k); R_gt itself is the first candidate, the comparison is a strict <, the earliest candidate wins.
+ * pm_type 0 L1, 1 Smooth_L1(beta), 2 MSE; z_type 0 REL (gt_trans_ratio[:,2]), 1 ABS (gt_trans[:,2]).
+ * sums f64[3] = sum over ROI, point, axis of loss(w (R_pred p [+ t_pred]) - w (R_gt' p [+ t_gt])) with w = 1 / max(extent) or 1,
+ * sum |pred_t_[:, :2] - gt_trans_ratio[:, :2]|, sum |pred_t_[:, 2] - gt_z|: per-ROI partials (workspace) added in ROI order.
+ * R_gt_sel f32[B,9] (may be null) = R_gt'; dR_pred f32[B,9], dt_pred f32[B,3] = d sums[0] / d R_pred, t_pred (dt_pred 0 with r_only);
+ * dpred_t_ f32[B,3] = d sums[1] / d pred_t_[:, :2] and d sums[2] / d pred_t_[:, 2].  A ROI whose obj lies outside [0, n_obj) makes
+ * sums[0] NaN and reads nothing. */
+size_t gdrnpp_gdrn_pose_losses_workspace_bytes(int B);
+int gdrnpp_gdrn_pose_losses(const float* R_pred, const float* R_gt, const float* t_pred, const float* t_gt, const int* obj,
+                            const float* points, int n_obj, int P, const double* sym_rots, const int* sym_off, int n_sym_total,
+                            const float* extents, const float* pred_t_, const float* gt_trans_ratio, const float* gt_trans, int symmetric,
+                            int r_only, int z_type, int pm_type, double beta, int B, double* sums, float* R_gt_sel, float* dR_pred,
+                            float* dt_pred, float* dpred_t_, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
