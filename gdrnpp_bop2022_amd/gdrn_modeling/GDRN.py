@@ -14,6 +14,6 @@ class GDRN(GDRN_DoubleMask):
 
 
 def build_model_optimizer(cfg, is_test=True):
-    """GDRN.py:480-567 — (model, None) for the inference build."""
+    """GDRN.py:480-567 — (model, None) for the inference build, (model, optimizer) with ``is_test=False``."""
     assert cfg.MODEL.POSE_NET.NAME == "GDRN", cfg.MODEL.POSE_NET.NAME
     return _build(cfg, is_test=is_test, model_cls=GDRN)

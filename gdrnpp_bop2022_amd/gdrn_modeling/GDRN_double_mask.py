@@ -14,8 +14,9 @@ the schedule re-designed for MI355X:
   (pose_from_pred_centroid_z.py:118-154), so ``forward`` never synchronises with the host.
   Consequence: ``out["rot"]`` is a DEVICE tensor (the reference returns a CPU tensor);
 * ``forward(do_loss=True)`` returns the reference's ``(out_dict, loss_dict)``: the network on PyTorch operators under autograd, the
-  pose in a differentiable torch form and the losses on the kernels of ``losses.py`` (``forward_loss``).  The optimiser is not
-  built: ``build_model_optimizer(is_test=False)`` still raises.
+  pose in a differentiable torch form and the losses on the kernels of ``losses.py`` (``forward_loss``);
+* ``build_model_optimizer(cfg, is_test=False)`` returns the model with the optimiser of ``cfg.SOLVER`` (``solver.py``: Ranger on one
+  multi-tensor HIP launch per step).
 """
 from __future__ import annotations
 
@@ -339,9 +340,8 @@ class GDRN_DoubleMask(nn.Module):
 
 
 def build_model_optimizer(cfg, is_test=True, model_cls=None):
-    """GDRN_double_mask.py:539-615 — returns (model, optimizer); the optimizer is None (inference build)."""
-    if not is_test:
-        raise NotImplementedError("training is out of scope of this build (SURVEY.md §2.1)")
+    """GDRN_double_mask.py:539-615 — returns (model, optimizer).  ``is_test=True``: the inference build, in eval mode, optimizer None.
+    ``is_test=False``: the model in train mode with ``solver.build_optimizer_with_params`` over the reference's parameter groups."""
     net_cfg = cfg.MODEL.POSE_NET
     init_backbone_args = copy.deepcopy(dict(net_cfg.BACKBONE.INIT_CFG))
     backbone = create_backbone(**init_backbone_args)
@@ -380,10 +380,15 @@ def build_model_optimizer(cfg, is_test=True, model_cls=None):
 
     model = (model_cls or GDRN_DoubleMask)(cfg, backbone, neck=None, geo_head_net=geo_head, pnp_net=pnp_net)
     model.eval()
+    optimizer = None
+    if not is_test:
+        from . import solver
+        optimizer = solver.build_optimizer_with_params(cfg, solver.model_param_groups(cfg, backbone, geo_head, pnp_net))
+        model.train()
     if cfg.MODEL.DEVICE != "cpu" and torch.cuda.is_available():
         model.to(torch.device(cfg.MODEL.DEVICE))
         model.to(memory_format=torch.channels_last)
-    return model, None
+    return model, optimizer
 
 
 _ALLOWED_UNEXPECTED = ("num_batches_tracked",)

@@ -1,6 +1,6 @@
 """Config surface kept from the reference (mmcv python-dict configs with ``_base_`` chains,
 configs/_base_/gdrn_base.py:1-174, configs/_base_/common_base.py:212-222) — restated as plain
-dict builders with attribute access; only keys that drive the inference hot path are carried.
+dict builders with attribute access; only keys that drive the inference hot path, the losses and the solver are carried.
 ``--opts KEY=VAL`` style overrides: ``merge_opts`` (core/utils/default_args_setup.py:91-96).
 """
 from __future__ import annotations
@@ -96,6 +96,11 @@ def gdrn_base() -> dict:
         # configs/_base_/common_base.py VAL block (the keys that name the BOP results file, test_utils.py:33-52) and EXP_ID
         # (core/utils/default_args_setup.py derives it from the config file name)
         VAL=dict(DATASET_NAME="lm", SPLIT="test", SPLIT_TYPE="", SAVE_BOP_CSV_ONLY=True),
+        # configs/_base_/common_base.py:134-176, the keys solver.py reads (BASE_LR is OPTIMIZER_CFG's lr unless set: main_gdrn.py:103)
+        SOLVER=dict(IMS_PER_BATCH=6, TOTAL_EPOCHS=160, OPTIMIZER_CFG=dict(type="RMSprop", lr=1e-4, momentum=0.0, weight_decay=0),
+                    GAMMA=0.1, LR_SCHEDULER_NAME="WarmupMultiStepLR", WARMUP_METHOD="linear", WARMUP_FACTOR=1.0 / 1000, WARMUP_ITERS=1000,
+                    ANNEAL_METHOD="step", ANNEAL_POINT=0.72, POLY_POWER=0.9, REL_STEPS=(0.5, 0.75), CLIP_GRADIENTS=dict(ENABLED=False),
+                    SET_NAN_GRAD_TO_ZERO=False),
         EXP_ID="gdrn_hip",
         DIST_PARAMS=dict(backend="nccl"),
     )
@@ -121,6 +126,10 @@ def _gdrnpp_convnext(num_classes: int) -> dict:
             ),
         ),
         TEST=dict(EVAL_PERIOD=0, VIS=False, TEST_BBOX_TYPE="est"),
+        # the solver block of every shipped convnext config (lines 34-44 of the ycbv one)
+        SOLVER=dict(IMS_PER_BATCH=48, TOTAL_EPOCHS=40, LR_SCHEDULER_NAME="flat_and_anneal", ANNEAL_METHOD="cosine", ANNEAL_POINT=0.72,
+                    OPTIMIZER_CFG=dict(_delete_=True, type="Ranger", lr=8e-4, weight_decay=0.01), WEIGHT_DECAY=0.0, WARMUP_FACTOR=0.001,
+                    WARMUP_ITERS=1000),
     )
 
 

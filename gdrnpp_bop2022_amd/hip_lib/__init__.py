@@ -26,6 +26,8 @@ from .gemm import (A_F16X2_ROWS, C_F16X2_ROWS, X3, conv2d_f32_split, conv3x3_f32
 from .net import (DENSE_MASK_TYPES, DENSE_SUMS, DENSE_XYZ_TYPES, LOSS_MASKS, PM_TYPES, POINT_PNP_TILE, ROT_DIMS, ROT_MODES, T_MODES,  # noqa: F401
                   bias_act_nhwc_, dwconv7x7_ln, gdrn_dense_losses, gdrn_dense_losses_backward, gdrn_pose_losses, groupnorm_act, head_tail_nhwc,
                   layernorm_nhwc, pnp_fc_heads, pnp_fc_heads_pose, point_pnp_fc, point_pnp_pool, stem_conv4x4_ln, upsample_bilinear2x)
+from .net import (RANGER_COEFS, RANGER_LONG_ROW, RANGER_LOOKAHEAD, RANGER_NAN_TO_NUM, RANGER_RECTIFIED, RANGER_TENSOR, RANGER_TILE,  # noqa: F401
+                  RANGER_WORK, RangerTables, ranger_plan, ranger_same_layout, ranger_step, ranger_tensor_ok)
 from .pose import (GT_INFO_COLUMNS, XYZ_CROP_COLUMNS, MeshSet, bop_errors, decode_correspondences, depth_refine, epnp_batched, epnp_ransac,  # noqa: F401
                    flow_forward, fps, gt_visibility, gt_xyz_crops, nnd_backward, nnd_forward, pack_pose_records, paste_masks_rle, pnp_iter_from_correspondences, pose_from_pred,
                    pose_errors, pose_from_pred_centroid_z, refine_kernel_name, refine_to_records, render_depth, set_refine_event_sink,

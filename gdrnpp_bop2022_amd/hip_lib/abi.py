@@ -158,6 +158,7 @@ SIGNATURES = {
     "gdrnpp_gdrn_pose_losses_workspace_bytes": (c_size_t, [c_int]),
     "gdrnpp_gdrn_pose_losses": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, _P, _P, c_int, _P, _P, _P, _P, c_int, c_int, c_int, c_int,
                                         c_double, c_int, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
+    "gdrnpp_ranger_step": (c_int, [_P, c_int, _P, c_int, _P, c_int, _P, _P]),
 }
 
 

@@ -1,7 +1,8 @@
 """Network-side layers outside the split GEMMs: the ConvNeXt NHWC kernels (tensors are logically NCHW with channels_last strides),
-the geometry head's tail, the Patch-PnP / point-PnP heads and the training losses over the network's outputs."""
+the geometry head's tail, the Patch-PnP / point-PnP heads, the training losses over the network's outputs and the optimiser step."""
 from __future__ import annotations
 
+import numpy as np
 import torch
 
 from .abi import channels_last_f32, dev_ptr, f32_ptr, launch, load, nhwc_ptr, opt_f32_ptr
@@ -318,3 +319,155 @@ def gdrn_pose_losses(R_pred, R_gt, obj, points, *, t_pred=None, t_gt=None, sym_r
            1 if symmetric else 0, 1 if r_only else 0, 0 if z_type == "REL" else 1, PM_TYPES[pm_type], float(beta), B, sums.data_ptr(),
            R_sel.data_ptr(), dR.data_ptr(), dt.data_ptr(), dpt.data_ptr() if dpt is not None else None, ws.data_ptr(), nbytes)
     return sums, R_sel, dR, dt, dpt
+
+
+# ---- Ranger optimiser step over all tensors of an optimiser (csrc/ranger.hip) ------------------------------------------------------------
+RANGER_TILE = 12288          # GDRNPP_RANGER_TILE: elements per work item (one workgroup, the piece of the gradient it holds in LDS)
+RANGER_RECTIFIED, RANGER_LOOKAHEAD, RANGER_NAN_TO_NUM = 1, 2, 4
+RANGER_COEFS = ("beta1", "beta2", "one_minus_beta1", "one_minus_beta2", "eps", "alpha", "wd_lr", "step_lr")
+RANGER_TENSOR = np.dtype([(k, "<u8") for k in ("p", "g", "m", "v", "slow")] + [("numel", "<i8"), ("row_len", "<i4"), ("flags", "<i4")]
+                         + [(k, "<f4") for k in RANGER_COEFS] + [("reserved", "<i4", (2,))])
+RANGER_WORK = np.dtype([("start", "<i8"), ("tensor", "<i4"), ("count", "<i4"), ("mean_slot", "<i4"), ("reserved", "<i4")])
+RANGER_LONG_ROW = np.dtype([("row", "<i8"), ("tensor", "<i4"), ("reserved", "<i4")])
+
+
+def ranger_plan(numels, row_lens, tile: int = RANGER_TILE):
+    """The work items of ``gdrnpp_ranger_step`` for tensors of ``numels`` elements -> (work ``RANGER_WORK``[n_work], long_rows
+    ``RANGER_LONG_ROW``[n_long]).  row_len 0: pieces of ``tile`` elements.  0 < row_len <= tile: runs of whole rows, as many as fit a tile —
+    a multiple of 4 rows where 4 fit, so that every item starts on a 16-byte boundary of the tensor whatever the row length.  row_len >
+    tile: every row is a long row with a slot for its mean and is cut into pieces inside it.  Host code, no device needed."""
+    work, long_rows = [], []
+    n_long = 0
+    for t, (n, L) in enumerate(zip(numels, row_lens)):
+        n, L = int(n), int(L)
+        if n == 0:
+            continue
+        if L < 0 or (L and n % L):
+            raise RuntimeError(f"ranger_plan: tensor {t}: row_len {L} does not divide numel {n}")
+        slot = None
+        if L == 0:
+            start = np.arange(0, n, tile, dtype=np.int64)
+            count = np.minimum(tile, n - start)
+        elif L <= tile:
+            per = tile // L
+            per -= per % 4 if per >= 4 else 0
+            start = np.arange(0, n, per * L, dtype=np.int64)
+            count = np.minimum(per * L, n - start)
+        else:
+            rows = n // L
+            inner = np.arange(0, L, tile, dtype=np.int64)
+            start = (np.arange(rows, dtype=np.int64)[:, None] * L + inner[None, :]).reshape(-1)
+            count = np.tile(np.minimum(tile, L - inner), rows)
+            slot = np.repeat(np.arange(n_long, n_long + rows, dtype=np.int64), len(inner))
+            lr = np.zeros(rows, RANGER_LONG_ROW)
+            lr["row"], lr["tensor"] = np.arange(rows), t
+            long_rows.append(lr)
+            n_long += rows
+        w = np.zeros(len(start), RANGER_WORK)
+        w["start"], w["tensor"], w["count"], w["mean_slot"] = start, t, count, -1 if slot is None else slot
+        work.append(w)
+    return (np.concatenate(work) if work else np.zeros(0, RANGER_WORK),
+            np.concatenate(long_rows) if long_rows else np.zeros(0, RANGER_LONG_ROW))
+
+
+class RangerTables:
+    """What one optimiser keeps between steps for ``ranger_step``: per layout (the numels and row lengths of the tensors that have a
+    gradient) the work items on the device, the device copy of the per-tensor table, and pinned staging buffers for its upload.  A staging
+    buffer is written again only after the event recorded behind its copy has completed (``query``, never a wait: if none is free, another
+    one is allocated), so a step neither waits for the device nor disturbs a copy that is still in flight."""
+
+    def __init__(self, device):
+        self.device = torch.device(device)
+        self.plans = {}          # (numels, row_lens) -> (n_work, work on the device, n_long, long rows on the device, means f32[n_long], pinned sources)
+        self.staging = []        # [pinned uint8 buffer, event recorded after its last copy]
+        self.table = None        # uint8 device buffer of the per-tensor table
+        self.uploads = 0         # asynchronous table copies issued (one per step)
+
+    def close(self):
+        """Wait for the device and drop the tables and the staging buffers (their memory goes back to torch's allocators here and now)."""
+        torch.cuda.synchronize(self.device)
+        self.plans, self.staging, self.table = {}, [], None
+
+    def _pinned(self, nbytes):
+        for slot in self.staging:
+            if slot[0].numel() >= nbytes and slot[1].query():
+                return slot
+        slot = [torch.empty((max(nbytes, 4096),), dtype=torch.uint8, pin_memory=True), torch.cuda.Event()]
+        self.staging.append(slot)
+        return slot
+
+    def _upload(self, host_bytes, dst):
+        """One asynchronous host-to-device copy of ``host_bytes`` (uint8 ndarray) through a free pinned buffer."""
+        slot = self._pinned(host_bytes.size)
+        slot[0].numpy()[:host_bytes.size] = host_bytes
+        dst[:host_bytes.size].copy_(slot[0][:host_bytes.size], non_blocking=True)
+        slot[1].record()
+
+    def plan(self, numels, row_lens):
+        key = (tuple(numels), tuple(row_lens))
+        hit = self.plans.get(key)
+        if hit is None:
+            work, long_rows = ranger_plan(numels, row_lens)
+            dev = []
+            for a in (work, long_rows):
+                d = torch.empty((max(a.nbytes, 16),), dtype=torch.uint8, device=self.device)
+                if a.nbytes:
+                    self._upload(a.view(np.uint8).reshape(-1), d)
+                dev.append(d)
+            means = torch.empty((max(len(long_rows), 1),), dtype=torch.float32, device=self.device)
+            hit = self.plans[key] = (len(work), dev[0], len(long_rows), dev[1], means)
+        return hit
+
+
+def ranger_tensor_ok(t, like=None) -> bool:
+    """Whether ``ranger_step`` takes ``t``: an fp32 device tensor that is dense with dimension 0 outermost (contiguous, or 4-D
+    channels_last: a row of numel / shape[0] elements is one run of memory either way) and, given ``like``, laid out as ``like`` is."""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or t.is_sparse:
+        return False
+    if not (t.is_contiguous() or (t.dim() == 4 and t.is_contiguous(memory_format=torch.channels_last))):
+        return False
+    return like is None or (t.shape == like.shape and t.device == like.device and ranger_same_layout(t, like))
+
+
+def ranger_same_layout(t, like) -> bool:
+    """Equal strides wherever a dimension has more than one element (the stride of a dimension of one element places nothing: a [C,1,7,7]
+    weight is contiguous and channels_last at once, and torch reports either set of strides for it)."""
+    a, b = t.stride(), like.stride()
+    return a == b or all(x == y for x, y, n in zip(a, b, like.shape) if n > 1)
+
+
+def ranger_step(tables: RangerTables, params, grads, exp_avgs, exp_avg_sqs, slows, row_lens, flags, coefs, validate: bool = True):
+    """``gdrnpp_ranger_step``: one Ranger step of every listed tensor, in place, in one launch (two with centralised rows longer than
+    ``RANGER_TILE``).  Five lists of f32 device tensors, tensor i of every list laid out alike (``ranger_tensor_ok``); row_lens[i] = numel / shape[0] where the gradient is
+    centralised, else 0; flags[i] = RANGER_RECTIFIED | RANGER_LOOKAHEAD | RANGER_NAN_TO_NUM; coefs[i] = the eight numbers of
+    ``RANGER_COEFS``, rounded to fp32 here.  The per-tensor table is rebuilt on the host and uploaded with one asynchronous copy on the
+    current stream; nothing is read back and nothing waits.  ``validate=False`` is for a caller that has just held every tensor to
+    ``ranger_tensor_ok`` itself (``solver.Ranger``): the per-tensor checks are the larger part of this function's host time."""
+    n = len(params)
+    if not (len(grads) == len(exp_avgs) == len(exp_avg_sqs) == len(slows) == len(row_lens) == len(flags) == len(coefs) == n):
+        raise RuntimeError("ranger_step: the per-tensor lists differ in length")
+    if n == 0:
+        return
+    host = np.zeros(n, RANGER_TENSOR)
+    numels = [int(p.numel()) for p in params]
+    for field, ts in (("p", params), ("g", grads), ("m", exp_avgs), ("v", exp_avg_sqs), ("slow", slows)):
+        if validate:
+            for i, t in enumerate(ts):
+                if not ranger_tensor_ok(t, params[i]) or t.device != tables.device:
+                    raise RuntimeError(f"ranger_step: {field}[{i}] must be a dense float32 tensor on {tables.device}, shaped and laid out as p[{i}] "
+                                       f"{tuple(params[i].shape)} is")
+        host[field] = [t.data_ptr() for t in ts]
+    host["numel"], host["row_len"], host["flags"] = numels, row_lens, flags
+    c = np.asarray(coefs, dtype=np.float64).reshape(n, len(RANGER_COEFS)).astype(np.float32)
+    for j, k in enumerate(RANGER_COEFS):
+        host[k] = c[:, j]
+    n_work, work, n_long, long_rows, means = tables.plan(numels, [int(L) for L in row_lens])
+    if n_work == 0:
+        return
+    nbytes = host.nbytes
+    if tables.table is None or tables.table.numel() < nbytes:
+        tables.table = torch.empty((2 * nbytes,), dtype=torch.uint8, device=tables.device)
+    tables._upload(host.view(np.uint8).reshape(-1), tables.table)
+    tables.uploads += 1
+    launch("gdrnpp_ranger_step", tables.table.data_ptr(), n, work.data_ptr(), n_work, long_rows.data_ptr() if n_long else None, n_long,
+           means.data_ptr() if n_long else None)

@@ -881,6 +881,52 @@ int gdrnpp_gdrn_pose_losses(const float* R_pred, const float* R_gt, const float*
                             int r_only, int z_type, int pm_type, double beta, int B, double* sums, float* R_gt_sel, float* dR_pred,
                             float* dt_pred, float* dpred_t_, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- Ranger optimiser step over every tensor of an optimiser (csrc/ranger.hip) — step() of lib/torch_utils/solver/ranger.py:111-200 ----
+ * One launch updates all tensors (a second, earlier launch forms the row means of centralised rows longer than a tile).  Three DEVICE
+ * tables, built by the caller:
+ *   tensors    one entry per tensor with a gradient: the five f32 arrays of numel elements (slow is touched only with LOOKAHEAD), row_len
+ *              = numel / shape[0] where the gradient is centralised (mean over all dimensions but the first subtracted), 0 where not,
+ *              and the step's coefficients as fp32: wd_lr = -weight_decay * lr (0 = no decay), step_lr = -step_size * lr.
+ *   work       the tensors cut into items of at most GDRNPP_RANGER_TILE elements, one workgroup each.  An item of a centralised tensor
+ *              with row_len <= GDRNPP_RANGER_TILE covers whole rows (start and count multiples of row_len) and has mean_slot -1; a longer
+ *              row is cut into items that lie inside it, with mean_slot = the row's index in long_rows.  Other tensors: mean_slot -1.
+ *   long_rows  the rows longer than a tile; long_means f32[n_long_rows] is scratch for their means.
+ * Per element, in fp32 with every product and sum rounded on its own:
+ *   g  = nan_to_num(g, 0, 1e5, -1e5) with NAN_TO_NUM, written back to the gradient;  g -= row mean (sum in fp64, fixed order)
+ *   v  = v beta2 + ((1 - beta2) g) g;   m = m beta1 + (1 - beta1) g;   p += wd_lr p  (wd_lr != 0)
+ *   p += step_lr (m / (sqrt(v) + eps)) with RECTIFIED, p += step_lr m without;   LOOKAHEAD: slow += alpha (p - slow), p = slow.
+ * The tables are not validated (they live on the device): an item must lie inside its tensor.  A count above the tile is cut to it. */
+#define GDRNPP_RANGER_TILE 12288
+#define GDRNPP_RANGER_RECTIFIED 1
+#define GDRNPP_RANGER_LOOKAHEAD 2
+#define GDRNPP_RANGER_NAN_TO_NUM 4
+typedef struct gdrnpp_ranger_tensor {
+  float* p;
+  float* g;
+  float* m;
+  float* v;
+  float* slow;
+  long long numel;
+  int row_len;
+  int flags;
+  float beta1, beta2, one_minus_beta1, one_minus_beta2, eps, alpha, wd_lr, step_lr;
+  int reserved[2];
+} gdrnpp_ranger_tensor; /* 96 bytes */
+typedef struct gdrnpp_ranger_work {
+  long long start;
+  int tensor;
+  int count;
+  int mean_slot;
+  int reserved;
+} gdrnpp_ranger_work; /* 24 bytes */
+typedef struct gdrnpp_ranger_long_row {
+  long long row;
+  int tensor;
+  int reserved;
+} gdrnpp_ranger_long_row; /* 16 bytes */
+int gdrnpp_ranger_step(const gdrnpp_ranger_tensor* tensors, int n_tensors, const gdrnpp_ranger_work* work, int n_work,
+                       const gdrnpp_ranger_long_row* long_rows, int n_long_rows, float* long_means, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
