@@ -7,7 +7,7 @@ non-zero status, a ``RuntimeError`` is raised (reference behavio
 ``TORCH_CHECK`` -> ``RuntimeError``, ransac_voting.cpp:7-19).
 
 This file is the namespace and nothing else.  The modules, in dependency order (a module imports only from those in front of it):
-``abi`` (signature table, loader, pointer checks, the one launch path), ``dispatch`` (kernel-choice thresholds), ``range_words``
+``abi`` (signature table, structs and constants read from the header, loader, pointer checks, the one launch path), ``dispatch`` (kernel-choice thresholds), ``range_words``
 (three-product range words and launch count), then one module per kernel family: ``gemm``, ``net``, ``pose``, ``roi``, ``yolox``.
 State that somebody assigns lives in its owner and is assigned there (``hip_lib.dispatch.SPLIT2_MIN_TILES = 1``); the three
 ``SPLIT2_*`` thresholds can be READ here, always as the owner's current value.

@@ -1,10 +1,12 @@
-"""The C ABI of ``libgdrnpp_hip.so`` (``include/gdrnpp_hip.h``): signature table, loader, pointer checks, and the one path every
-status-returning entry point is launched through (``launch``).  The only module that touches ctypes function objects."""
+"""The C ABI of ``libgdrnpp_hip.so``: signature table, structs and constants read from ``include/gdrnpp_hip.h`` at import, loader,
+pointer checks, and the one path every status-returning entry point is launched through (``launch``).  The only module that touches
+ctypes function objects."""
 from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_long, c_longlong, c_size_t, c_void_p
+import re
+from ctypes import c_char_p, c_double, c_float, c_int, c_long, c_longlong, c_size_t, c_void_p
 
 import torch
 
@@ -14,152 +16,72 @@ LIB_PATH = os.environ.get("GDRNPP_HIP_LIB", os.path.join(_PKG_DIR, "libgdrnpp_hi
 _lib = None
 
 
-class gdrnpp_meshes(ctypes.Structure):
-    _fields_ = [
-        ("verts", c_void_p),
-        ("faces", c_void_p),
-        ("vert_off", c_void_p),
-        ("face_off", c_void_p),
-        ("n_obj", c_int),
-        ("max_verts", c_int),
-        ("max_faces", c_int),
-    ]
+# every scalar type include/gdrnpp_hip.h uses.  const char* is c_char_p; any other pointer is c_void_p, which takes what the callers
+# pass: byref(struct), data_ptr() integers (of device tables too, where a typed POINTER could not be the rule) and None
+C_TYPES = {"void": None, "int": c_int, "long": c_long, "long long": c_longlong, "float": c_float, "double": c_double, "size_t": c_size_t}
 
 
-class gdrnpp_roi_table(ctypes.Structure):
-    _fields_ = [(k, c_void_p) for k in ("center64", "scale64", "im_idx", "roi_cls", "roi_cam", "roi_center", "roi_wh", "scale",
-                                        "resize_ratio", "roi_extent", "score", "roi_id")]
+def _ctype(spelling: str, decl: str, strings: bool = True):
+    """The ctypes type of one type as the header spells it (``strings``: const char* is a string, as in a prototype, or a plain
+    pointer, as in a struct).  ``decl`` is quoted when the type is not one of ``C_TYPES``."""
+    t = " ".join(spelling.replace("*", " * ").split())
+    if strings and t == "const char *":
+        return c_char_p
+    if re.fullmatch(r"[\w ]+( \*)+", t):
+        return c_void_p
+    if t.removeprefix("const ") not in C_TYPES:
+        raise ValueError(f"gdrnpp_hip.h: unknown type {t!r} in {' '.join(decl.split())!r}: abi.C_TYPES has no ctypes type for it")
+    return C_TYPES[t.removeprefix("const ")]
 
 
-# name -> (restype, argtypes); must list every symbol of include/gdrnpp_hip.h
-_P = c_void_p
-SIGNATURES = {
-    "gdrnpp_version": (c_int, []),
-    "gdrnpp_set_option": (c_int, [c_char_p, c_int]),
-    "gdrnpp_get_option": (c_int, [c_char_p, POINTER(c_int)]),
-    "gdrnpp_copy_d2d": (c_int, [_P, _P, c_size_t, _P]),
-    "gdrnpp_epnp_ransac_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
-    "gdrnpp_epnp_ransac": (c_int, [_P, _P, _P, c_int, _P, _P, c_int, c_int, c_float, c_double, _P, _P, _P, _P, _P,
-                                   c_int, _P, c_size_t, _P]),
-    "gdrnpp_epnp_batched": (c_int, [_P, _P, c_int, _P, _P, _P, _P, c_int, _P]),
-    "gdrnpp_last_error": (c_char_p, []),
-    "farthest_point_sampling": (None, [_P, _P, c_int, c_int]),
-    "farthest_point_sampling_init_center": (None, [_P, _P, c_int, c_int]),
-    "uncertainty_pnp": (None, [_P, _P, _P, _P, _P, _P, c_int]),
-    "gdrnpp_fps_workspace_bytes": (c_size_t, [c_int, c_int]),
-    "gdrnpp_fps": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P, _P]),
-    "gdrnpp_nnd_forward": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, _P]),
-    "gdrnpp_nnd_backward": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, _P]),
-    "gdrnpp_generate_hypothesis": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, _P]),
-    "gdrnpp_voting_for_hypothesis": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_float, _P]),
-    "gdrnpp_generate_hypothesis_vanishing_point": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, _P]),
-    "gdrnpp_voting_for_hypothesis_vanishing_point": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_float, _P]),
-    "gdrnpp_vote_count": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_float, c_int, _P]),
-    "gdrnpp_uncertainty_pnp_batched": (c_int, [_P, _P, _P, _P, _P, _P, _P, c_int, c_int, _P]),
-    "gdrnpp_pnp_iter_from_correspondences": (c_int, [_P, _P, _P, c_int, _P, _P, _P, _P, _P, _P, c_int, _P]),
-    "gdrnpp_decode_correspondences": (
-        c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_float, _P]),
-    "gdrnpp_pose_from_pred_centroid_z": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, _P]),
-    "gdrnpp_zoom_K": (c_int, [_P, _P, _P, _P, c_int, c_float, _P]),
-    "gdrnpp_render_depth": (
-        c_int, [POINTER(gdrnpp_meshes), _P, _P, _P, _P, _P, _P, c_int, c_int, c_float, c_float, _P]),
-    "gdrnpp_depth_refine_workspace_bytes": (c_size_t, [POINTER(gdrnpp_meshes), c_int]),
-    "gdrnpp_depth_refine": (
-        c_int, [POINTER(gdrnpp_meshes), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_float,
-                c_int, c_int, c_float, c_float, _P, c_size_t, _P]),
-    "gdrnpp_refine_to_records": (
-        c_int, [POINTER(gdrnpp_meshes), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int,
-                c_float, c_int, c_int, c_float, c_float, _P, c_size_t, _P]),
-    "gdrnpp_pose_errors_workspace_bytes": (c_size_t, [POINTER(gdrnpp_meshes), c_int]),
-    "gdrnpp_pose_errors": (c_int, [POINTER(gdrnpp_meshes), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, _P, c_size_t, _P]),
-    "gdrnpp_bop_errors_workspace_bytes": (c_size_t, [POINTER(gdrnpp_meshes), _P, c_int]),
-    "gdrnpp_bop_errors": (c_int, [POINTER(gdrnpp_meshes), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, _P, c_size_t, _P]),
-    "gdrnpp_sym_errors_workspace_bytes": (c_size_t, [POINTER(gdrnpp_meshes), _P, c_int]),
-    "gdrnpp_sym_errors": (c_int, [POINTER(gdrnpp_meshes), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, _P, c_size_t, _P]),
-    "gdrnpp_vsd_counts_workspace_bytes": (c_size_t, [POINTER(gdrnpp_meshes), c_int]),
-    "gdrnpp_vsd_counts": (c_int, [POINTER(gdrnpp_meshes), _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, _P, c_int, c_float,
-                                  c_double, c_double, _P, c_int, _P, c_size_t, _P]),
-    "gdrnpp_gt_visibility_workspace_bytes": (c_size_t, [POINTER(gdrnpp_meshes), c_int]),
-    "gdrnpp_gt_visibility": (c_int, [POINTER(gdrnpp_meshes), _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_float, c_double,
-                                     c_double, _P, _P, _P, c_int, _P, c_size_t, _P]),
-    "gdrnpp_gt_xyz_crop_workspace_bytes": (c_size_t, [POINTER(gdrnpp_meshes), c_int]),
-    "gdrnpp_gt_xyz_crop": (c_int, [POINTER(gdrnpp_meshes), _P, _P, _P, _P, c_int, c_int, c_double, c_double, _P, c_longlong, _P, _P, c_int,
-                                   _P, c_size_t, _P]),
-    "gdrnpp_roi_train_targets": (c_int, [_P, c_longlong, _P, _P, _P, c_int, _P, _P, _P, c_int, c_int, _P, _P, _P, _P, c_int, _P, c_int, c_int,
-                                         c_int, c_int, _P, _P, _P, _P, _P, _P, _P, c_int, _P]),
-    "gdrnpp_pose_from_pred": (c_int, [_P, c_int, _P, c_int, _P, _P, _P, _P, _P, _P, c_int, c_int, _P]),
-    "gdrnpp_debug_refine_profile": (c_int, [_P]),
-    "gdrnpp_pack_weight_bf16x3": (c_int, [_P, _P, c_int, c_int, _P]),
-    "gdrnpp_linear_f32_split": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P]),
-    "gdrnpp_linear_f32_split_grouped": (c_int, [_P, _P, _P, _P, c_int, c_int, _P, c_int, c_int, c_int, c_int, _P]),
-    "gdrnpp_stem_conv4x4_ln": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_float, _P]),
-    "gdrnpp_head_tail_nhwc": (c_int, [_P, c_int, _P, _P, _P, _P, c_int, c_int, c_int, _P]),
-    "gdrnpp_linear_f32_splitk_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
-    "gdrnpp_linear_f32_splitk": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, c_size_t, _P]),
-    "gdrnpp_conv2d_f32_split": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
-    "gdrnpp_conv3x3_f32_split": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
-    "gdrnpp_roi_align": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_int, c_int, _P]),
-    "gdrnpp_conv2d_f32_splitk_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
-    "gdrnpp_conv2d_f32_splitk": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P,
-                                         c_size_t, _P]),
-    "gdrnpp_roi_pool": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_float, _P]),
-    "gdrnpp_debug_stream_read": (c_int, [_P, c_size_t, c_int, _P, c_int, _P]),
-    "gdrnpp_debug_spin": (c_int, [c_int, _P]),
-    "gdrnpp_crop_resize_roi": (
-        c_int, [_P, _P, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, _P, _P, _P]),
-    "gdrnpp_yolox_postprocess_workspace_bytes": (c_size_t, [c_int, c_int]),
-    "gdrnpp_yolox_postprocess": (c_int, [_P, c_int, c_int, c_int, c_float, c_float, c_int, _P, _P, c_int, _P, c_size_t, _P]),
-    "gdrnpp_conv_bias_act_f32": (c_int, [_P, c_int, c_int, _P, c_int, _P, _P, c_int, c_int, _P, c_int, c_int, c_long, c_long, c_int, c_int,
-                                         c_int, c_int, c_int, c_int, c_int, c_int, c_float, _P]),
-    "gdrnpp_yolox_focus": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
-    "gdrnpp_spp_maxpool_5_9_13": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
-    "gdrnpp_yolox_letterbox": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, c_int, c_int, c_int, c_int, c_int, _P]),
-    "gdrnpp_rois_from_dets_workspace_bytes": (c_size_t, [c_int, c_int]),
-    "gdrnpp_rois_from_dets": (c_int, [_P, _P, c_int, c_int, c_int, c_float, c_int, c_int, c_double, c_int, _P, c_int, _P, c_double, c_int,
-                                      c_int, _P, _P, _P, _P, c_size_t, _P]),
-    "gdrnpp_upsample_nearest2x_slice": (c_int, [_P, c_int, c_int, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
-    "gdrnpp_paste_masks_rle": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_float, _P, _P, c_int, _P]),
-    "gdrnpp_flow_forward": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, _P]),
-    "gdrnpp_pack_pose_records": (c_int, [_P, _P, _P, _P, _P, _P, _P, c_int, _P]),
-    "gdrnpp_dwconv7x7_ln_nhwc": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_float, _P]),
-    "gdrnpp_dwconv7x7_ln_nhwc_rows": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_float, c_int, _P]),
-    "gdrnpp_layernorm_nhwc": (c_int, [_P, _P, _P, _P, c_long, c_int, c_float, _P]),
-    "gdrnpp_upsample_bilinear2x_nhwc": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P]),
-    "gdrnpp_groupnorm_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
-    "gdrnpp_groupnorm_act_nhwc": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_float, c_int, _P]),
-    "gdrnpp_bias_act_nhwc": (c_int, [_P, _P, _P, _P, c_long, c_int, c_int, _P]),
-    "gdrnpp_deconv_col2im_nhwc": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
-    "gdrnpp_deconv_col2im_gn_nhwc": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
-    "gdrnpp_pnp_fc_heads": (c_int, [_P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, _P]),
-    "gdrnpp_pnp_fc_heads_pose": (c_int, [_P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, c_int, _P]),
-    "gdrnpp_point_pnp_workspace_bytes": (c_size_t, [c_int, c_int]),
-    "gdrnpp_point_pnp_pool": (c_int, [_P, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, _P, c_size_t, _P]),
-    "gdrnpp_point_pnp_fc": (c_int, [_P, c_size_t, _P, _P, _P, _P, _P, c_int, c_int, _P]),
-    "gdrnpp_upconv_gather_partials": (c_int, [c_int, c_int, c_int]),
-    "gdrnpp_upconv_gather_gn_nhwc": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
-    "gdrnpp_conv3x3_gnstats_partials": (c_int, [c_int, c_int]),
-    "gdrnpp_conv3x3_f32_split_gnstats": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
-    "gdrnpp_groupnorm_apply_nhwc": (c_int, [_P, _P, c_int, _P, _P, _P, c_int, c_int, c_int, c_int, c_float, c_int, _P]),
-    "gdrnpp_pack_weight_f16x2_bytes": (c_size_t, [c_int, c_int]),
-    "gdrnpp_pack_weight_f16x2": (c_int, [_P, _P, c_int, c_int, _P]),
-    "gdrnpp_linear_f32_split2": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P]),
-    "gdrnpp_linear_f32_split2_rows": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P]),
-    "gdrnpp_conv3x3_f32_split2": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P]),
-    "gdrnpp_conv2d_f32_split2": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P]),
-    "gdrnpp_split2_range_word": (c_int, [_P, c_int, _P]),
-    "gdrnpp_pack_mlp_fused_f16x2_bytes": (c_size_t, [c_int, c_int]),
-    "gdrnpp_pack_mlp_fused_f16x2": (c_int, [_P, _P, _P, c_int, c_int, _P]),
-    "gdrnpp_convnext_mlp_f32_fused": (c_int, [_P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, _P, _P, _P]),
-    "gdrnpp_gdrn_dense_losses_workspace_bytes": (c_size_t, [c_int, c_int]),
-    "gdrnpp_gdrn_dense_losses": (c_int, [_P, _P, _P, c_int, _P, _P, _P, c_int, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int,
-                                         c_int, c_int, c_int, _P, _P, _P, c_size_t, _P]),
-    "gdrnpp_gdrn_dense_losses_backward": (c_int, [_P, _P, _P, c_int, _P, _P, _P, c_int, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int,
-                                                  c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
-    "gdrnpp_gdrn_pose_losses_workspace_bytes": (c_size_t, [c_int]),
-    "gdrnpp_gdrn_pose_losses": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, _P, _P, c_int, _P, _P, _P, _P, c_int, c_int, c_int, c_int,
-                                        c_double, c_int, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
-    "gdrnpp_ranger_step": (c_int, [_P, c_int, _P, c_int, _P, c_int, _P, _P]),
-}
+def parse_header(src: str):
+    """``include/gdrnpp_hip.h``, given as its path or its text -> (signatures ``name -> (restype, [argtypes])``, structs ``name ->
+    ctypes.Structure`` with the header's members in the header's order, defines ``name -> int``).  Regular expressions over the text
+    without its comments, and strict: a type outside ``C_TYPES``, a declaration that does not split into type, name and parameters, a
+    struct member that cannot be placed (bit-field, nested struct) or a define that is no integer raises ValueError quoting it —
+    skipping it, or guessing a pointer, would launch a kernel on a shifted argument list."""
+    if "\n" not in src:
+        if not os.path.exists(src):
+            raise RuntimeError(f"gdrnpp_bop2022_amd: C header {src} is missing — the ctypes binding is derived from it "
+                               f"(GDRNPP_HIP_HEADER names one kept elsewhere).  There is no second copy of the ABI.")
+        with open(src) as f:
+            src = f.read()
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", src, flags=re.S)
+    defines = {}
+    for name, value in re.findall(r"^[ \t]*#[ \t]*define[ \t]+(\w+)[ \t]+(\S.*?)[ \t]*$", text, re.M):
+        if not re.fullmatch(r"-?\d+|\(-?\d+\)", value):
+            raise ValueError(f"gdrnpp_hip.h: #define {name} {value}: not a decimal integer")
+        defines[name] = int(value.strip("()"))
+    text = re.sub(r'extern\s+"C"\s*\{(.*)\}', r"\1", re.sub(r"^[ \t]*#.*$", "", text, flags=re.M), flags=re.S)
+    structs, typedef = {}, r"typedef\s+struct\s+(\w+)\s*\{([^{}]*)\}\s*\1\s*;"
+    for name, body in re.findall(typedef, text):
+        fields = []
+        for member in filter(None, map(str.strip, body.split(";"))):
+            m = re.fullmatch(r"(.+?[\s*])((?:\w+(?:\[\d+\])?\s*,\s*)*\w+(?:\[\d+\])?)", member, re.S)
+            ctype = _ctype(m.group(1), member, strings=False) if m else None
+            if ctype is None:
+                raise ValueError(f"gdrnpp_hip.h: struct {name}: cannot place member {' '.join(member.split())!r}")
+            for field in m.group(2).split(","):
+                field, _, n = field.strip().rstrip("]").partition("[")
+                fields.append((field, ctype * int(n) if n else ctype))
+        structs[name] = type(name, (ctypes.Structure,), {"_fields_": fields})
+    signatures = {}
+    for decl in filter(None, map(str.strip, re.sub(typedef, "", text).split(";"))):
+        m = re.fullmatch(r"(.+?[\s*])(\w+)\s*\((.*)\)", decl, re.S)
+        params = m.group(3).split(",") if m and m.group(3).strip() not in ("", "void") else []
+        types = [re.fullmatch(r"\s*(.+?[\s*])\w+\s*", p, re.S) for p in params]
+        if not m or not all(types):
+            raise ValueError(f"gdrnpp_hip.h: cannot split {' '.join(decl.split())!r} into return type, name and named parameters")
+        args = [_ctype(t.group(1), decl) for t in types]
+        if None in args:
+            raise ValueError(f"gdrnpp_hip.h: void parameter in {' '.join(decl.split())!r}")
+        signatures[m.group(2)] = (_ctype(m.group(1), decl), args)
+    return signatures, structs, defines
+
+
+HEADER_PATH = os.environ.get("GDRNPP_HIP_HEADER", os.path.join(os.path.dirname(_PKG_DIR), "include", "gdrnpp_hip.h"))
+SIGNATURES, STRUCTS, DEFINES = parse_header(HEADER_PATH)        # once, at import
+gdrnpp_meshes, gdrnpp_roi_table = STRUCTS["gdrnpp_meshes"], STRUCTS["gdrnpp_roi_table"]
 
 
 def load(path: str | None = None) -> ctypes.CDLL:

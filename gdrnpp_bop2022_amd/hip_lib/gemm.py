@@ -5,11 +5,11 @@ from __future__ import annotations
 import torch
 
 from . import dispatch
-from .abi import channels_last_f32, dev_ptr, f32_ptr, launch, load, opt_f32_ptr
+from .abi import DEFINES, channels_last_f32, dev_ptr, f32_ptr, launch, load, opt_f32_ptr
 from .range_words import count_x3, x3_flag_ptr
 
 X3 = "_x3"   # LaunchTimer kind suffix of the three-product (fp16x2) kernels: 3 instead of 6 MFMA flops per fp32-equivalent flop
-A_F16X2_ROWS, C_F16X2_ROWS = 1, 2      # include/gdrnpp_hip.h
+A_F16X2_ROWS, C_F16X2_ROWS = DEFINES["GDRNPP_A_F16X2_ROWS"], DEFINES["GDRNPP_C_F16X2_ROWS"]
 _EPILOGUES = {"none": 0, "gelu": 1, "scale_res": 2}
 
 

@@ -5,7 +5,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from .abi import channels_last_f32, dev_ptr, f32_ptr, launch, load, nhwc_ptr, opt_f32_ptr
+from .abi import DEFINES, STRUCTS, channels_last_f32, dev_ptr, f32_ptr, launch, load, nhwc_ptr, opt_f32_ptr
 
 
 def dwconv7x7_ln(x, w49c, bias, ln_w=None, ln_b=None, eps: float = 1e-6, y_rows: bool = False):
@@ -322,13 +322,10 @@ def gdrn_pose_losses(R_pred, R_gt, obj, points, *, t_pred=None, t_gt=None, sym_r
 
 
 # ---- Ranger optimiser step over all tensors of an optimiser (csrc/ranger.hip) ------------------------------------------------------------
-RANGER_TILE = 12288          # GDRNPP_RANGER_TILE: elements per work item (one workgroup, the piece of the gradient it holds in LDS)
-RANGER_RECTIFIED, RANGER_LOOKAHEAD, RANGER_NAN_TO_NUM = 1, 2, 4
-RANGER_COEFS = ("beta1", "beta2", "one_minus_beta1", "one_minus_beta2", "eps", "alpha", "wd_lr", "step_lr")
-RANGER_TENSOR = np.dtype([(k, "<u8") for k in ("p", "g", "m", "v", "slow")] + [("numel", "<i8"), ("row_len", "<i4"), ("flags", "<i4")]
-                         + [(k, "<f4") for k in RANGER_COEFS] + [("reserved", "<i4", (2,))])
-RANGER_WORK = np.dtype([("start", "<i8"), ("tensor", "<i4"), ("count", "<i4"), ("mean_slot", "<i4"), ("reserved", "<i4")])
-RANGER_LONG_ROW = np.dtype([("row", "<i8"), ("tensor", "<i4"), ("reserved", "<i4")])
+RANGER_TILE = DEFINES["GDRNPP_RANGER_TILE"]          # elements per work item (one workgroup, the piece of the gradient it holds in LDS)
+RANGER_RECTIFIED, RANGER_LOOKAHEAD, RANGER_NAN_TO_NUM = (DEFINES["GDRNPP_RANGER_" + k] for k in ("RECTIFIED", "LOOKAHEAD", "NAN_TO_NUM"))
+RANGER_TENSOR, RANGER_WORK, RANGER_LONG_ROW = (np.dtype(STRUCTS["gdrnpp_ranger_" + k]) for k in ("tensor", "work", "long_row"))
+RANGER_COEFS = tuple(k for k in RANGER_TENSOR.names if RANGER_TENSOR[k] == np.float32)      # beta1 .. step_lr, the struct's float members
 
 
 def ranger_plan(numels, row_lens, tile: int = RANGER_TILE):

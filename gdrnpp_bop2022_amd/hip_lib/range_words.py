@@ -6,10 +6,10 @@ from __future__ import annotations
 
 import torch
 
-from .abi import current_stream
+from .abi import DEFINES, current_stream
 
 X3_SLOTS = 1024
-X3_NONFINITE, X3_SMALL_ROWS = 1, 2
+X3_NONFINITE, X3_SMALL_ROWS = DEFINES["GDRNPP_SPLIT2_NONFINITE"], DEFINES["GDRNPP_SPLIT2_SMALL_ROWS"]
 _X3_FLAGS = {}   # (device index, stream handle) -> i32[X3_SLOTS]
 _X3_FLAG_OVERRIDE = None
 _X3_LAUNCHES = 0   # launches of the three-product kernels by this process (engine.inference_step: is there a flag to check?)

@@ -4,7 +4,7 @@ from __future__ import annotations
 
 import torch
 
-from .abi import dev_ptr, f32_ptr, launch, load, opt_f32_ptr
+from .abi import DEFINES, dev_ptr, f32_ptr, launch, load, opt_f32_ptr
 
 
 def yolox_postprocess(det_preds, num_classes: int, conf_thre: float = 0.7, nms_thre: float = 0.45, class_agnostic: bool = False,
@@ -24,7 +24,7 @@ def yolox_postprocess(det_preds, num_classes: int, conf_thre: float = 0.7, nms_t
     return dets, count
 
 
-CONV_ACTS = {"none": 0, "silu": 1, "sigmoid": 2, "yolox_box": 3}
+CONV_ACTS = {k: DEFINES["GDRNPP_ACT_" + k.upper()] for k in ("none", "silu", "sigmoid", "yolox_box")}
 
 
 def pack_conv_weight_kmajor(weight: torch.Tensor) -> torch.Tensor:

@@ -98,7 +98,7 @@ def test_thresholds_read_on_the_namespace_are_the_owners_current_values():
 @pytest.mark.parametrize("index", range(len(MODULES)), ids=MODULES)
 def test_modules_import_in_table_order(index):
     """Besides torch, numpy and the standard library a module imports only package modules in front of it in the table; ctypes is
-    abi's (pose and roi use it for byref and the c_double arrays)."""
+    abi's (pose and roi use it for byref and the c_double arrays), and so is re, for reading the header."""
     name, allowed = MODULES[index], set(MODULES[:index])
     outside = set()
     for node in ast.walk(_module_tree(name)):
@@ -109,7 +109,8 @@ def test_modules_import_in_table_order(index):
             outside.add(node.module.split(".")[0])
         elif isinstance(node, ast.Import):
             outside.update(a.name.split(".")[0] for a in node.names)
-    assert outside <= {"__future__", "torch", "numpy", "os", "threading"} | ({"ctypes"} if name in ("abi", "pose", "roi") else set()), outside
+    own = ({"ctypes"} if name in ("abi", "pose", "roi") else set()) | ({"re"} if name == "abi" else set())
+    assert outside <= {"__future__", "torch", "numpy", "os", "threading"} | own, outside
 
 
 def test_init_is_the_namespace_and_nothing_else():
@@ -146,9 +147,16 @@ def test_abi_has_the_launch_pattern_once():
     calls = [n.func for n in ast.walk(_module_tree("abi")) if isinstance(n, ast.Call)]
     assert sum(isinstance(f, ast.Name) and f.id == "current_stream" for f in calls) == 1         # in launch, nowhere else
     assert sum(isinstance(f, ast.Attribute) and f.attr == "launch" for f in calls) == 1          # the timer's, in launch
-    for node in ast.walk(_module_tree("abi")):          # SIGNATURES: one spelling per ctypes type
-        if isinstance(node, ast.Assign) and getattr(node.targets[0], "id", "") == "SIGNATURES":
-            assert not [n for n in ast.walk(node.value) if isinstance(n, ast.Attribute)]
+    # SIGNATURES: one ctypes type per C type — each entry is, by identity, a value of the one map (a single dict literal), or a pointer
+    abi = _mod("abi")
+    maps = [n.value for n in ast.walk(_module_tree("abi")) if isinstance(n, ast.Assign) and getattr(n.targets[0], "id", "") == "C_TYPES"]
+    assert len(maps) == 1 and isinstance(maps[0], ast.Dict) and [k.value for k in maps[0].keys] == list(abi.C_TYPES)
+    assert all(isinstance(v, (ast.Name, ast.Constant)) for v in maps[0].values)
+    allowed = list(abi.C_TYPES.values()) + [abi.c_void_p, abi.c_char_p]
+    assert len(abi.SIGNATURES) > 100
+    for name, (res, args) in abi.SIGNATURES.items():
+        assert all(any(t is a for a in allowed) for t in [res] + args), name
+        assert all(t is not None for t in args), name
 
 
 def _hip_lib_aliases(tree):
