@@ -16,33 +16,14 @@
 //   by counting the ones ordered in front of it (max_det is small); phase 2: exclusive scan of the images' counts, rows written
 //   at base + rank.  Positions are functions of the input alone: the order is deterministic, no atomics.
 #include "common.hpp"
+#include "resize_u8.hpp"
 
 #include <cstdint>
 
 namespace {
 
-enum { kModeCopy = 0, kModeArea = 1, kModeLinear = 2 };
+using namespace gdrnpp::resize_u8;          // kMode*, Tap, linear_tap: shared with replace_bg.hip
 constexpr float kPad = 114.f;
-constexpr int kCoefBits = 11, kCoefOne = 1 << kCoefBits;
-
-struct Tap { int i0, i1, c0, c1; };
-
-// OpenCV's coefficient of destination index d along an axis of n source samples
-__device__ __forceinline__ Tap linear_tap(int d, double scale, int n, bool clamp_fraction) {
-  float f = (float)((d + 0.5) * scale - 0.5);
-  int s = (int)floorf(f);
-  f -= (float)s;
-  if (clamp_fraction) {                     // columns: the index is clamped and the fraction dropped
-    if (s < 0) { f = 0.f; s = 0; }
-    if (s >= n - 1) { f = 0.f; s = n - 1; }
-  }
-  Tap t;
-  t.c0 = __float2int_rn((1.f - f) * (float)kCoefOne);
-  t.c1 = __float2int_rn(f * (float)kCoefOne);
-  t.i0 = min(max(s, 0), n - 1);             // rows: the two row indices are clamped, the coefficients stay
-  t.i1 = min(max(s + 1, 0), n - 1);
-  return t;
-}
 
 template <bool FOCUS>
 __global__ __launch_bounds__(256) void letterbox_kernel(const uint8_t* __restrict__ img, int H, int W, int rh, int rw, int mode,

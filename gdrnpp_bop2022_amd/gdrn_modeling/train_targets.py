@@ -11,7 +11,9 @@ and the mask bytes of ``hip_lib.gt_visibility``.
 Out of scope, each left to its owner or not carried:
   * the image, depth and coord-2d crops (roi_img, roi_depth, roi_coord_2d, roi_coord_2d_rel): ``hip_lib.crop_resize_roi`` serves them
     from the same centre and scale;
-  * background replacement (``replace_bg``; its truncation mask comes in as a mask like any other), colour and depth augmentation;
+  * background replacement: ``train_inputs.replace_bg_batch`` composites the full images and forms the truncation mask on the device; its
+    ``mask_trunc`` and ``trunc_idx`` come in here as ``masks`` and the instances' ``trunc_idx`` like any other mask;
+  * colour and depth augmentation;
   * ``INPUT.SMOOTH_XYZ`` (must be off);
   * ``TRAIN.VIS``'s bilinear masks (must be off: every crop is nearest-neighbour);
   * the losses: they consume these targets in ``gdrn_modeling.losses`` (``gdrn_loss``).

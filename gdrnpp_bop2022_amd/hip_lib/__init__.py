@@ -34,8 +34,8 @@ from .pose import (GT_INFO_COLUMNS, XYZ_CROP_COLUMNS, MeshSet, bop_errors, decod
                    sym_errors, uncertainty_pnp_batched, vsd_counts, vsd_errors, zoom_K)
 from .range_words import (X3_NONFINITE, X3_SLOTS, X3_SMALL_ROWS, range_words_of, split2_nonfinite, split2_range_words,  # noqa: F401
                           x3_flag_ptr, x3_flag_scope, x3_flags, x3_launch_count)
-from .roi import (ROI_BIN_MASKS, ROI_TABLE_COLUMNS, ROI_TARGET_KEYS, crop_resize_roi, roi_align, roi_pool, roi_table, roi_train_targets,  # noqa: F401
-                  rois_from_dets)
+from .roi import (REPLACE_BG_COLUMNS, REPLACE_BG_CUTS, REPLACE_BG_MODES, ROI_BIN_MASKS, ROI_TABLE_COLUMNS, ROI_TARGET_KEYS, crop_resize_roi,  # noqa: F401
+                  replace_bg, replace_bg_table, roi_align, roi_pool, roi_table, roi_train_targets, rois_from_dets)
 from .yolox import (CONV_ACTS, conv_bias_act_f32, letterbox_sizes, pack_conv_weight_kmajor, spp_maxpool_5_9_13,  # noqa: F401
                     upsample_nearest2x_slice, yolox_focus, yolox_letterbox, yolox_postprocess)
 

@@ -1,5 +1,5 @@
 """ROI preparation: crop + resize of the detections' boxes, ROIAlign / RoIPool, the device-side ROI table filled from
-detections, and the per-ROI training targets."""
+detections, the per-ROI training targets, and the background replacement of the training images they are cut from."""
 from __future__ import annotations
 
 import ctypes
@@ -242,3 +242,65 @@ def roi_train_targets(packed, table, centers, scales, im_size, *, src=None, mask
            int(bin_mask), ptr("roi_mask_obj"), ptr("roi_mask_visib"), ptr("roi_mask_trunc"), ptr("roi_mask_full"), ptr("roi_region"),
            ptr("roi_xyz"), ptr("roi_xyz_bin"), n)
     return res
+
+
+# the columns of replace_bg's host table (include/gdrnpp_hip.h); scale_x, scale_y and u hold the bits of an fp64
+REPLACE_BG_COLUMNS = ("do", "bg_off", "bg_stride", "x0", "y0", "cw", "ch", "dw", "dh", "mode", "scale_x", "scale_y", "cut", "u")
+REPLACE_BG_F64 = ("scale_x", "scale_y", "u")
+REPLACE_BG_MODES = ("copy", "area", "linear")                                 # cv2.resize's forms: mode = index
+REPLACE_BG_CUTS = ("none", "upper", "bottom", "left", "right")                # trunc_mask's branches: cut = index
+
+
+def replace_bg_table(rows):
+    """[{column: value}] -> the i64[B,14] host table of ``replace_bg``; a column left out is 0, the fp64 columns are stored as their bits."""
+    import numpy as np
+
+    table = np.zeros((len(rows), len(REPLACE_BG_COLUMNS)), np.int64)
+    for b, row in enumerate(rows):
+        unknown = set(row) - set(REPLACE_BG_COLUMNS)
+        if unknown:
+            raise RuntimeError(f"replace_bg_table: unknown columns {sorted(unknown)}; the columns are {REPLACE_BG_COLUMNS}")
+        for k, name in enumerate(REPLACE_BG_COLUMNS):
+            if name in row:
+                table[b, k] = np.float64(row[name]).view(np.int64) if name in REPLACE_BG_F64 else int(row[name])
+    return table
+
+
+def replace_bg(images, masks, bg, table, *, out_mask=None):
+    """``gdrnpp_replace_bg``: ``replace_bg`` + ``trunc_mask`` (core/base_data_loader.py:413-478) for B images in one call.
+
+    images u8[B,H,W,3] on the device, composited IN PLACE: wherever the truncated mask is 0 the pixel takes the background's, bytes of
+    kept pixels are never written.  masks u8[B,H,W] (non-zero = foreground).  bg: a flat u8 device tensor of decoded backgrounds, 3 bytes
+    per pixel, rows dense.  table: host i64[B,14] with the columns ``REPLACE_BG_COLUMNS`` (``replace_bg_table``): per image whether to
+    touch it at all, where its background's crop lies in ``bg``, the size and form of the cv2.resize, and the cut with its random draw.
+    The library checks every value the kernel indexes with before it uploads the table in one copy; a bad row raises RuntimeError.
+    out_mask: the u8[B,H,W] to write mask_trunc into (rows of images with do = 0 are left as they are); None allocates zeros.
+    -> (mask_trunc u8[B,H,W] of 0 / 1, flags i32[B]: 1 where a cut met an empty mask and was skipped).  Nothing is read back."""
+    import numpy as np
+
+    what = "replace_bg"
+    dev_ptr(images, torch.uint8, "images")
+    if images.dim() != 4 or images.shape[3] != 3:
+        raise RuntimeError(f"{what}: images must be u8[B,H,W,3], got {tuple(images.shape)}")
+    B, H, W, _ = (int(v) for v in images.shape)
+    dev_ptr(masks, torch.uint8, "masks")
+    if tuple(masks.shape) != (B, H, W):
+        raise RuntimeError(f"{what}: masks must be u8[{B},{H},{W}], got {tuple(masks.shape)}")
+    dev_ptr(bg, torch.uint8, "bg")
+    table = np.ascontiguousarray(table.cpu().numpy() if isinstance(table, torch.Tensor) else table)
+    if table.shape != (B, len(REPLACE_BG_COLUMNS)) or table.dtype != np.int64:
+        raise RuntimeError(f"{what}: table must be a host i64[{B},{len(REPLACE_BG_COLUMNS)}], got {table.shape} of {table.dtype}")
+    dev = images.device
+    if out_mask is None:
+        out_mask = torch.zeros((B, H, W), dtype=torch.uint8, device=dev)
+    dev_ptr(out_mask, torch.uint8, "out_mask")
+    if tuple(out_mask.shape) != (B, H, W):
+        raise RuntimeError(f"{what}: out_mask must be u8[{B},{H},{W}], got {tuple(out_mask.shape)}")
+    flags = torch.zeros((B,), dtype=torch.int32, device=dev)
+    if B == 0:
+        return out_mask, flags
+    nbytes = load().gdrnpp_replace_bg_workspace_bytes(B)
+    ws = torch.empty(((nbytes + 7) // 8,), dtype=torch.int64, device=dev)
+    launch("gdrnpp_replace_bg", images.data_ptr(), masks.data_ptr(), out_mask.data_ptr(), B, H, W, bg.data_ptr() if bg.numel() else None,
+           bg.numel(), table.ctypes.data, flags.data_ptr(), ws.data_ptr(), nbytes)
+    return out_mask, flags

@@ -470,6 +470,37 @@ int gdrnpp_roi_train_targets(const unsigned short* xyz_packed, long long xyz_px,
                              float* roi_mask_trunc, float* roi_mask_full, int* roi_region, float* roi_xyz, unsigned char* roi_xyz_bin,
                              int n, void* stream);
 
+/* ---- background replacement of the training loader (csrc/replace_bg.hip) — `replace_bg` and `trunc_mask` of
+ * core/base_data_loader.py:413-478 over `get_bg_image` / `get_bg_image_v2` (:480-579) and `resize_short_edge`
+ * (core/utils/data_utils.py:208-235), for B images of H x W in one call.  Device pointers: images u8[B,H,W,3], composited IN PLACE
+ * (bytes of kept pixels are never written); masks u8[B,H,W], the instance masks (non-zero = foreground); mask_trunc u8[B,H,W], written
+ * as 0 / 1; bg: bg_bytes bytes holding the decoded backgrounds, 3 bytes per pixel, rows dense; flags i32[B].
+ *   table is a HOST array i64[B,14], one row per image, with the columns (hip_lib.REPLACE_BG_COLUMNS)
+ *     0  do        0: the image and its mask_trunc are left untouched, the rest of the row is not read
+ *     1  bg_off    byte offset of the background image in bg
+ *     2  bg_stride its row length in pixels
+ *     3  x0        4  y0     origin of the crop in that image
+ *     5  cw        6  ch     size of the crop
+ *     7  dw        8  dh     size the crop is resized to; pasted top-left on zeros, so dw <= W and dh <= H
+ *     9  mode      0 copy (dw x dh == cw x ch), 1 the 2:1 area mean, 2 linear: OpenCV's forms of an 8-bit INTER_LINEAR cv2.resize
+ *    10  scale_x  11  scale_y   the bits of an fp64: OpenCV's interpolation scale, 1 / fx for cv2.resize(im, None, None, fx, fy) and
+ *                  1 / (dst / src) for cv2.resize(im, dsize); the host's arithmetic, the kernel derives none (mode 2 only)
+ *    12  cut       0 none, 1 block upper, 2 block bottom, 3 block left, 4 block right (trunc_mask's branches)
+ *    13  u         the bits of an fp64 in [0, 1): the random.random() behind trunc_mask's random.uniform (cut != 0 only)
+ * Every value the kernels index with is checked here, before the table is staged into the workspace in one copy: a crop that leaves its
+ * image or bg, dw > W, dh > H, a copy or area mean whose sizes do not agree, a mode, cut, scale or u out of range return GDRNPP_EINVAL
+ * naming the row, and nothing is launched.  H, W < 32768 and B <= 65535, or GDRNPP_ELIMIT.  B = 0 succeeds and launches nothing.
+ *   Phase 1 (images with a cut): the extents x1 <= x2 (rows) and y1 <= y2 (columns) of the non-zero mask bytes, by atomicMin / atomicMax.
+ * Phase 2, per pixel (r, c): line = int(lo + (hi - lo) u) in fp64, nothing contracted, with (lo, hi) = (x1, c_h), (c_h, x2), (y1, c_w),
+ * (c_w, y2) for cuts 1..4, c_h = 0.5 (x1 + x2), c_w = 0.5 (y1 + y2); keep = mask != 0, and r >= line, r < line, c >= line, c < line for
+ * cuts 1..4; mask_trunc = keep; where !keep the pixel becomes the resized crop's pixel at (r, c) if r < dh and c < dw, else 0.  An empty
+ * mask under a cut (the reference raises in np.min) sets flags[b] = 1 and the cut is skipped; every other flags[b] is written 0.
+ * workspace: gdrnpp_replace_bg_workspace_bytes(B) bytes of device memory, 8-byte aligned, used by this call alone. */
+size_t gdrnpp_replace_bg_workspace_bytes(int B);
+int gdrnpp_replace_bg(unsigned char* images, const unsigned char* masks, unsigned char* mask_trunc, int B, int H, int W,
+                      const unsigned char* bg, long long bg_bytes, const long long* table, int* flags, void* workspace,
+                      size_t workspace_bytes, void* stream);
+
 /* device-to-device copy into a raw device pointer on `stream` — the transfer CppEGLRenderer::map_tensor performs with
  * cudaMemcpy2DFromArray in the reference (lib/egl_renderer/cpp/egl_renderer.cpp:262-298): attachment -> caller's tensor */
 int gdrnpp_copy_d2d(void* dst, const void* src, size_t bytes, void* stream);
