@@ -50,7 +50,7 @@ class ConvNeXtBlock(nn.Module):
         self.norm = nn.LayerNorm(dim, eps=1e-6)
         self.mlp = Mlp(dim, 4 * dim)
         self.gamma = nn.Parameter(ls_init_value * torch.ones(dim))
-        self._cache = {}  # tap-major depthwise weights for the HIP kernel (inference only)
+        self._cache = {}  # tap-major depthwise weights for the HIP kernel (inference only: the training path, DwConvLN, makes its copy per forward)
 
     def forward(self, x):
         shortcut = x

@@ -129,10 +129,63 @@ def _dwconv_hip_ok(conv: nn.Conv2d, x: torch.Tensor) -> bool:
     return enabled_for(x) and conv.kernel_size == (7, 7) and conv.groups == c and c % 4 == 0 and q <= 256 and 256 % q == 0
 
 
+# Training: layers that have a backward on this library's kernels take it under autograd when this switch is on (off by default:
+# with it off a forward under enable_grad runs PyTorch's operators, as it always has).  So far: dwconv_ln.
+_TRAIN_KERNELS = False
+
+
+def set_train_kernels(flag: bool) -> None:
+    global _TRAIN_KERNELS
+    _TRAIN_KERNELS = bool(flag)
+
+
+def train_kernels() -> bool:
+    return _TRAIN_KERNELS
+
+
+class DwConvLN(torch.autograd.Function):
+    """Depthwise 7x7 + LayerNorm over C with its backward on HIP kernels (csrc/dwconv_ln_bwd.hip).  x (N,C,H,W) channels_last,
+    weight = conv.weight [C,1,7,7], w49c = its tap-major copy (a constant of the graph: the gradient goes to ``weight``) -> y
+    (N,C,H,W) channels_last, the bits of the inference forward.  The backward recomputes the convolution from x, which the block
+    keeps as its shortcut anyway; nothing else is saved but the parameters."""
+
+    @staticmethod
+    def forward(ctx, x, weight, w49c, bias, ln_weight, ln_bias, eps):
+        ctx.save_for_backward(x, weight, w49c, bias, ln_weight, ln_bias)
+        ctx.eps = eps
+        return hip_lib.dwconv7x7_ln(x, w49c, bias, ln_weight, ln_bias, eps, y_rows=False)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_y):
+        x, weight, w49c, bias, ln_weight, ln_bias = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        want = (need[0], need[1], need[3], need[4], need[5])
+        if not any(want):
+            return (None,) * 7
+        dx, dw, db, dg, dbeta = hip_lib.dwconv7x7_ln_backward(x, weight, bias, ln_weight, ln_bias, ctx.eps, _cl(grad_y), want=want, w49c=w49c)
+        return dx, dw, None, db, dg, dbeta, None
+
+
+def _dwconv_train_ok(conv: nn.Conv2d, ln: nn.LayerNorm, x: torch.Tensor) -> bool:
+    c = conv.in_channels
+    q = c // 4
+    return (_TRAIN_KERNELS and _ENABLED and torch.is_grad_enabled() and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4
+            and conv.kernel_size == (7, 7) and conv.stride == (1, 1) and conv.padding == (3, 3) and conv.dilation == (1, 1)
+            and conv.groups == c == conv.out_channels and c % 4 == 0 and q <= 256 and 256 % q == 0 and conv.bias is not None
+            and ln.elementwise_affine and ln.bias is not None and tuple(ln.normalized_shape) == (c,))
+
+
 def dwconv_ln(conv: nn.Conv2d, ln: nn.LayerNorm, x: torch.Tensor, cache: dict, y_rows: bool = False) -> torch.Tensor:
     """ConvNeXt block head: depthwise 7x7 then LayerNorm over C.  Returns the NHWC *view* [N,H,W,C].  ``y_rows``: as an "f16x2
-    rows" tensor for ``convnext_mlp(..., a_rows=True)`` (HIP path only; ``mlp_takes_rows`` says when)."""
+    rows" tensor for ``convnext_mlp(..., a_rows=True)`` (HIP path only; ``mlp_takes_rows`` says when).  With gradients enabled
+    and ``set_train_kernels(True)`` the layer is ``DwConvLN``: the inference kernel forward, HIP kernels backward."""
     c = conv.in_channels
+    if not y_rows and _dwconv_train_ok(conv, ln, x):
+        # tap-major [49, C], made per forward: the weight changes every step, and a refill of ``cache`` waits for the device twice
+        w49c = conv.weight.detach().reshape(c, 49).t().contiguous()
+        y = DwConvLN.apply(_cl(x), conv.weight, w49c, conv.bias, ln.weight, ln.bias, ln.eps)
+        return y.permute(0, 2, 3, 1)
     if _dwconv_hip_ok(conv, x):
         hit = cached(cache, "w49c", weight_tag(conv.weight), lambda: (conv.weight.detach().reshape(c, 49).t().contiguous(),),
                      conv.weight)  # tap-major [49, C]

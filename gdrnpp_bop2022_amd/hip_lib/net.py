@@ -19,6 +19,44 @@ def dwconv7x7_ln(x, w49c, bias, ln_w=None, ln_b=None, eps: float = 1e-6, y_rows:
     return y
 
 
+def dwconv7x7_ln_backward(x, weight, bias, ln_weight, ln_bias, eps: float, grad_y, want=(True,) * 5, w49c=None):
+    """``gdrnpp_dwconv7x7_ln_backward``: the gradients of ``dwconv7x7_ln(x, ...)`` (with its LayerNorm) for grad_y = dL/dy
+    -> (dx, dweight, dbias, dln_weight, dln_bias).  x, grad_y (N,C,H,W) channels_last; weight [C,1,7,7] (conv.weight) and dweight in the
+    same layout; the others f32[C].  ``want``: five flags in the order of the result — an entry is None where its flag is false, and
+    the pass only it needs is not launched.  ``w49c``: the tap-major copy [49,C] of ``weight`` when the caller has one (the forward's),
+    else it is made here.  u and the statistics are recomputed from x: nothing of the forward is needed.  Fixed summation order: two
+    calls give the same bits."""
+    what = "dwconv7x7_ln_backward"
+    want = tuple(bool(w) for w in want)
+    if len(want) != 5 or not any(want):
+        raise RuntimeError(f"{what}: want must hold five flags, at least one of them set")
+    px = nhwc_ptr(x, "x")
+    n, c, h, w = x.shape
+    if not isinstance(grad_y, torch.Tensor) or tuple(grad_y.shape) != (n, c, h, w):
+        raise RuntimeError(f"{what}: grad_y must be f32[{n},{c},{h},{w}] as x is, got {tuple(getattr(grad_y, 'shape', ()))}")
+    pg = nhwc_ptr(grad_y, "grad_y")
+    if tuple(weight.shape) != (c, 1, 7, 7):
+        raise RuntimeError(f"{what}: weight must be f32[{c},1,7,7], got {tuple(weight.shape)}")
+    for name, t in (("bias", bias), ("ln_weight", ln_weight), ("ln_bias", ln_bias)):
+        if t is None or t.numel() != c:
+            raise RuntimeError(f"{what}: {name} must be f32[{c}]")
+    if w49c is None:
+        w49c = weight.detach().reshape(c, 49).t().contiguous()
+    elif tuple(w49c.shape) != (49, c):
+        raise RuntimeError(f"{what}: w49c must be f32[49,{c}], got {tuple(w49c.shape)}")
+    pw, pb, pl = f32_ptr(w49c, "w49c"), f32_ptr(bias, "bias"), f32_ptr(ln_weight, "ln_weight")
+    f32_ptr(ln_bias, "ln_bias")
+    nbytes = load().gdrnpp_dwconv7x7_ln_backward_workspace_bytes(n, h, w, c)
+    ws = torch.empty((max(nbytes, 16) // 8,), dtype=torch.float64, device=x.device)
+    dx = torch.empty_like(x, memory_format=torch.channels_last) if want[0] else None
+    dweight = torch.empty((c, 1, 7, 7), dtype=torch.float32, device=x.device) if want[1] else None
+    dbias, dln_w, dln_b = (torch.empty((c,), dtype=torch.float32, device=x.device) if f else None for f in want[2:])
+    # pass A reads x and g and writes du; dx reads du and writes dx; dw reads du and x (7 kernel rows, from L2)
+    launch("gdrnpp_dwconv7x7_ln_backward", px, pw, pb, pl, pg, *(t.data_ptr() if t is not None else None for t in (dx, dweight, dbias, dln_w, dln_b)),
+           n, h, w, c, float(eps), ws.data_ptr(), nbytes, timed=("hbm:dwconv7_ln_bwd", 0.0, 4.0 * x.numel() * (3 + 2 * want[0] + 2 * want[1])))
+    return dx, dweight, dbias, dln_w, dln_b
+
+
 def layernorm_nhwc(x, weight, bias, eps: float = 1e-6):
     """x (N,C,H,W) channels_last -> LayerNorm over C per pixel, same shape/format."""
     n, c, h, w = x.shape

@@ -540,6 +540,18 @@ int gdrnpp_dwconv7x7_ln_nhwc(const float* x, const float* w49c, const float* bia
 int gdrnpp_dwconv7x7_ln_nhwc_rows(const float* x, const float* w49c, const float* bias,
                                   const float* ln_w, const float* ln_b, float* y, int N,
                                   int H, int W, int C, float eps, int y_rows, void* stream);
+/* Backward of dwconv7x7 + LayerNorm (ln_w non-NULL) for grad_y = dL/dy f32[N,H,W,C]: dx f32[N,H,W,C], dw f32[C,49] (the layout
+ * of conv.weight [C,1,7,7], not tap-major), db, dln_w, dln_b f32[C].  u and the LayerNorm statistics are recomputed from x
+ * with the forward's own fma chain; nothing of the forward is kept.  An output given as NULL is not computed, and the pass
+ * that only it needs is not launched (dx: one pass, dw: one pass).  No atomics: partial sums go to fixed slots of the
+ * workspace, whose count depends on the shape alone, and are added in slot order in fp64 — two calls give equal bits.
+ * workspace: gdrnpp_dwconv7x7_ln_backward_workspace_bytes(N,H,W,C) bytes, 16-byte aligned = one f32[N,H,W,C] (du) +
+ * at most 512 x 3C + 64 x 49C doubles; 0 for a shape the kernels do not take (C % 4, C / 4 no power of two <= 256). */
+size_t gdrnpp_dwconv7x7_ln_backward_workspace_bytes(int N, int H, int W, int C);
+int gdrnpp_dwconv7x7_ln_backward(const float* x, const float* w49c, const float* bias, const float* ln_w,
+                                 const float* grad_y, float* dx, float* dw, float* db, float* dln_w,
+                                 float* dln_b, int N, int H, int W, int C, float eps, void* workspace,
+                                 size_t workspace_bytes, void* stream);
 int gdrnpp_upsample_bilinear2x_nhwc(const float* x, float* y, int N, int H, int W,
                                     int C, void* stream);
 size_t gdrnpp_groupnorm_workspace_bytes(int N, int HW, int G);
