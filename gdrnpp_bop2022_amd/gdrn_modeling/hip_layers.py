@@ -130,7 +130,8 @@ def _dwconv_hip_ok(conv: nn.Conv2d, x: torch.Tensor) -> bool:
 
 
 # Training: layers that have a backward on this library's kernels take it under autograd when this switch is on (off by default:
-# with it off a forward under enable_grad runs PyTorch's operators, as it always has).  So far: dwconv_ln.
+# with it off a forward under enable_grad runs PyTorch's operators, as it always has).  So far: dwconv_ln (DwConvLN) and convnext_mlp
+# (ConvNeXtMlp) — with both, a ConvNeXt block trains without a kernel that is not this library's.
 _TRAIN_KERNELS = False
 
 
@@ -292,13 +293,52 @@ def mlp_takes_rows(mlp, conv_dw: nn.Conv2d, x_nchw: torch.Tensor, cache: dict) -
     return x3_for(cache, "fc1", mlp.fc1.weight, hip_lib.pack_weight_f16x2, m, 4 * c, c)[0] is not None
 
 
+class ConvNeXtMlp(torch.autograd.Function):
+    """ConvNeXt block tail y = resid + gamma * fc2(gelu(fc1(x))) on [M,C] rows with its backward on HIP kernels (csrc/mlp_bwd.hip +
+    the six-product split GEMM for products up to a depth of 256).  Saved: x, the pre-activation and the parameters — neither h nor the MLP's output.  The shortcut's
+    gradient is grad_y itself."""
+
+    @staticmethod
+    def forward(ctx, x2d, w1, b1, w2, b2, gamma, resid):
+        y, pre = hip_lib.convnext_mlp_forward_train(x2d, w1, b1, w2, b2, gamma, resid)
+        ctx.save_for_backward(x2d, pre, w1, w2, b2, gamma)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_y):
+        x2d, pre, w1, w2, b2, gamma = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        grad_y = grad_y.contiguous()
+        grads = (None,) * 6
+        if any(need[:6]):
+            grads = hip_lib.convnext_mlp_backward(x2d, pre, w1, w2, b2, gamma, grad_y, want=need[:6])
+        return (*grads, grad_y if need[6] else None)
+
+
+def _mlp_train_ok(mlp, gamma: torch.Tensor, x_nhwc: torch.Tensor, shortcut_nhwc: torch.Tensor, m: int, c: int) -> bool:
+    fc1, fc2 = getattr(mlp, "fc1", None), getattr(mlp, "fc2", None)
+    act = getattr(mlp, "act", None)
+    if not (_TRAIN_KERNELS and _ENABLED and torch.is_grad_enabled() and isinstance(fc1, nn.Linear) and isinstance(fc2, nn.Linear)):
+        return False
+    tensors = (x_nhwc, shortcut_nhwc, gamma, fc1.weight, fc1.bias, fc2.weight, fc2.bias)
+    return (all(t is not None and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() for t in tensors)
+            and c % 128 == 0 and tuple(fc1.weight.shape) == (4 * c, c) and tuple(fc2.weight.shape) == (c, 4 * c) and gamma.numel() == c
+            and shortcut_nhwc.shape == x_nhwc.shape and isinstance(act, nn.GELU) and getattr(act, "approximate", "none") == "none"
+            and 0 < m and m * 4 * c < (1 << 31))      # the GEMMs index rows with int, the split GEMM's A image below 4 GiB
+
+
 def convnext_mlp(mlp, gamma: torch.Tensor, x_nhwc: torch.Tensor, shortcut_nhwc: torch.Tensor, cache: dict, a_rows: bool = False) -> torch.Tensor:
     """timm ConvNeXtBlock tail on NHWC tensors: shortcut + gamma * fc2(gelu(fc1(x))).  On the GPU both Linear layers
     run in the library's own GEMM with the exact-erf GELU and the layer-scale/residual fused into the epilogues
     (two HBM passes over the hidden tensor saved); otherwise plain PyTorch.  ``a_rows``: x_nhwc is an f16x2-rows tensor
-    (``dwconv_ln(..., y_rows=True)`` after ``mlp_takes_rows`` said yes)."""
+    (``dwconv_ln(..., y_rows=True)`` after ``mlp_takes_rows`` said yes).  With gradients enabled and ``set_train_kernels(True)`` the
+    tail is ``ConvNeXtMlp``: this library's kernels forward and backward (six-product GEMMs up to a depth of 256, exact-f32 beyond)."""
     c = x_nhwc.shape[-1]
     m = x_nhwc.numel() // c
+    if not a_rows and _mlp_train_ok(mlp, gamma, x_nhwc, shortcut_nhwc, m, c):
+        y = ConvNeXtMlp.apply(x_nhwc.view(m, c), mlp.fc1.weight, mlp.fc1.bias, mlp.fc2.weight, mlp.fc2.bias, gamma, shortcut_nhwc.reshape(m, c))
+        return y.view(x_nhwc.shape)
     if _MLP_GEMM != "torch" and _mlp_split_ok(x_nhwc, shortcut_nhwc, m, c):
         fused = None if a_rows else _fused_mlp_weights(mlp, cache, m, c)
         if fused is not None:     # stage 0 (C = 128): fc1 + GELU + fc2 + layer scale + residual in one launch, no hidden tensor in HBM

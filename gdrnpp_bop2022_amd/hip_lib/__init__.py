@@ -23,6 +23,8 @@ from .gemm import (A_F16X2_ROWS, C_F16X2_ROWS, X3, conv2d_f32_split, conv3x3_f32
                    pack_conv3x3_weight_bf16x3, pack_conv_weight_bf16x3, pack_conv_weight_f16x2, pack_deconv_weight_bf16x3, pack_deconv_weight_f16x2,
                    pack_mlp_fused_f16x2, pack_upconv_weight_bf16x3, pack_upconv_weight_f16x2, pack_weight_bf16x3, pack_weight_f16x2,
                    packed_rows_in_range, unpack_weight_bf16x3, unpack_weight_f16x2, upsample2x_conv3x3_groupnorm_act, upsample2x_conv3x3_raw)
+from .gemm import (colsum_f32, convnext_mlp_backward, convnext_mlp_forward_train, gelu_f32, gemm_tn_f32, linear_f32_exact, mlp_bwd_act_,  # noqa: F401
+                   pack_weight_bf16x3_t)
 from .net import (DENSE_MASK_TYPES, DENSE_SUMS, DENSE_XYZ_TYPES, LOSS_MASKS, PM_TYPES, POINT_PNP_TILE, ROT_DIMS, ROT_MODES, T_MODES,  # noqa: F401
                   bias_act_nhwc_, dwconv7x7_ln, dwconv7x7_ln_backward, gdrn_dense_losses, gdrn_dense_losses_backward, gdrn_pose_losses, groupnorm_act, head_tail_nhwc,
                   layernorm_nhwc, pnp_fc_heads, pnp_fc_heads_pose, point_pnp_fc, point_pnp_pool, stem_conv4x4_ln, upsample_bilinear2x)

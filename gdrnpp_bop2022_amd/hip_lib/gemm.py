@@ -1,5 +1,6 @@
 """The split-GEMM family: weight packing, linear / convolution / transposed-convolution launches in the six-product (bf16x3) and
-three-product (fp16x2) forms, the fused ConvNeXt MLP and the GEMM + GroupNorm pairs."""
+three-product (fp16x2) forms, the fused ConvNeXt MLP, the GEMM + GroupNorm pairs, and the ConvNeXt MLP tail for training (forward
+under autograd and its backward: csrc/mlp_bwd.hip beside the six-product linear)."""
 from __future__ import annotations
 
 import torch
@@ -343,3 +344,158 @@ def upsample2x_conv3x3_groupnorm_act(x_cl, weight_packed, bias, gamma, beta, gro
     y, part, P = upsample2x_conv3x3_raw(x_cl, weight_packed, bias, groups, x3_slot, chunk)
     n, cout, oh, ow = y.shape
     return _groupnorm_apply(y, part, P, gamma, beta, n, oh * ow, cout, groups, eps, gelu)
+
+
+# ---- training: the ConvNeXt MLP tail under autograd (csrc/mlp_bwd.hip) ----------------------------------------------------------
+def pack_weight_bf16x3_t(weight, row_scale=None):
+    """``pack_weight_bf16x3((weight * row_scale[:, None]).t().contiguous())`` read straight from ``weight`` f32[R,K] (``row_scale``
+    f32[R] or None) -> bf16[K/128, R/16, 3, 2, 128, 8]: the operand of a data-gradient product, without a transpose or a multiply
+    kernel.  Byte for byte that composition."""
+    r, k = weight.shape
+    if row_scale is not None and row_scale.numel() != r:
+        raise RuntimeError(f"pack_weight_bf16x3_t: row_scale must be f32[{r}]")
+    packed = torch.empty((k // 128, r // 16, 3, 2, 128, 8), dtype=torch.bfloat16, device=weight.device)
+    launch("gdrnpp_pack_weight_bf16x3_t", f32_ptr(weight, "weight"), opt_f32_ptr(row_scale, "row_scale"), packed.data_ptr(), r, k)
+    return packed
+
+
+def gelu_f32(pre):
+    """h = gelu(pre) (exact-erf form) with the function of the split GEMMs' GELU epilogue (``gdrnpp_gelu_f32``)."""
+    h = torch.empty_like(pre)
+    launch("gdrnpp_gelu_f32", f32_ptr(pre, "pre"), h.data_ptr(), pre.numel(), timed=("hbm:gelu", 0.0, 8.0 * pre.numel()))
+    return h
+
+
+def _colsum_ws(m: int, cols: int, device):
+    nbytes = load().gdrnpp_colsum_workspace_bytes(m, cols)
+    return torch.empty((max(nbytes, 16) // 8,), dtype=torch.float64, device=device), nbytes
+
+
+def colsum_f32(x2d, scale=None, want32: bool = True):
+    """Column sums of x2d f32[M,cols] in fp64, fixed order -> (sum64 f64[cols], fl(scale * sum) f32[cols] or None)."""
+    m, cols = x2d.shape
+    ws, nbytes = _colsum_ws(m, cols, x2d.device)
+    s64 = torch.empty((cols,), dtype=torch.float64, device=x2d.device)
+    s32 = torch.empty((cols,), dtype=torch.float32, device=x2d.device) if want32 else None
+    launch("gdrnpp_colsum_f32", f32_ptr(x2d, "x"), opt_f32_ptr(scale, "scale"), s64.data_ptr(), s32.data_ptr() if want32 else None, m, cols,
+           ws.data_ptr(), nbytes, timed=("hbm:colsum", 0.0, 4.0 * x2d.numel()))
+    return s64, s32
+
+
+def mlp_bwd_act_(pre, dh, want_h: bool = True, want_db1: bool = True):
+    """``gdrnpp_mlp_bwd_act``: dh f32[M,H] becomes dpre = dh * gelu'(pre) IN PLACE -> (h = gelu(pre) or None, db1 = colsum(dpre) or None)."""
+    m, cols = pre.shape
+    if tuple(dh.shape) != (m, cols):
+        raise RuntimeError(f"mlp_bwd_act_: dh must be f32[{m},{cols}] as pre is, got {tuple(dh.shape)}")
+    ws, nbytes = _colsum_ws(m, cols, pre.device)
+    h = torch.empty_like(pre) if want_h else None
+    db1 = torch.empty((cols,), dtype=torch.float32, device=pre.device) if want_db1 else None
+    launch("gdrnpp_mlp_bwd_act", f32_ptr(pre, "pre"), f32_ptr(dh, "dh"), h.data_ptr() if want_h else None, db1.data_ptr() if want_db1 else None,
+           m, cols, ws.data_ptr(), nbytes, timed=("hbm:mlp_bwd_act", 0.0, 4.0 * pre.numel() * (3 + want_h)))
+    return h, db1
+
+
+def gemm_tn_f32(a, b, row_scale=None, w=None, bias=None, sg=None, want_g: bool = True):
+    """G[N1,N2] = a^T b for a f32[M,N1], b f32[M,N2] (N1, N2 multiples of 128, any M >= 1) on the exact-f32 matrix instruction
+    (``gdrnpp_gemm_tn_f32``): the weight-gradient product.  Deterministic: fixed slots, fp64 finalize, one rounding.
+    ``row_scale`` f32[N1]: G[c,:] = fl(row_scale[c] * sum).  With ``w`` f32[N1,N2], ``bias`` f32[N1] and ``sg`` f64[N1] the result is
+    (G, drow) with drow[c] = fl(sum_k w[c,k] sum[c,k] + bias[c] sg[c]), the layer-scale gradient, taken before G is rounded;
+    ``want_g`` False leaves G out (None)."""
+    m, n1 = a.shape
+    if b.dim() != 2 or b.shape[0] != m:
+        raise RuntimeError(f"gemm_tn_f32: b must have the {m} rows of a, got {tuple(b.shape)}")
+    n2 = b.shape[1]
+    layer_scale = w is not None
+    if layer_scale and (bias is None or sg is None or tuple(w.shape) != (n1, n2) or bias.numel() != n1 or sg.numel() != n1):
+        raise RuntimeError(f"gemm_tn_f32: the layer-scale form takes w f32[{n1},{n2}], bias f32[{n1}] and sg f64[{n1}]")
+    if not (want_g or layer_scale):
+        raise RuntimeError("gemm_tn_f32: nothing asked for")
+    nbytes = load().gdrnpp_gemm_tn_f32_workspace_bytes(m, n1, n2)
+    if nbytes == 0:
+        raise RuntimeError(f"gemm_tn_f32: N1={n1} N2={n2} must be multiples of 128 (M={m} >= 1)")
+    ws = torch.empty((nbytes // 8,), dtype=torch.float64, device=a.device)
+    g = torch.empty((n1, n2), dtype=torch.float32, device=a.device) if want_g else None
+    drow = torch.empty((n1,), dtype=torch.float32, device=a.device) if layer_scale else None
+    launch("gdrnpp_gemm_tn_f32", f32_ptr(a, "a"), f32_ptr(b, "b"), g.data_ptr() if want_g else None, m, n1, n2, opt_f32_ptr(row_scale, "row_scale"),
+           opt_f32_ptr(w, "w"), opt_f32_ptr(bias, "bias"), dev_ptr(sg, torch.float64, "sg") if layer_scale else None,
+           drow.data_ptr() if layer_scale else None, ws.data_ptr(), nbytes, timed=("gemm_tn", 2.0 * m * n1 * n2, 4.0 * m * (n1 + n2) + 4.0 * n1 * n2))
+    return (g, drow) if layer_scale else g
+
+
+def linear_f32_exact(x2d, weight, bias=None, gamma=None, resid=None, weight_kn: bool = False, row_scale=None):
+    """out = x2d @ weight^T + bias (``weight`` f32[N,K], as nn.Linear holds it) or, ``weight_kn``, x2d @ (row_scale[:, None] * weight)
+    for a weight f32[K,N]; with ``gamma`` and ``resid``: resid + gamma * (that).  ``gdrnpp_linear_f32_exact``: the exact-f32 matrix
+    instruction, fp32 chains of 128 carried in fp64, one rounding — for products too deep for the six-product kernel's accuracy."""
+    m, k = x2d.shape
+    n = weight.shape[1] if weight_kn else weight.shape[0]
+    if tuple(weight.shape) != ((k, n) if weight_kn else (n, k)):
+        raise RuntimeError(f"linear_f32_exact: weight {tuple(weight.shape)} does not fit x [{m},{k}]")
+    if (gamma is None) != (resid is None) or (row_scale is not None and not weight_kn):
+        raise RuntimeError("linear_f32_exact: gamma and resid come together; row_scale goes with weight_kn")
+    out = torch.empty((m, n), dtype=torch.float32, device=x2d.device)
+    nbytes = load().gdrnpp_linear_f32_exact_workspace_bytes(m, n, k)      # 0: one depth slot, no workspace
+    ws = torch.empty((nbytes // 8,), dtype=torch.float64, device=x2d.device) if nbytes else None
+    launch("gdrnpp_linear_f32_exact", f32_ptr(x2d, "x"), f32_ptr(weight, "weight"), 0 if weight_kn else 1, opt_f32_ptr(row_scale, "row_scale"),
+           opt_f32_ptr(bias, "bias"), opt_f32_ptr(gamma, "gamma"), opt_f32_ptr(resid, "resid"), out.data_ptr(), m, n, k,
+           ws.data_ptr() if nbytes else None, nbytes,
+           timed=("linear_exact", 2.0 * m * n * k, 4.0 * (m * k + n * k + m * n * (2 if gamma is not None else 1))))
+    return out
+
+
+# Deepest product of the training tail that runs on the six-product kernel.  Measured on an MI355X against fp64 on the same operands,
+# beside a CPU sgemm: gdrnpp_linear_f32_split 1.3 - 1.6e-6 at K = 128 (CPU 1.7 - 2.0e-6), 2.5e-6 at 256 (1.8e-6), 2.5 - 3.0e-6 at 512
+# (1.4 - 1.7e-6), 3.5 - 3.7e-6 at 1024 (1.1 - 1.4e-6): from 512 on it is at or past the factor 2 the gradient tests' bar allows, so
+# those products take linear_f32_exact.  Inference is not concerned.
+_SIX_PRODUCT_MAX_DEPTH = 256
+
+
+def _tail_product(a, w, bias=None, epilogue="none", gamma=None, resid=None, weight_kn=False, row_scale=None):
+    """One forward-shaped product of the training tail: a @ w^T (w [N,K]) or, ``weight_kn``, a @ (row_scale[:, None] * w) (w [K,N])."""
+    if a.shape[1] > _SIX_PRODUCT_MAX_DEPTH:
+        return linear_f32_exact(a, w, bias, gamma, resid, weight_kn, row_scale)
+    packed = pack_weight_bf16x3_t(w, row_scale) if weight_kn else pack_weight_bf16x3(w)
+    return linear_f32_split(a, packed, bias, epilogue, gamma, resid)
+
+
+def convnext_mlp_forward_train(x2d, w1, b1, w2, b2, gamma, resid):
+    """The ConvNeXt MLP tail for autograd -> (y, pre): pre = x2d W1^T + b1 (kept for the backward), y = resid + gamma * (gelu(pre)
+    W2^T + b2).  Products up to a depth of 256 on the six-product split GEMM with the weights packed per call (they change every
+    step), deeper ones on ``linear_f32_exact``; h is not kept."""
+    pre = _tail_product(x2d, w1, b1)
+    y = _tail_product(gelu_f32(pre), w2, b2, "scale_res", gamma, resid)
+    return y, pre
+
+
+def convnext_mlp_backward(x2d, pre, w1, w2, b2, gamma, grad_y, want=(True,) * 6):
+    """Gradients of ``convnext_mlp_forward_train`` for grad_y = dL/dy f32[M,C] -> (dx, dw1, db1, dw2, db2, dgamma); the shortcut's
+    gradient is grad_y itself.  ``want``: six flags in that order — an entry is None where its flag is false and the kernels only it
+    needs are not launched; the others keep their bits.  Saved from the forward: x2d and pre only (h is recomputed, z never formed:
+    dgamma = rowsum(W2 * G) + b2 * colsum(g) with G = g^T h).  Fixed summation order: two calls give the same bits."""
+    what = "convnext_mlp_backward"
+    want = tuple(bool(f) for f in want)
+    if len(want) != 6 or not any(want):
+        raise RuntimeError(f"{what}: want must hold six flags, at least one of them set")
+    m, c = x2d.shape
+    hid = w1.shape[0]
+    if tuple(pre.shape) != (m, hid) or tuple(w1.shape) != (hid, c) or tuple(w2.shape) != (c, hid) or tuple(grad_y.shape) != (m, c) \
+            or b2.numel() != c or gamma.numel() != c:
+        raise RuntimeError(f"{what}: shapes x [{m},{c}], pre {tuple(pre.shape)}, w1 {tuple(w1.shape)}, w2 {tuple(w2.shape)}, grad_y {tuple(grad_y.shape)} do not fit")
+    w_dx, w_dw1, w_db1, w_dw2, w_db2, w_dg = want
+    need_dpre, need_g = w_dx or w_dw1 or w_db1, w_dw2 or w_dg
+    dx = dw1 = db1 = dw2 = db2 = dgamma = h = None
+    if need_dpre:
+        dpre = _tail_product(grad_y, w2, weight_kn=True, row_scale=gamma)        # dh = g (diag(gamma) W2), then in place
+        h, db1 = mlp_bwd_act_(pre, dpre, want_h=need_g, want_db1=w_db1)
+        if w_dx:
+            dx = _tail_product(dpre, w1, weight_kn=True)
+        if w_dw1:
+            dw1 = gemm_tn_f32(dpre, x2d)
+    elif need_g:
+        h = gelu_f32(pre)
+    if need_g or w_db2:
+        sg, db2 = colsum_f32(grad_y, gamma, want32=w_db2)
+    if need_g:
+        dw2, dgamma = gemm_tn_f32(grad_y, h, gamma, w2, b2, sg, want_g=w_dw2)
+        if not w_dg:
+            dgamma = None
+    return dx, dw1, db1, dw2, db2, dgamma

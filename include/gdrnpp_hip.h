@@ -552,6 +552,49 @@ int gdrnpp_dwconv7x7_ln_backward(const float* x, const float* w49c, const float*
                                  const float* grad_y, float* dx, float* dw, float* db, float* dln_w,
                                  float* dln_b, int N, int H, int W, int C, float eps, void* workspace,
                                  size_t workspace_bytes, void* stream);
+/* Backward of the ConvNeXt MLP tail y = s + gamma (.) (gelu(x W1^T + b1) W2^T + b2) (csrc/mlp_bwd.hip): the kernels beside
+ * gdrnpp_linear_f32_split, which runs the two data-gradient products dh = g (diag(gamma) W2) and dx = dpre W1 as it is.
+ *  pack_weight_bf16x3_t : the image gdrnpp_pack_weight_bf16x3 makes of T = (diag(row_scale) W)^T, f32[K,R], read from W f32[R,K]
+ *                 (row_scale f32[R] or NULL; K % 128 == 0, R % 32 == 0): byte for byte that of the transposed, scaled copy.
+ *  gelu_f32     : h = gelu(pre), n elements (n % 4 == 0), with the function of the split GEMMs' GELU epilogue.
+ *  colsum_f32   : column sums of x f32[M,cols] (cols % 4 == 0) in fp64 through fixed partial slots: sum64[cols] (fp64) and / or
+ *                 sum32[c] = fl(scale[c] sum[c]) (scale f32[cols] or NULL).  workspace: gdrnpp_colsum_workspace_bytes(M, cols) bytes
+ *                 (at most 256 x cols doubles), 16-byte aligned.
+ *  mlp_bwd_act  : one pass over [M,cols]: dh_dpre holds dh on entry and dpre = dh gelu'(pre) on return, gelu'(x) = Phi(x) +
+ *                 x phi(x); h (or NULL) receives gelu(pre), recomputed; db1 (or NULL) f32[cols] the column sums of dpre.  The
+ *                 workspace of colsum_f32.
+ *  gemm_tn_f32  : G[N1,N2] = sum_m A[m,N1] B[m,N2], A f32[M,N1], B f32[M,N2] row-major, N1 % 128 == 0, N2 % 128 == 0, any M >= 1,
+ *                 on the exact-f32 matrix instruction.  fp32 chains of at most 128 rows are carried in fp64; the rows are dealt to at
+ *                 most 64 slots (512-row chunks; no more slots than bring the grid to 512 workgroups; the count from the shape
+ *                 alone) whose fp64 tiles the finalize adds in slot order and
+ *                 rounds once: no atomics, two calls give equal bits.  row_scale (f32[N1] or NULL): G[c,:] = fl(row_scale[c] sum).
+ *                 drow (f32[N1] or NULL; needs W f32[N1,N2], b f32[N1], sg f64[N1]): drow[c] = fl(sum_k W[c,k] sum[c,k] + b[c]
+ *                 sg[c]) from the fp64 sums — the layer-scale gradient.  G may be NULL when drow is asked for.  workspace:
+ *                 gdrnpp_gemm_tn_f32_workspace_bytes(M, N1, N2) bytes (slots x N1 x N2 doubles), 16-byte aligned; 0 for a shape
+ *                 outside the kernel. */
+ /* linear_f32_exact : out[M,N] = epilogue(A[M,K] Bop) on the exact-f32 matrix instruction with gemm_tn_f32's sums (fp32 chains of 128,
+ *                 fp64 carries, one rounding): the deep products of the tail (K >= 512), where the six-product kernel's fp32
+ *                 accumulation is past twice a CPU sgemm's error.  b_is_nk != 0: B f32[N,K] (an nn.Linear weight, out = A B^T);
+ *                 else B f32[K,N], times row_scale[k] (f32[K] or NULL).  bias f32[N] or NULL; gamma f32[N] and resid f32[M,N]
+ *                 together or both NULL: out = resid + gamma (sum + bias).  N % 128 == 0, K % 32 == 0, any M >= 1.  A launch
+ *                 with fewer than 256 output tiles cuts K into slots (multiples of 128, their count from the shape alone) whose
+ *                 fp64 tiles a finalize adds in slot order: workspace of gdrnpp_linear_f32_exact_workspace_bytes(M, N, K) bytes
+ *                 (slots x M x N doubles; 0 with one slot, and the workspace may then be NULL), 16-byte aligned. */
+size_t gdrnpp_linear_f32_exact_workspace_bytes(int M, int N, int K);
+int gdrnpp_linear_f32_exact(const float* A, const float* B, int b_is_nk, const float* row_scale, const float* bias,
+                            const float* gamma, const float* resid, float* out, int M, int N, int K, void* workspace,
+                            size_t workspace_bytes, void* stream);
+int gdrnpp_pack_weight_bf16x3_t(const float* W, const float* row_scale, void* packed, int R, int K, void* stream);
+int gdrnpp_gelu_f32(const float* pre, float* h, size_t n, void* stream);
+size_t gdrnpp_colsum_workspace_bytes(long M, int cols);
+int gdrnpp_colsum_f32(const float* x, const float* scale, double* sum64, float* sum32, long M, int cols,
+                      void* workspace, size_t workspace_bytes, void* stream);
+int gdrnpp_mlp_bwd_act(const float* pre, float* dh_dpre, float* h, float* db1, long M, int cols,
+                       void* workspace, size_t workspace_bytes, void* stream);
+size_t gdrnpp_gemm_tn_f32_workspace_bytes(int M, int N1, int N2);
+int gdrnpp_gemm_tn_f32(const float* A, const float* B, float* G, int M, int N1, int N2, const float* row_scale,
+                       const float* W, const float* b, const double* sg, float* drow, void* workspace,
+                       size_t workspace_bytes, void* stream);
 int gdrnpp_upsample_bilinear2x_nhwc(const float* x, float* y, int N, int H, int W,
                                     int C, void* stream);
 size_t gdrnpp_groupnorm_workspace_bytes(int N, int HW, int G);
