@@ -45,7 +45,7 @@ int ensure_dynamic_lds(const void* kernel, int bytes) {
   return 0;
 }
 // tuning switches: written by gdrnpp_set_option, read by launches on any host thread
-static std::atomic<int> g_opt_glds{1}, g_opt_mi4{-1}, g_opt_pipe{3}, g_opt_panel{4}, g_opt_big_tiles{256}, g_opt_dw_tile{-1}, g_opt_splitk_small{1}, g_opt_mlp_fused_pipe{1}, g_opt_dw_lds_w{1}, g_opt_dw_lds_pad{0}, g_opt_upconv_lowres{1}, g_opt_dw_specialise{1};
+static std::atomic<int> g_opt_glds{1}, g_opt_mi4{-1}, g_opt_pipe{3}, g_opt_panel{4}, g_opt_big_tiles{256}, g_opt_dw_tile{-1}, g_opt_splitk_small{1}, g_opt_mlp_fused_pipe{1}, g_opt_dw_lds_w{1}, g_opt_dw_lds_pad{0}, g_opt_upconv_lowres{1}, g_opt_dw_specialise{1}, g_opt_conv3x3_window{1};
 int option_split_gemm_glds() { return g_opt_glds; }
 int option_split_gemm_pipe() { return g_opt_pipe; }
 int option_split_gemm_mi4() { return g_opt_mi4; }
@@ -57,6 +57,7 @@ int option_mlp_fused_pipe() { return g_opt_mlp_fused_pipe; }
 int option_dwconv_lds_w() { return g_opt_dw_lds_w; }
 int option_dwconv_lds_pad() { return g_opt_dw_lds_pad; }
 int option_dwconv_specialise() { return g_opt_dw_specialise; }
+int option_conv3x3_window() { return g_opt_conv3x3_window; }
 }  // namespace gdrnpp
 
 namespace {
@@ -124,6 +125,7 @@ int gdrnpp_set_option(const char* name, int value) {
   if (!strcmp(name, "dwconv_lds_pad")) { gdrnpp::g_opt_dw_lds_pad = value < 0 ? 0 : (value > 112 * 1024 ? 112 * 1024 : value); return 0; }
   if (!strcmp(name, "split_gemm_mi4")) { gdrnpp::g_opt_mi4 = value < 0 ? -1 : (value != 0); return 0; }
   if (!strcmp(name, "upconv_lowres")) { gdrnpp::g_opt_upconv_lowres = value != 0; return 0; }
+  if (!strcmp(name, "conv3x3_window")) { gdrnpp::g_opt_conv3x3_window = value != 0; return 0; }
   gdrnpp::set_error("gdrnpp_set_option: unknown option '%s'", name);
   return GDRNPP_EINVAL;
 }
@@ -135,7 +137,8 @@ int gdrnpp_get_option(const char* name, int* value) {
       {"splitk_small_tiles", &gdrnpp::g_opt_splitk_small}, {"dwconv_tile", &gdrnpp::g_opt_dw_tile},
       {"mlp_fused_pipe", &gdrnpp::g_opt_mlp_fused_pipe}, {"dwconv_lds_w", &gdrnpp::g_opt_dw_lds_w},
       {"dwconv_lds_pad", &gdrnpp::g_opt_dw_lds_pad},  {"split_gemm_mi4", &gdrnpp::g_opt_mi4},
-      {"upconv_lowres", &gdrnpp::g_opt_upconv_lowres}, {"dwconv_specialise", &gdrnpp::g_opt_dw_specialise}};
+      {"upconv_lowres", &gdrnpp::g_opt_upconv_lowres}, {"dwconv_specialise", &gdrnpp::g_opt_dw_specialise},
+      {"conv3x3_window", &gdrnpp::g_opt_conv3x3_window}};
   for (const auto& e : table)
     if (!strcmp(name, e.name)) { *value = e.opt->load(); return 0; }
   gdrnpp::set_error("gdrnpp_get_option: unknown option '%s'", name);

@@ -77,6 +77,7 @@ int option_dwconv_tile();       // -1 (default): by launch size; 0 / 1 / 2: forc
 int option_dwconv_lds_w();      // 1 (default): [49][C] weights in LDS + persistent workgroups where they fit; 0: weights through L1 / L2, no LDS (A/B:
                                 // a workgroup that needs 98 KB of LDS cannot start on a CU that holds one 80 KB GEMM workgroup of another stream)
 int option_dwconv_specialise();  // 1 (default): C = 128 / 256 / 512 / 1024 run the dwconv7x7+LN kernel compiled for that width; 0: the run-time-width form
+int option_conv3x3_window();     // 1 (default): the three-product conv3x3 stages one input window per 16-channel chunk where the shape allows (gemm_split2_pipe.hip); 0: one A image per tap
                                 // at every C (A/B and bit-equality switch)
 int option_dwconv_lds_pad();    // experiment only: dynamic LDS bytes the no-LDS form allocates all the same (profiles/r06_dwconv_shared.txt)
 

@@ -43,7 +43,9 @@
 // workgroups per CU.  Linear form, the 3x3 / stride 1 / pad 1 convolution and the general K x K / stride / pad convolution
 // (implicit im2col, k-tile order of gemm_split.hpp), optional GroupNorm statistics in the epilogue (GnStats,
 // split_gemm_device.hpp).  -DGDRNPP2_TIMING_NO_{BREAD,SPLIT,SYNC,DMA}, -DGDRNPP2_NO_RANGE_CHECK: timing-only builds (results
-// invalid) that take one component out of the k-loop (profiles/r03y_split2_kloop_dissection.txt).  The alternatives this kernel
+// invalid) that take one component out of the k-loop (profiles/r03y_split2_kloop_dissection.txt).  At W = 16 / 32 / 64 the 3x3
+// convolution runs conv3x3_window_kernel below, which stages the input once per 16-channel chunk instead of once per tap (library
+// option "conv3x3_window", profiles/conv3x3_window.md).  The alternatives this kernel
 // was measured against are retired (docs/DESIGN_HISTORY.md, "Retired variants").
 #include "split2_common.hpp"
 
@@ -420,6 +422,256 @@ int launch_one(const float* A, const uint4* Wp, const float* bias, const float* 
   return launch_kernel<EPI, CONV, GNS>(A, Wp, bias, gamma, resid, C, M, N, K, cg, panel, gn, range_flag, st, what, c_rows);
 }
 
+// ---- window-staged form of the 3x3 / stride 1 / pad 1 convolution (library option "conv3x3_window") ---------------------------
+// The CONV == 1 form above brings every input pixel of a tile from L2 into LDS nine times, once per tap.  Here the image width W
+// (16 / 32 / 64) is a compile-time constant, a tile is 256 / W whole image rows, and all nine taps of a 16-channel chunk read one
+// window of the tile's rows plus the row above and the row below: (256 + 2 W) pixels x 64 bytes, staged once per chunk by LDS-DMA
+// (24 / 20 / 18 pieces of 1 KB against 9 x 16) and double-buffered.  The window is the run of pixels m0 - W .. m0 + 255 + W of the
+// NHWC tensor, so the A fragment of tap (dy, dx) of tile row r is window pixel r + W (1 + dy) + dx: one wave-uniform offset per tap,
+// and the swizzle key (pixel >> 2) & 3 — that of the A stages above, applied on the source side of the DMA — is recomputed from that
+// pixel.  Halo ROWS outside the image come from g_zero_page (decided per piece: a piece is 16 pixels of one row; no address outside
+// the tensor is formed).  There are no halo COLUMNS: left and right of the image the run holds the neighbouring row's pixel, and the
+// lanes whose row sits in column 0 / W - 1 replace what they read for a dx = -1 / +1 tap by zeros ahead of the split (8 v_cndmask
+// per row half).  Two windows of 24 KB and the four weight slots are the 80 KB of the form above, so the weight protocol (slot
+// kt & 3, DMA two k-tiles ahead, one barrier per two k-tiles) is that form's, unchanged.  k order: chunk outer, tap inner
+// (kt = 9 chunk + tap; the packed weights are tap-major and are visited as wkt = tap * cpt + chunk).
+//
+// Window protocol.  Wave w moves pieces j * 4 + w; piece j of the window of chunk c + 1 is issued in slot 4 of k-tile (c, tap j),
+// j < 6.  A k-tile that issued one waits with vmcnt(1) behind slot SB (the weights are older), one that did not with vmcnt(0); so
+// behind slot SB of (c, 6) every piece of a wave has landed, and the barrier of (c, 6) or (c, 7) — whichever k-tile is odd —
+// publishes them ahead of the first read, the one behind slot SB of (c, 7).  The buffer the pieces go to held chunk c - 1, last
+// read in slot 9 of (c - 1, 7), ahead of the barrier of (c - 1, 7) or (c - 1, 8).
+constexpr int WIN_B = (256 + 2 * 64) * 64;      // bytes of a window buffer (that of W = 64, whatever W): 24 KB
+constexpr int WIN_LDS_BYTES = 2 * WIN_B + NB * W2_TILE_B;
+static_assert(WIN_LDS_BYTES <= LDS_BYTES, "two workgroups per CU");
+
+// z: the lane's pixel lies outside the image for the tap of this raw fragment (left / right border): it multiplies zeros
+__device__ __forceinline__ void zero_raw(HalfSplit2T<false>& hs, bool z) {
+#pragma unroll
+  for (int i = 0; i < 8; ++i) hs.x[i] = z ? 0.f : hs.x[i];
+}
+
+// IW: image width (16 / 32 / 64).  Requires H % (256 / IW) == 0 (a tile is whole rows of one image; M % 256 == 0 follows) and
+// Cin % 32 == 0.  Waves, accumulators, row -> lane map, weight slots, epilogue and GnStats partials are those of
+// gemm_split2_pipe_kernel<EPI, 1, GNS>.
+template <int EPI, int IW, bool GNS>
+__global__ __launch_bounds__(256, 2) void conv3x3_window_kernel(const float* __restrict__ A, const uint4* __restrict__ Wp,
+                                                                const float* __restrict__ bias, float* __restrict__ C, int M, int N,
+                                                                ConvGeom cg, GnStats gn, int* range_flag) {
+  using HalfSplit2 = HalfSplit2T<false>;
+  constexpr int NS = 6 * NJ, SB = 19, S1 = 13;        // slots of a k-tile as in gemm_split2_pipe_kernel
+  constexpr int NPIECES = (256 + 2 * IW) / 16;        // 1 KB pieces (16 pixels) of a window
+  constexpr int NPW = (NPIECES + 3) / 4;              // pieces per wave: 6 / 5 / 5
+  constexpr int WPMAX = 255 + 2 * IW;                 // last window pixel
+  static_assert(NPW <= 6, "the pieces of a window go out in k-tiles 0 .. 5 of the chunk before");
+  extern __shared__ uint4 smem[];  // [2][WIN_B / 16] windows | [NB][512] weight slots
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int ntn = N / BN;
+  const TileMN tile = tile_coords(xcd_tile_id(), ntn, 0, M);
+  const int tile_n = tile.n, m0 = tile.m * 256, n0 = tile_n * BN;
+  const int cpt = cg.C / BK, nk = 9 * cpt, K = 9 * cg.C;
+  const unsigned lds0 = lds_addr(smem);
+  const float wsc = reinterpret_cast<const float*>(Wp + (size_t)(N / BN) * nk * W2_TILE_SLOTS)[1];
+  const float* const gamma = nullptr;   // (names the shared epilogue refers to under epilogues this kernel does not have)
+  const float* const resid = nullptr;
+  constexpr int c_rows = 0;
+
+  // ---- window DMA: a lane of piece p fills chunk position (lane & 3) of window pixel 16 p + lane / 4 with source chunk
+  // (lane & 3) ^ key, key = (pixel >> 2) & 3 = (lane >> 4) & 3
+  const int y0 = (m0 % (cg.H * IW)) / IW;             // image row of the tile's first pixel
+  const unsigned woff = (unsigned)(lane >> 2) * (unsigned)(cg.C * 4) + (unsigned)(((lane & 3) ^ ((lane >> 4) & 3)) * 16);
+  const unsigned zoff = (unsigned)(lane & 3) * 16u;
+  // piece j of this wave of the window of chunk `chunk` -> window buffer at LDS byte offset wb
+  auto dma_win = [&](int chunk, unsigned wb, int j) {
+    const int p = j * 4 + wave;
+    if (p < NPIECES) {
+      const int y = y0 - 1 + (16 * p) / IW;           // image row of the piece's 16 pixels
+      const unsigned dst = lds0 + wb + (unsigned)p * 1024u;
+      if ((unsigned)y < (unsigned)cg.H)
+        dma_s(woff, A + ((long)m0 - IW + 16 * p) * cg.C + chunk * BK, dst);
+      else
+        dma_s(zoff, g_zero_page, dst);
+    }
+  };
+  const unsigned boff = (unsigned)((wave * 2) * 64 + lane) * 16u;
+  const char* const wbase = reinterpret_cast<const char*>(Wp + (size_t)tile_n * nk * W2_TILE_SLOTS);
+  const unsigned ldsB = lds0 + (unsigned)(2 * WIN_B) + (unsigned)(wave * 2) * 1024u;
+  auto dma_b = [&](int kt, unsigned sb, auto cc) {
+    constexpr int c = decltype(cc)::value;
+    const int chunk = kt / 9, tap = kt - 9 * chunk;
+    dma_s(boff, wbase + ((size_t)(tap * cpt + chunk) * W2_TILE_B + c * 1024), ldsB + sb + (unsigned)(c * 1024));
+  };
+
+  f32x16 acc[2][NJ];
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < NJ; ++j)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+
+  // ---- fragment lanes: MFMA operand lane = tile row (lane & 31) (+ 32 in the second half), k-block fk = lane >> 5
+  const int frow = lane & 31, fk = lane >> 5;
+  const int lrow0 = wave * 64 + frow;
+  const bool edgeL0 = lrow0 % IW == 0, edgeL1 = (lrow0 + 32) % IW == 0;                 // column 0 (row halves 0 / 1)
+  const bool edgeR0 = lrow0 % IW == IW - 1, edgeR1 = (lrow0 + 32) % IW == IW - 1;       // column W - 1
+  const uint4* const sBf = smem + 2 * (WIN_B / 16) + fk * BN + frow;
+
+  // raw A fragment of row half `half` for k-tile kt (clamped to the last): window pixel = tile row + tap offset
+  auto load_half = [&](HalfSplit2& hs, int kt, int half) {
+    const int ktc = min(kt, nk - 1), chunk = ktc / 9, tap = ktc - 9 * chunk, ty = tap / 3;
+    const int toff = IW * ty + (tap - 3 * ty) - 1;
+    // pixels -1 and WPMAX + 1 belong to lanes that are zeroed (tile row 0 / 255, column 0 / W - 1): keep their reads inside the window
+    const int wp = min(max(lrow0 + half * 32 + toff, 0), WPMAX);
+    const int s0 = 4 * wp + ((2 * fk) ^ ((wp >> 2) & 3));
+    hs.load(smem + (chunk & 1) * (WIN_B / 16), s0, s0 ^ 1);
+  };
+  // dx of k-tile kt (clamped to the last): -1 / +1 = the lanes in column 0 / W - 1 multiply zeros
+  auto tap_dx = [&](int kt) {
+    const int ktc = min(kt, nk - 1), tap = ktc % 9;
+    return tap % 3 - 1;
+  };
+
+  auto bslot = [](int P, int J) { return P * KB * BN + J * 32; };
+  [[maybe_unused]] float ssq[4] = {0.f, 0.f, 0.f, 0.f};
+
+  // One k-tile: the slot plan of gemm_split2_pipe_kernel's ktile with the window in place of the A stages
+  auto ktile = [&](int kt, HalfSplit2 (&cur)[2], HalfSplit2 (&nxt)[2], f16x8 (&fbL)[NJ], f16x8 (&fbH)[NJ], auto odd_) {
+    constexpr int ODD = decltype(odd_)::value;
+    const uint4* const b = sBf + (kt & 3) * (W2_TILE_B / 16);
+    const uint4* const bn = sBf + ((kt + 1) & 3) * (W2_TILE_B / 16);
+    const int kt_b = min(kt + 2, nk - 1);
+    const unsigned sb_wr = (unsigned)(((kt + 2) & 3) * W2_TILE_B);
+    const int chunk = kt / 9, tap = kt - 9 * chunk;
+    const bool piece = tap < NPW && tap * 4 + wave < NPIECES && chunk + 1 < cpt;   // wave-uniform
+    const int dxn = tap_dx(kt + 1);
+    const bool z0 = (dxn < 0 && edgeL0) || (dxn > 0 && edgeR0), z1 = (dxn < 0 && edgeL1) || (dxn > 0 && edgeR1);
+    static_for<0, NS>([&](auto s_) {
+      constexpr int S = decltype(s_)::value;
+      constexpr int G = S / (2 * NJ), I = (S % (2 * NJ)) / NJ, J = S % NJ;
+      const f16x8 fa = (G == 1) ? cur[I].template frag<1>() : cur[I].template frag<0>();
+      const f16x8 fb = (G == 0) ? fbL[J] : fbH[J];
+      acc[I][J] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa, fb, acc[I][J], 0, 0, 0);
+      if constexpr (S % 2 == 0 && S < 4) dma_b(kt_b, sb_wr, std::integral_constant<int, S / 2>{});
+      if constexpr (S == 4) {
+        if (piece) dma_win(chunk + 1, (unsigned)(((chunk + 1) & 1) * WIN_B), tap);
+      }
+      if constexpr (S % 2 == 1 && S < NJ) {   // weight split h of kt
+        constexpr int j0 = S - 1;
+        fbH[j0] = __builtin_bit_cast(f16x8, b[bslot(0, j0)]);
+        fbH[j0 + 1] = __builtin_bit_cast(f16x8, b[bslot(0, j0 + 1)]);
+      }
+#ifndef GDRNPP2_NO_RANGE_CHECK
+      {
+        constexpr int rc[4] = {0, 2, 11, 12};
+        if constexpr (S == rc[0]) { ssq[2] = sumsq2(cur[1].h[0], ssq[2]); ssq[3] = sumsq2(cur[1].h[1], ssq[3]); }
+        if constexpr (S == rc[1]) { ssq[2] = sumsq2(cur[1].h[2], ssq[2]); ssq[3] = sumsq2(cur[1].h[3], ssq[3]); }
+        if constexpr (S == rc[2]) { ssq[0] = sumsq2(cur[0].h[0], ssq[0]); ssq[1] = sumsq2(cur[0].h[1], ssq[1]); }
+        if constexpr (S == rc[3]) { ssq[0] = sumsq2(cur[0].h[2], ssq[0]); ssq[1] = sumsq2(cur[0].h[3], ssq[1]); }
+      }
+#endif
+      if constexpr (S == S1 - 4) load_half(nxt[1], kt + 1, 1);
+      if constexpr (S == 3) zero_raw(nxt[0], z0);
+      if constexpr (S == S1) zero_raw(nxt[1], z1);
+      if constexpr (S >= 3 && S < 11) nxt[0].template step<S - 3>();
+      if constexpr (S >= S1 && S < S1 + 8) nxt[1].template step<S - S1>();
+      if constexpr (S == SB) {
+        if (piece) wait_vmcnt<1>(); else wait_vmcnt<0>();
+        __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): every LDS read of what is about to be refilled has returned
+        if constexpr (ODD) __builtin_amdgcn_s_barrier();
+      }
+      if constexpr (S > SB && S <= SB + NJ / 2) {   // weight split l of k-tile kt+1
+        constexpr int j0 = 2 * (S - SB - 1);
+        fbL[j0] = __builtin_bit_cast(f16x8, bn[bslot(1, j0)]);
+        fbL[j0 + 1] = __builtin_bit_cast(f16x8, bn[bslot(1, j0 + 1)]);
+      }
+      if constexpr (S == SB + NJ / 2 + 1) load_half(cur[0], kt + 2, 0);
+      __builtin_amdgcn_sched_barrier(0);
+    });
+  };
+
+  // ---- prologue: the window of chunk 0, k-tiles 0 and 1 of the weights; split k-tile 0; first fragments of the loop
+  HalfSplit2 f0[2], f1[2];
+  f16x8 fbL[NJ], fbH[NJ];
+  for (int j = 0; j < NPW; ++j) dma_win(0, 0u, j);
+  static_for<0, 2>([&](auto c) { dma_b(0, 0u, c); });
+  static_for<0, 2>([&](auto c) { dma_b(1, (unsigned)W2_TILE_B, c); });
+  wait_vmcnt<0>();
+  __builtin_amdgcn_s_barrier();
+  load_half(f0[0], 0, 0);
+  load_half(f0[1], 0, 1);
+  zero_raw(f0[0], edgeL0);   // tap 0: dx = -1
+  zero_raw(f0[1], edgeL1);
+  static_for<0, 8>([&](auto s) { f0[0].template step<decltype(s)::value>(); f0[1].template step<decltype(s)::value>(); });
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) fbL[j] = __builtin_bit_cast(f16x8, sBf[bslot(1, j)]);
+  load_half(f1[0], 1, 0);
+
+  // ---- main loop, two k-tiles per trip (nk = 9 cpt is even: Cin % 32 == 0)
+  for (int kt = 0; kt < nk; kt += 2) {
+    ktile(kt, f0, f1, fbL, fbH, std::integral_constant<int, 0>{});
+    ktile(kt + 1, f1, f0, fbL, fbH, std::integral_constant<int, 1>{});
+  }
+  wait_vmcnt<0>();
+  __builtin_amdgcn_s_waitcnt(0xc07f);
+  __builtin_amdgcn_s_barrier();  // both windows are dead: the epilogue reuses them
+
+  bool bad = false;
+#define EPI_TILES_M 2
+#define EPI_HALVES (NJ / 2)
+#define EPI_ACC(i, j) acc[i][j]
+#define EPI_ROW0 m0 + wave * 64
+#define EPI_COL0 n0
+#define EPI_BIAS bias
+#define EPI_STAGE smem
+#define EPI_STAGE_BYTES (2 * WIN_B)
+#define EPI_SCALE wsc
+#define EPI_GN gn
+#define EPI_RANGE_BAD bad
+#include "split_epilogue_body.hpp"
+  // range verdict of the wave's 64 A rows, as in gemm_split2_pipe_kernel
+  bool small = false;
+#ifndef GDRNPP2_NO_RANGE_CHECK
+  {
+    float s0 = ssq[0] + ssq[1], s1 = ssq[2] + ssq[3];
+    s0 += __shfl_xor(s0, 32, 64);
+    s1 += __shfl_xor(s1, 32, 64);
+    const float thr = (float)K * 0x1p-8f;
+    small = (s0 > 0.f && s0 < thr) || (s1 > 0.f && s1 < thr);
+    bad |= !(s0 < __builtin_inff()) || !(s1 < __builtin_inff());
+  }
+#endif
+  const int word = (__builtin_amdgcn_ballot_w64(bad) != 0 ? GDRNPP_SPLIT2_NONFINITE : 0) |
+                   (__builtin_amdgcn_ballot_w64(small) != 0 ? GDRNPP_SPLIT2_SMALL_ROWS : 0);
+  if (word && lane == 0) atomicOr(range_flag ? range_flag : &g_split2_range_word, word);
+}
+
+template <int EPI, int IW, bool GNS>
+int launch_window_w(const float* A, const uint4* Wp, const float* bias, float* C, int M, int N, ConvGeom cg, GnStats gn, int* range_flag,
+                    hipStream_t st, const char* what) {
+  const int rc = gdrnpp::ensure_dynamic_lds((const void*)conv3x3_window_kernel<EPI, IW, GNS>, WIN_LDS_BYTES);
+  if (rc) return rc;
+  const long tiles = (long)(M / 256) * (N / BN);
+  GDRNPP_REQUIRE(tiles < (1l << 30), GDRNPP_ELIMIT, "%s: grid too large", what);
+  hipLaunchKernelGGL((conv3x3_window_kernel<EPI, IW, GNS>), dim3((unsigned)tiles), dim3(256), WIN_LDS_BYTES, st, A, Wp, bias, C, M, N, cg, gn,
+                     range_flag);
+  return gdrnpp::check_launch(what);
+}
+
+// the window-staged form serves W = 16 / 32 / 64 with tiles of whole rows of one image
+bool window_form(int H, int W) {
+  return gdrnpp::option_conv3x3_window() && (W == 16 || W == 32 || W == 64) && H % (256 / W) == 0;
+}
+
+template <int EPI, bool GNS>
+int launch_window(const float* A, const uint4* Wp, const float* bias, float* C, int M, int N, ConvGeom cg, GnStats gn, int* range_flag,
+                  hipStream_t st, const char* what) {
+  if (cg.W == 16) return launch_window_w<EPI, 16, GNS>(A, Wp, bias, C, M, N, cg, gn, range_flag, st, what);
+  if (cg.W == 32) return launch_window_w<EPI, 32, GNS>(A, Wp, bias, C, M, N, cg, gn, range_flag, st, what);
+  return launch_window_w<EPI, 64, GNS>(A, Wp, bias, C, M, N, cg, gn, range_flag, st, what);
+}
+
 }  // namespace
 
 extern "C" size_t gdrnpp_pack_weight_f16x2_bytes(int N, int K) {
@@ -494,10 +746,16 @@ extern "C" int gdrnpp_conv3x3_f32_split2(const float* x_nhwc, const void* W_pack
     GDRNPP_REQUIRE(epilogue == EPI_BIAS && (H * W) % 256 == 0 && groups > 0 && Cout == 8 * groups, GDRNPP_ELIMIT,
                    "gdrnpp_conv3x3_f32_split2: GroupNorm statistics need the plain epilogue, H*W %% 256 == 0 and 8 channels per group "
                    "(H*W=%d Cout=%d groups=%d)", H * W, Cout, groups);
+    if (window_form(H, W))
+      return launch_window<EPI_BIAS, true>(x_nhwc, Wp, bias, y_nhwc, (int)M, Cout, cg, GnStats{gn_partials, groups, (H * W) / 256}, range_flag, st, what);
     return launch_one<EPI_BIAS, 1, true>(x_nhwc, Wp, bias, nullptr, nullptr, y_nhwc, (int)M, Cout, 9 * Cin, cg, 0,
                                          GnStats{gn_partials, groups, (H * W) / 256}, range_flag, st, what);
   }
   const GnStats gn{nullptr, 0, 0};
+  if (window_form(H, W)) {
+    if (epilogue == EPI_GELU) return launch_window<EPI_GELU, false>(x_nhwc, Wp, bias, y_nhwc, (int)M, Cout, cg, gn, range_flag, st, what);
+    return launch_window<EPI_BIAS, false>(x_nhwc, Wp, bias, y_nhwc, (int)M, Cout, cg, gn, range_flag, st, what);
+  }
   if (epilogue == EPI_GELU)
     return launch_one<EPI_GELU, 1, false>(x_nhwc, Wp, bias, nullptr, nullptr, y_nhwc, (int)M, Cout, 9 * Cin, cg, 0, gn, range_flag, st, what);
   return launch_one<EPI_BIAS, 1, false>(x_nhwc, Wp, bias, nullptr, nullptr, y_nhwc, (int)M, Cout, 9 * Cin, cg, 0, gn, range_flag, st, what);

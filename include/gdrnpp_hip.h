@@ -61,6 +61,10 @@ const char* gdrnpp_last_error(void);
  *   "upconv_lowres"    0 / 1       read by the callers' routing, not by a launch: a 3x3 convolution behind a bilinear x2 upsampling runs
  *                                   as a tap GEMM at the low resolution + gdrnpp_upconv_gather_gn_nhwc (default 1) or as the upsampling
  *                                   and the convolution of the high-resolution tensor (0)
+ *   "conv3x3_window"   0 / 1       three-product 3x3 / stride 1 / pad 1 convolution (gdrnpp_conv3x3_f32_split2) at W = 16 / 32 / 64 with
+ *                                   H % (256 / W) == 0: a workgroup stages the input window of its 256 pixels once per 16-channel chunk and
+ *                                   reads the nine taps from it (default 1) or stages one operand image per tap (0; every other shape runs
+ *                                   that form).  Same products, another summation order: results differ in their last bits
  * unknown name -> GDRNPP_EINVAL. */
 int gdrnpp_set_option(const char* name, int value);
 /* the value gdrnpp_set_option left (clamped as that entry point clamps it) or the default */
