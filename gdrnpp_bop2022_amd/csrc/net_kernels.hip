@@ -1101,6 +1101,18 @@ int gdrnpp_deconv_col2im_gn_nhwc(const float* cols, const float* bias, float* y,
   return gdrnpp::check_launch("gdrnpp_deconv_col2im_gn_nhwc");
 }
 
+int gdrnpp_groupnorm_stats_nhwc(const float* x, double* gn_partials, int N, int HW, int C, int G, void* stream) {
+  GDRNPP_REQUIRE(x && gn_partials, GDRNPP_EINVAL, "gdrnpp_groupnorm_stats_nhwc: null pointer");
+  GDRNPP_REQUIRE(N > 0 && HW > 0 && C > 0 && G > 0 && C % G == 0, GDRNPP_EINVAL, "gdrnpp_groupnorm_stats_nhwc: N=%d HW=%d C=%d G=%d", N, HW, C,
+                 G);
+  const int cpg = C / G, Q = C / 4;
+  GDRNPP_REQUIRE(C % 4 == 0 && cpg % 4 == 0 && Q <= 256 && 256 % Q == 0 && G <= 64 && N <= 65535, GDRNPP_ELIMIT,
+                 "gdrnpp_groupnorm_stats_nhwc: unsupported shape C=%d G=%d N=%d", C, G, N);
+  const int P = HW >= 1024 ? 64 : (HW >= 64 ? 8 : 1);      // = gdrnpp_groupnorm_workspace_bytes / gdrnpp_groupnorm_act_nhwc
+  hipLaunchKernelGGL(gn_stats_kernel, dim3(P, N), dim3(256), sizeof(double) * 512, (hipStream_t)stream, x, gn_partials, HW, C, G, P);
+  return gdrnpp::check_launch("gdrnpp_groupnorm_stats_nhwc");
+}
+
 int gdrnpp_groupnorm_apply_nhwc(const float* x, const double* partials, int P, const float* gamma, const float* beta,
                                 float* y, int N, int HW, int C, int G, float eps, int act_gelu, void* stream) {
   GDRNPP_REQUIRE(x && partials && gamma && beta && y, GDRNPP_EINVAL, "gdrnpp_groupnorm_apply_nhwc: null pointer");

@@ -69,6 +69,8 @@ def _cl(x):
 
 
 def upsample2x(layer: nn.Module, x: torch.Tensor) -> torch.Tensor:
+    if _train_ok(x) and x.shape[1] % 4 == 0:
+        return Upsample2x.apply(_cl(x))
     if enabled_for(x) and x.shape[1] % 4 == 0:
         return hip_lib.upsample_bilinear2x(_cl(x))
     _fallback("upsample2x: C % 4 != 0", x)
@@ -87,7 +89,10 @@ def _exact_gelu_or_none(act: nn.Module | None) -> bool:
 
 
 def groupnorm_act(gn: nn.GroupNorm, act: nn.Module | None, x: torch.Tensor) -> torch.Tensor:
-    """GroupNorm followed by ``act`` (fused when act is the exact GELU or None)."""
+    """GroupNorm followed by ``act`` (fused when act is the exact GELU or None).  With gradients enabled and
+    ``set_train_kernels(True)`` the pair is ``GroupNormAct``."""
+    if isinstance(gn, nn.GroupNorm) and _gn_train_ok(gn, x) and _exact_gelu_or_none(act):
+        return GroupNormAct.apply(_cl(x), gn.weight, gn.bias, gn.num_groups, gn.eps, act is not None)
     if isinstance(gn, nn.GroupNorm) and _gn_ok(gn, x) and _exact_gelu_or_none(act):
         return hip_lib.groupnorm_act(_cl(x), gn.weight, gn.bias, gn.num_groups, gn.eps, gelu=act is not None)
     _fallback("groupnorm_act: " + type(gn).__name__ + " / activation outside the HIP kernel", x)
@@ -131,7 +136,10 @@ def _dwconv_hip_ok(conv: nn.Conv2d, x: torch.Tensor) -> bool:
 
 # Training: layers that have a backward on this library's kernels take it under autograd when this switch is on (off by default:
 # with it off a forward under enable_grad runs PyTorch's operators, as it always has).  So far: dwconv_ln (DwConvLN) and convnext_mlp
-# (ConvNeXtMlp) — with both, a ConvNeXt block trains without a kernel that is not this library's.
+# (ConvNeXtMlp) — with both, a ConvNeXt block trains without a kernel that is not this library's — and the geometry head's layers:
+# conv3x3_groupnorm_act (Conv3x3GnAct), conv_transpose2d_groupnorm_act (ConvTranspose2dGn), groupnorm_act (GroupNormAct) and
+# upsample2x (Upsample2x).  The head's 1x1 output layer, the stem and downsample layers, the ResNet path and Patch-PnP keep
+# PyTorch's graph.
 _TRAIN_KERNELS = False
 
 
@@ -166,6 +174,128 @@ class DwConvLN(torch.autograd.Function):
             return (None,) * 7
         dx, dw, db, dg, dbeta = hip_lib.dwconv7x7_ln_backward(x, weight, bias, ln_weight, ln_bias, ctx.eps, _cl(grad_y), want=want, w49c=w49c)
         return dx, dw, None, db, dg, dbeta, None
+
+
+def _train_ok(x: torch.Tensor) -> bool:
+    """The part of every training guard that does not depend on the layer: switch on, gradients enabled, a 4-D fp32 device tensor."""
+    return _TRAIN_KERNELS and _ENABLED and torch.is_grad_enabled() and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4
+
+
+def _gn_train_shape_ok(gn: nn.GroupNorm, n: int) -> bool:
+    """Shapes ``gdrnpp_groupnorm_act_backward`` takes (those of ``_gn_ok``) for ``n`` images."""
+    c, g = gn.num_channels, gn.num_groups
+    q = c // 4
+    return (gn.affine and c % 4 == 0 and (c // g) % 4 == 0 and q <= 256 and 256 % q == 0 and g <= 64 and 0 < n <= 65535
+            and gn.weight.is_cuda and gn.weight.dtype == torch.float32)
+
+
+def _gn_train_ok(gn: nn.GroupNorm, x: torch.Tensor) -> bool:
+    return _train_ok(x) and x.shape[1] == gn.num_channels and _gn_train_shape_ok(gn, x.shape[0])
+
+
+def _conv_gn_train_ok(conv: nn.Conv2d, gn: nn.GroupNorm, act, x: torch.Tensor) -> bool:
+    return (_train_ok(x) and isinstance(conv, nn.Conv2d) and isinstance(gn, nn.GroupNorm) and _gn_train_shape_ok(gn, x.shape[0])
+            and conv.kernel_size == (3, 3) and conv.stride == (1, 1) and conv.padding == (1, 1) and conv.dilation == (1, 1)
+            and conv.groups == 1 and conv.padding_mode == "zeros" and conv.in_channels % 128 == 0 and conv.out_channels % 128 == 0
+            and x.shape[1] == conv.in_channels and gn.num_channels == conv.out_channels and _exact_gelu_or_none(act)
+            and conv.weight.is_cuda and conv.weight.dtype == torch.float32 and x.shape[0] * x.shape[2] * x.shape[3] < (1 << 31) - 4096)
+
+
+class Conv3x3GnAct(torch.autograd.Function):
+    """The head's [Conv2d 3x3/1/1, GroupNorm(, GELU)] with its backward on HIP kernels (csrc/conv_gn_bwd.hip).  x (N,Cin,H,W)
+    channels_last -> y (N,Cout,H,W) channels_last.  The forward runs the fp32-MFMA convolution (``gdrnpp_conv_bias_act_f32``: the six-product kernel is
+    past the gradient tests' bar at this depth), the GroupNorm statistics and the apply pass; saved are x, the convolution's output z and the statistics' partial sums — y and the pre-activation are recomputed."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, gn_weight, gn_bias, groups, eps, gelu):
+        z = hip_lib.conv3x3_f32_mfma(x, hip_lib.conv3x3_weight_kn(weight), bias)      # operand made per forward: the weight changes every step
+        y, part = hip_lib.groupnorm_act_train(z, gn_weight, gn_bias, groups, eps, gelu)
+        ctx.save_for_backward(x, z, part, weight, gn_weight, gn_bias)
+        ctx.gn = (groups, eps, gelu)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_y):
+        x, z, part, weight, gn_weight, gn_bias = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        dx = dw = db = dg = dbeta = None
+        if any(need[:5]):
+            dz, dg, dbeta = hip_lib.groupnorm_act_backward(z, part, gn_weight, gn_bias, *ctx.gn, _cl(grad_y), want=(any(need[:3]), need[3], need[4]))
+            if any(need[:3]):
+                dx, dw, db = hip_lib.conv3x3_backward(x, weight, dz, want=need[:3])
+        return dx, dw, db, dg, dbeta, None, None, None
+
+
+class GroupNormAct(torch.autograd.Function):
+    """GroupNorm(, GELU) alone with its backward on ``gdrnpp_groupnorm_act_backward``: the norm behind the head's ConvTranspose2d and
+    behind a convolution outside ``Conv3x3GnAct``.  Saved: the input and the statistics' partial sums."""
+
+    @staticmethod
+    def forward(ctx, z, gn_weight, gn_bias, groups, eps, gelu):
+        y, part = hip_lib.groupnorm_act_train(z, gn_weight, gn_bias, groups, eps, gelu)
+        ctx.save_for_backward(z, part, gn_weight, gn_bias)
+        ctx.gn = (groups, eps, gelu)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_y):
+        z, part, gn_weight, gn_bias = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        grads = (None,) * 3
+        if any(need[:3]):
+            grads = hip_lib.groupnorm_act_backward(z, part, gn_weight, gn_bias, *ctx.gn, _cl(grad_y), want=need[:3])
+        return (*grads, None, None, None)
+
+
+class ConvTranspose2dGn(torch.autograd.Function):
+    """The head's [ConvTranspose2d, GroupNorm(, GELU)] with its backward on HIP kernels: the im2col gather, the exact-f32 product for dx,
+    the TN GEMM for the weight gradient, ``gdrnpp_groupnorm_act_backward`` for the norm.  Saved: x, the transposed convolution's
+    output z and the statistics' partial sums (left by the forward's col2im gather)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, gn_weight, gn_bias, geom, groups, eps, gelu):
+        z, part = hip_lib.conv_transpose2d_train(x, weight, bias, *geom, groups)
+        ctx.save_for_backward(x, z, part, weight, gn_weight, gn_bias)
+        ctx.geom, ctx.gn = geom, (groups, eps, gelu)
+        return hip_lib.groupnorm_apply(z, part, gn_weight, gn_bias, groups, eps, gelu)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_y):
+        x, z, part, weight, gn_weight, gn_bias = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        dx = dw = db = dg = dbeta = None
+        if any(need[:5]):
+            dz, dg, dbeta = hip_lib.groupnorm_act_backward(z, part, gn_weight, gn_bias, *ctx.gn, _cl(grad_y), want=(any(need[:3]), need[3], need[4]))
+            if any(need[:3]):
+                dx, dw, db = hip_lib.conv_transpose2d_backward(x, weight, dz, *ctx.geom, want=need[:3])
+        return dx, dw, db, dg, dbeta, None, None, None, None
+
+
+def _deconv_gn_train_ok(deconv: nn.ConvTranspose2d, gn: nn.GroupNorm, act, x: torch.Tensor) -> bool:
+    ks = deconv.kernel_size[0] if isinstance(deconv, nn.ConvTranspose2d) else 0
+    return (_train_ok(x) and isinstance(deconv, nn.ConvTranspose2d) and isinstance(gn, nn.GroupNorm) and _gn_train_shape_ok(gn, x.shape[0])
+            and deconv.kernel_size[0] == deconv.kernel_size[1] and deconv.stride[0] == deconv.stride[1]
+            and deconv.padding[0] == deconv.padding[1] and deconv.output_padding[0] == deconv.output_padding[1]
+            and deconv.output_padding[0] < deconv.stride[0] and deconv.dilation == (1, 1) and deconv.groups == 1
+            and x.shape[1] == deconv.in_channels and deconv.in_channels % 128 == 0 and (ks * ks * deconv.out_channels) % 128 == 0
+            and gn.num_channels == deconv.out_channels and _exact_gelu_or_none(act) and deconv.weight.is_cuda
+            and deconv.weight.dtype == torch.float32 and x.shape[0] * x.shape[2] * x.shape[3] * ks * ks * deconv.out_channels < (1 << 31))
+
+
+class Upsample2x(torch.autograd.Function):
+    """nn.UpsamplingBilinear2d(2) with its adjoint on ``gdrnpp_upsample_bilinear2x_backward_nhwc``; nothing is saved."""
+
+    @staticmethod
+    def forward(ctx, x):
+        return hip_lib.upsample_bilinear2x(x)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_y):
+        return hip_lib.upsample_bilinear2x_backward(_cl(grad_y))
 
 
 def _dwconv_train_ok(conv: nn.Conv2d, ln: nn.LayerNorm, x: torch.Tensor) -> bool:
@@ -495,7 +625,10 @@ def conv_transpose2d(deconv: nn.ConvTranspose2d, x: torch.Tensor) -> torch.Tenso
 def conv_transpose2d_groupnorm_act(deconv: nn.ConvTranspose2d, gn: nn.GroupNorm, act: nn.Module | None, x: torch.Tensor):
     """The head's [ConvTranspose2d, GroupNorm(, GELU)] triple with the GroupNorm statistics taken by the col2im gather
     (``hip_lib.conv_transpose2d_groupnorm_act``).  Returns None when the layers are outside that form; the caller then runs them
-    one by one."""
+    one by one.  With gradients enabled and ``set_train_kernels(True)`` the triple is ``ConvTranspose2dGn``."""
+    if _deconv_gn_train_ok(deconv, gn, act, x):
+        geom = (deconv.kernel_size[0], deconv.stride[0], deconv.padding[0], deconv.output_padding[0])
+        return ConvTranspose2dGn.apply(_cl(x), deconv.weight, deconv.bias, gn.weight, gn.bias, geom, gn.num_groups, gn.eps, act is not None)
     if not (_CONV_GN_FUSED and _deconv_split_ok(deconv, x) and isinstance(gn, nn.GroupNorm) and gn.num_channels == deconv.out_channels
             and _gn_ok(gn, x) and _exact_gelu_or_none(act)):
         return None
@@ -517,7 +650,9 @@ def set_conv_gn_fused(flag: bool) -> None:
 def conv3x3_groupnorm_act(conv: nn.Conv2d, gn: nn.GroupNorm, act: nn.Module | None, x: torch.Tensor):
     """The head's [Conv2d 3x3/1/1, GroupNorm(, GELU)] triple with the GroupNorm statistics taken in the convolution's
     epilogue (``hip_lib.conv3x3_groupnorm_act``).  Returns None when the layers or the shape are outside that form; the
-    caller then runs them one by one."""
+    caller then runs them one by one.  With gradients enabled and ``set_train_kernels(True)`` the triple is ``Conv3x3GnAct``."""
+    if _conv_gn_train_ok(conv, gn, act, x):
+        return Conv3x3GnAct.apply(_cl(x), conv.weight, conv.bias, gn.weight, gn.bias, gn.num_groups, gn.eps, act is not None)
     if not (_CONV_GN_FUSED and _CONV_SPLIT and _MLP_GEMM == "split" and enabled_for(x) and conv.kernel_size == (3, 3) and conv.stride == (1, 1)
             and conv.padding == (1, 1) and conv.dilation == (1, 1) and conv.groups == 1 and conv.padding_mode == "zeros"
             and conv.in_channels % 32 == 0 and conv.out_channels % 128 == 0 and gn.affine
@@ -552,7 +687,8 @@ def upsample2x_conv3x3_groupnorm_act(conv: nn.Conv2d, gn: nn.GroupNorm, act: nn.
     """[UpsamplingBilinear2d(2), Conv2d 3x3/1/1, GroupNorm(, GELU)] on the low-resolution input ``x``: the nine tap products at
     the low resolution (a quarter of the convolution's matrix work), then a gather that interpolates and sums them and takes
     the GroupNorm statistics.  Returns None outside the form of ``conv3x3_groupnorm_act`` (or with the library option
-    "upconv_lowres" at 0, or below the minimum size); the caller then runs the layers one by one."""
+    "upconv_lowres" at 0, or below the minimum size); the caller then runs the layers one by one.  Under autograd too (``enabled_for``
+    is false there): with ``set_train_kernels(True)`` the two layers are then ``Upsample2x`` and ``Conv3x3GnAct``."""
     if not (_CONV_GN_FUSED and _CONV_SPLIT and _MLP_GEMM == "split" and enabled_for(x) and isinstance(conv, nn.Conv2d)
             and isinstance(gn, nn.GroupNorm) and conv.kernel_size == (3, 3) and conv.stride == (1, 1)
             and conv.padding == (1, 1) and conv.dilation == (1, 1) and conv.groups == 1 and conv.padding_mode == "zeros"

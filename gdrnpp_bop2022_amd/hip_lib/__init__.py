@@ -25,9 +25,12 @@ from .gemm import (A_F16X2_ROWS, C_F16X2_ROWS, X3, conv2d_f32_split, conv3x3_f32
                    packed_rows_in_range, unpack_weight_bf16x3, unpack_weight_f16x2, upsample2x_conv3x3_groupnorm_act, upsample2x_conv3x3_raw)
 from .gemm import (colsum_f32, convnext_mlp_backward, convnext_mlp_forward_train, gelu_f32, gemm_tn_f32, linear_f32_exact, mlp_bwd_act_,  # noqa: F401
                    pack_weight_bf16x3_t)
+from .gemm import (conv3x3_backward, conv3x3_f32_mfma, conv3x3_weight_kn, conv3x3_weight_kn_flipped, conv3x3_wgrad_f32,  # noqa: F401
+                   conv_transpose2d_backward, conv_transpose2d_train, deconv_im2col, deconv_weight_kn, groupnorm_apply)
 from .net import (DENSE_MASK_TYPES, DENSE_SUMS, DENSE_XYZ_TYPES, LOSS_MASKS, PM_TYPES, POINT_PNP_TILE, ROT_DIMS, ROT_MODES, T_MODES,  # noqa: F401
-                  bias_act_nhwc_, dwconv7x7_ln, dwconv7x7_ln_backward, gdrn_dense_losses, gdrn_dense_losses_backward, gdrn_pose_losses, groupnorm_act, head_tail_nhwc,
-                  layernorm_nhwc, pnp_fc_heads, pnp_fc_heads_pose, point_pnp_fc, point_pnp_pool, stem_conv4x4_ln, upsample_bilinear2x)
+                  bias_act_nhwc_, dwconv7x7_ln, dwconv7x7_ln_backward, gdrn_dense_losses, gdrn_dense_losses_backward, gdrn_pose_losses, groupnorm_act,
+                  groupnorm_act_backward, groupnorm_act_train, head_tail_nhwc,
+                  layernorm_nhwc, pnp_fc_heads, pnp_fc_heads_pose, point_pnp_fc, point_pnp_pool, stem_conv4x4_ln, upsample_bilinear2x, upsample_bilinear2x_backward)
 from .net import (RANGER_COEFS, RANGER_LONG_ROW, RANGER_LOOKAHEAD, RANGER_NAN_TO_NUM, RANGER_RECTIFIED, RANGER_TENSOR, RANGER_TILE,  # noqa: F401
                   RANGER_WORK, RangerTables, ranger_plan, ranger_same_layout, ranger_step, ranger_tensor_ok)
 from .pose import (GT_INFO_COLUMNS, XYZ_CROP_COLUMNS, MeshSet, bop_errors, decode_correspondences, depth_refine, epnp_batched, epnp_ransac,  # noqa: F401

@@ -499,3 +499,144 @@ def convnext_mlp_backward(x2d, pre, w1, w2, b2, gamma, grad_y, want=(True,) * 6)
         if not w_dg:
             dgamma = None
     return dx, dw1, db1, dw2, db2, dgamma
+
+
+# ---- training: the geometry head's [conv3x3, GroupNorm(, GELU)] under autograd (csrc/conv_gn_bwd.hip) ----------------------------
+# The two forward-shaped convolutions (z, and dx = conv3x3(dz, W')) have a depth of 9 Cin = 1152 - 2304.  Measured on an MI355X, error
+# over the gradient tests' bar at depths 1152 / 2304 / 2304 (tools/head_bwd_microbench.py --engine-errors, profiles/head_bwd_microbench.json):
+#   six-product conv3x3 on its 256-row tiles (what a training batch runs)   1.87 / 2.49 / 2.37     1.01 ms per 48-ROI layer
+#   six-product conv3x3 as dispatched at those small sizes (K cut in chunks) 0.34 / 0.40 / 0.42
+#   gdrnpp_conv_bias_act_f32 (fp32 MFMA, two-level fp32 sums)                0.42 / 0.40 / 0.42     2.59 ms
+#   an implicit GEMM with gemm_rows' fp64 carries, written for this and not kept  0.39 / 0.39 / 0.32   2.50 ms
+# So both run on gdrnpp_conv_bias_act_f32 as it is: inside the bar whatever the launch size, and within 5 % of the kernel not kept.
+_ACT_NONE = DEFINES["GDRNPP_ACT_NONE"]
+
+
+def conv3x3_weight_kn(weight):
+    """nn.Conv2d weight [Cout,Cin,3,3] -> the forward operand of ``conv3x3_f32_mfma``: f32[9 Cin, Cout], row (ky 3 + kx) Cin + ci."""
+    cout, cin = weight.shape[:2]
+    return weight.detach().permute(2, 3, 1, 0).reshape(9 * cin, cout).contiguous()
+
+
+def conv3x3_weight_kn_flipped(weight):
+    """nn.Conv2d weight [Cout,Cin,3,3] -> the data-gradient operand W'[(ky 3 + kx) Cout + co][ci] = W[co][ci][2-ky][2-kx], f32[9 Cout, Cin]."""
+    cout, cin = weight.shape[:2]
+    return weight.detach().flip(2, 3).permute(2, 3, 0, 1).reshape(9 * cout, cin).contiguous()
+
+
+def conv3x3_f32_mfma(x_cl, weight_kn, bias=None):
+    """3x3 / stride 1 / zero pad 1 convolution of a channels_last tensor [N,Cin,H,W] with ``weight_kn`` f32[9 Cin, Cout]
+    (``conv3x3_weight_kn``) on the exact-f32 matrix instruction (``gdrnpp_conv_bias_act_f32`` without activation or residual: fp32
+    sums in a fixed two-level order, bit-reproducible) -> channels_last [N,Cout,H,W].  Cin % 4 == 0, Cout % 4 == 0."""
+    n, cin, h, w = channels_last_f32(x_cl, "conv3x3_f32_mfma")
+    if weight_kn.dim() != 2 or weight_kn.shape[0] != 9 * cin:
+        raise RuntimeError(f"conv3x3_f32_mfma: weight_kn must be f32[{9 * cin},Cout], got {tuple(weight_kn.shape)}")
+    cout = weight_kn.shape[1]
+    if cin % 4 or cout % 4:
+        raise RuntimeError(f"conv3x3_f32_mfma: Cin={cin} and Cout={cout} must be multiples of 4")
+    out = torch.empty((n, cout, h, w), dtype=torch.float32, device=x_cl.device, memory_format=torch.channels_last)
+    launch("gdrnpp_conv_bias_act_f32", x_cl.data_ptr(), cin, 0, f32_ptr(weight_kn, "weight_kn"), cout, opt_f32_ptr(bias, "bias"), None, 0, 0,
+           out.data_ptr(), cout, 0, 0, 0, n, h, w, cin, cout, 3, 1, _ACT_NONE, 0.0,
+           timed=("mfma_f32:conv3x3", 2.0 * n * h * w * cout * 9 * cin, 4.0 * n * h * w * (cin + cout) + 36.0 * cin * cout))
+    return out
+
+
+def conv3x3_wgrad_f32(dz_cl, x_cl):
+    """dW f32[Cout,Cin,3,3] = the weight gradient of a 3x3 / stride 1 / zero pad 1 convolution for dz [N,Cout,H,W] and its input x
+    [N,Cin,H,W], both channels_last (``gdrnpp_conv3x3_wgrad_f32``: implicit TN GEMM on the exact-f32 matrix instruction, fixed slots,
+    fp64 finalize, one rounding).  Cin % 128 == 0, Cout % 128 == 0."""
+    n, cout, h, w = channels_last_f32(dz_cl, "conv3x3_wgrad_f32")
+    xn, cin, xh, xw = channels_last_f32(x_cl, "conv3x3_wgrad_f32")
+    if (xn, xh, xw) != (n, h, w):
+        raise RuntimeError(f"conv3x3_wgrad_f32: x {tuple(x_cl.shape)} does not fit dz {tuple(dz_cl.shape)}")
+    nbytes = load().gdrnpp_conv3x3_wgrad_f32_workspace_bytes(n, h, w, cin, cout)
+    if nbytes == 0:
+        raise RuntimeError(f"conv3x3_wgrad_f32: Cin={cin} and Cout={cout} must be multiples of 128")
+    ws = torch.empty((nbytes // 8,), dtype=torch.float64, device=x_cl.device)
+    dw = torch.empty((cout, cin, 3, 3), dtype=torch.float32, device=x_cl.device)
+    launch("gdrnpp_conv3x3_wgrad_f32", dz_cl.data_ptr(), x_cl.data_ptr(), dw.data_ptr(), n, h, w, cin, cout, ws.data_ptr(), nbytes,
+           timed=("conv3x3_wgrad", 2.0 * n * h * w * cout * 9 * cin, 4.0 * n * h * w * (cin + cout) + 36.0 * cin * cout))
+    return dw
+
+
+def conv3x3_backward(x_cl, weight, dz_cl, want=(True, True, True)):
+    """Gradients of z = conv3x3(x, weight) + bias for dz = dL/dz -> (dx, dweight, dbias).  ``want``: three flags in that order — an
+    entry is None where its flag is false and its launches are left out; the others keep their bits.  dx = conv3x3(dz, W') on
+    ``conv3x3_f32_mfma`` with the flipped, transposed weight formed here (the weight changes every step), dweight =
+    ``conv3x3_wgrad_f32``, dbias = ``colsum_f32(dz)``."""
+    want = tuple(bool(f) for f in want)
+    if len(want) != 3 or not any(want):
+        raise RuntimeError("conv3x3_backward: want must hold three flags, at least one of them set")
+    n, cout, h, w = dz_cl.shape
+    dx = conv3x3_f32_mfma(dz_cl, conv3x3_weight_kn_flipped(weight)) if want[0] else None
+    dw = conv3x3_wgrad_f32(dz_cl, x_cl) if want[1] else None
+    db = colsum_f32(dz_cl.permute(0, 2, 3, 1).reshape(n * h * w, cout))[1] if want[2] else None
+    return dx, dw, db
+
+
+def deconv_weight_kn(weight):
+    """nn.ConvTranspose2d weight [Cin,Cout,KS,KS] -> Wmat f32[KS KS Cout, Cin], rows (ky, kx, co): nn.Linear's [N,K] form of the
+    forward product cols = x Wmat^T and the [K,N] form of the data gradient dx = dcols Wmat."""
+    cin, cout, kh, kw = weight.shape
+    return weight.detach().permute(2, 3, 1, 0).reshape(kh * kw * cout, cin).contiguous()
+
+
+def deconv_im2col(dy_cl, h: int, w: int, ks: int, stride: int, pad: int, out_pad: int):
+    """``gdrnpp_deconv_im2col_nhwc``: dcols f32[N h w, ks ks Cout] from dy [N,Cout,OH,OW] channels_last, the adjoint of the col2im gather
+    of ``conv_transpose2d_f32_split`` (values copied, zero where a tap leaves dy)."""
+    n, cout, oh, ow = channels_last_f32(dy_cl, "deconv_im2col")
+    if (oh, ow) != ((h - 1) * stride - 2 * pad + ks + out_pad, (w - 1) * stride - 2 * pad + ks + out_pad):
+        raise RuntimeError(f"deconv_im2col: dy {tuple(dy_cl.shape)} is not the output of a {h} x {w} input with k={ks} s={stride} p={pad} op={out_pad}")
+    dcols = torch.empty((n * h * w, ks * ks * cout), dtype=torch.float32, device=dy_cl.device)
+    launch("gdrnpp_deconv_im2col_nhwc", dy_cl.data_ptr(), dcols.data_ptr(), n, h, w, cout, ks, stride, pad, out_pad,
+           timed=("hbm:deconv_im2col", 0.0, 4.0 * (dy_cl.numel() + dcols.numel())))
+    return dcols
+
+
+def conv_transpose2d_train(x_cl, weight, bias, ks: int, stride: int, pad: int, out_pad: int, groups: int):
+    """nn.ConvTranspose2d of a channels_last tensor for training -> (z channels_last [N,Cout,OH,OW], GroupNorm(groups) partial sums
+    f64[N,P,groups,2]): cols = x Wmat^T through ``_tail_product`` (six products up to a depth of 256, exact-f32 beyond), then the
+    col2im gather that also leaves the statistics (``gdrnpp_deconv_col2im_gn_nhwc``)."""
+    n, cin, h, w = channels_last_f32(x_cl, "conv_transpose2d_train")
+    cout = weight.shape[1]
+    cols = _tail_product(x_cl.permute(0, 2, 3, 1).reshape(n * h * w, cin), deconv_weight_kn(weight))
+    oh, ow = (h - 1) * stride - 2 * pad + ks + out_pad, (w - 1) * stride - 2 * pad + ks + out_pad
+    z = torch.empty((n, cout, oh, ow), dtype=torch.float32, device=x_cl.device, memory_format=torch.channels_last)
+    P = load().gdrnpp_groupnorm_workspace_bytes(n, oh * ow, groups) // (16 * n * groups)
+    part = torch.empty((n, P, groups, 2), dtype=torch.float64, device=x_cl.device)
+    launch("gdrnpp_deconv_col2im_gn_nhwc", cols.data_ptr(), opt_f32_ptr(bias, "bias"), z.data_ptr(), part.data_ptr(), n, h, w, cout, ks, stride,
+           pad, out_pad, groups)
+    return z, part
+
+
+def conv_transpose2d_backward(x_cl, weight, dz_cl, ks: int, stride: int, pad: int, out_pad: int, want=(True, True, True)):
+    """Gradients of z = conv_transpose2d(x, weight) + bias for dz = dL/dz -> (dx, dweight [Cin,Cout,ks,ks], dbias): the im2col gather,
+    then dx = ``linear_f32_exact(dcols, Wmat)`` and dweight = ``gemm_tn_f32(x, dcols)``; dbias = ``colsum_f32(dz)``.  ``want``: three
+    flags in that order — an entry is None where its flag is false and its launches are left out.  Cin % 128 == 0 and
+    ks ks Cout % 128 == 0."""
+    want = tuple(bool(f) for f in want)
+    if len(want) != 3 or not any(want):
+        raise RuntimeError("conv_transpose2d_backward: want must hold three flags, at least one of them set")
+    n, cin, h, w = channels_last_f32(x_cl, "conv_transpose2d_backward")
+    cout = weight.shape[1]
+    if tuple(weight.shape) != (cin, cout, ks, ks) or cin % 128 or (ks * ks * cout) % 128:
+        raise RuntimeError(f"conv_transpose2d_backward: weight {tuple(weight.shape)} for Cin={cin}, ks={ks}: Cin and ks ks Cout must be multiples of 128")
+    dx = dw = db = None
+    if want[0] or want[1]:
+        dcols = deconv_im2col(dz_cl, h, w, ks, stride, pad, out_pad)
+        if want[0]:
+            dx2d = linear_f32_exact(dcols, deconv_weight_kn(weight), weight_kn=True)
+            dx = dx2d.view(n, h, w, cin).permute(0, 3, 1, 2)
+        if want[1]:
+            g = gemm_tn_f32(x_cl.permute(0, 2, 3, 1).reshape(n * h * w, cin), dcols)
+            dw = g.view(cin, ks, ks, cout).permute(0, 3, 1, 2).contiguous()
+    if want[2]:
+        oh, ow = dz_cl.shape[2:]
+        db = colsum_f32(dz_cl.permute(0, 2, 3, 1).reshape(n * oh * ow, cout))[1]
+    return dx, dw, db
+
+
+def groupnorm_apply(z_cl, part, gamma, beta, groups: int, eps: float = 1e-5, gelu: bool = False):
+    """y = GroupNorm(groups)(z) [-> GELU] from the partial sums f64[N,P,groups,2] a GEMM's epilogue or gather left (``gdrnpp_groupnorm_apply_nhwc``)."""
+    n, c, h, w = channels_last_f32(z_cl, "groupnorm_apply")
+    return _groupnorm_apply(z_cl, part, int(part.shape[1]), gamma, beta, n, h * w, c, groups, eps, gelu)

@@ -82,6 +82,59 @@ def groupnorm_act(x, gamma, beta, groups: int, eps: float = 1e-5, gelu: bool = F
     return y
 
 
+def upsample_bilinear2x_backward(grad_y):
+    """``gdrnpp_upsample_bilinear2x_backward_nhwc``: dx (N,C,H,W) channels_last of ``upsample_bilinear2x`` for grad_y (N,C,2H,2W)."""
+    n, c, oh, ow = grad_y.shape
+    if oh % 2 or ow % 2:
+        raise RuntimeError(f"upsample_bilinear2x_backward: grad_y must be (N,C,2H,2W), got {tuple(grad_y.shape)}")
+    dx = torch.empty((n, c, oh // 2, ow // 2), dtype=torch.float32, device=grad_y.device, memory_format=torch.channels_last)
+    launch("gdrnpp_upsample_bilinear2x_backward_nhwc", nhwc_ptr(grad_y, "grad_y"), dx.data_ptr(), n, oh // 2, ow // 2, c,
+           timed=("hbm:upsample2x_bwd", 0.0, 5.0 * grad_y.numel()))
+    return dx
+
+
+def groupnorm_act_train(z, gamma, beta, groups: int, eps: float = 1e-5, gelu: bool = False):
+    """GroupNorm(groups) [+ exact GELU] of z (N,C,H,W) channels_last for training -> (y, partials f64[N,P,groups,2]): the statistics
+    pass alone (``gdrnpp_groupnorm_stats_nhwc``), then ``gdrnpp_groupnorm_apply_nhwc``.  z and the partials are what
+    ``groupnorm_act_backward`` takes."""
+    n, c, h, w = z.shape
+    P = load().gdrnpp_groupnorm_workspace_bytes(n, h * w, groups) // (16 * n * groups)
+    part = torch.empty((n, P, groups, 2), dtype=torch.float64, device=z.device)
+    y = torch.empty_like(z, memory_format=torch.channels_last)
+    launch("gdrnpp_groupnorm_stats_nhwc", nhwc_ptr(z, "z"), part.data_ptr(), n, h * w, c, groups, timed=("hbm:groupnorm_stats", 0.0, 4.0 * z.numel()))
+    launch("gdrnpp_groupnorm_apply_nhwc", z.data_ptr(), part.data_ptr(), P, f32_ptr(gamma, "gamma"), f32_ptr(beta, "beta"), y.data_ptr(), n, h * w, c,
+           groups, float(eps), 1 if gelu else 0, timed=("hbm:groupnorm_apply", 0.0, 8.0 * z.numel()))
+    return y, part
+
+
+def groupnorm_act_backward(z, partials, gamma, beta, groups: int, eps: float, gelu: bool, grad_y, want=(True,) * 3):
+    """``gdrnpp_groupnorm_act_backward``: gradients of y = act(GroupNorm(z)) for grad_y = dL/dy -> (dz, dgamma, dbeta).  z, grad_y
+    (N,C,H,W) channels_last; ``partials`` f64[N,P,groups,2] from the forward.  ``want``: three flags in the order of the result — an
+    entry is None where its flag is false and the launches only it needs are left out.  Fixed summation order: two calls give the
+    same bits."""
+    what = "groupnorm_act_backward"
+    want = tuple(bool(f) for f in want)
+    if len(want) != 3 or not any(want):
+        raise RuntimeError(f"{what}: want must hold three flags, at least one of them set")
+    pz = nhwc_ptr(z, "z")
+    n, c, h, w = z.shape
+    if not isinstance(grad_y, torch.Tensor) or tuple(grad_y.shape) != (n, c, h, w):
+        raise RuntimeError(f"{what}: grad_y must be f32[{n},{c},{h},{w}] as z is, got {tuple(getattr(grad_y, 'shape', ()))}")
+    if partials.dim() != 4 or partials.shape[0] != n or tuple(partials.shape[2:]) != (groups, 2) or gamma.numel() != c or beta.numel() != c:
+        raise RuntimeError(f"{what}: partials must be f64[{n},P,{groups},2], gamma and beta f32[{c}]")
+    nbytes = load().gdrnpp_groupnorm_act_backward_workspace_bytes(n, h * w, c, groups)
+    if nbytes == 0:
+        raise RuntimeError(f"{what}: shape C={c} G={groups} N={n} is outside the kernel")
+    ws = torch.empty((nbytes // 8,), dtype=torch.float64, device=z.device)
+    dz = torch.empty_like(z, memory_format=torch.channels_last) if want[0] else None
+    dgamma, dbeta = (torch.empty((c,), dtype=torch.float32, device=z.device) if f else None for f in want[1:])
+    launch("gdrnpp_groupnorm_act_backward", pz, dev_ptr(partials, torch.float64, "partials"), int(partials.shape[1]), f32_ptr(gamma, "gamma"),
+           f32_ptr(beta, "beta"), nhwc_ptr(grad_y, "grad_y"), dz.data_ptr() if want[0] else None, dgamma.data_ptr() if want[1] else None,
+           dbeta.data_ptr() if want[2] else None, n, h * w, c, groups, float(eps), 1 if gelu else 0, ws.data_ptr(), nbytes,
+           timed=("hbm:groupnorm_bwd", 0.0, 4.0 * z.numel() * (2 + 3 * want[0])))
+    return dz, dgamma, dbeta
+
+
 def bias_act_nhwc_(x_cl, bias, resid=None, relu: bool = True):
     """In place: x = act(x + bias[c] (+ resid)) on a channels_last float32 tensor [N,C,H,W] (C % 4 == 0)."""
     n, c, h, w = channels_last_f32(x_cl, "bias_act_nhwc_")

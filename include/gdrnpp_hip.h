@@ -737,6 +737,48 @@ int gdrnpp_conv3x3_f32_split_gnstats(const float* x_nhwc, const void* W_packed, 
 int gdrnpp_groupnorm_apply_nhwc(const float* x, const double* partials, int P, const float* gamma, const float* beta,
                                 float* y, int N, int HW, int C, int G, float eps, int act_gelu, void* stream);
 
+/* ---- training the geometry head: backward of [conv3x3, GroupNorm(, GELU)], of the bilinear x2 and of the transposed convolution
+ * (csrc/conv_gn_bwd.hip).  The forward-shaped convolutions (the training forward and dx = conv3x3(dz, W')) are
+ * gdrnpp_conv_bias_act_f32 below, whose two-level fp32 sums meet the gradient tests' bar at a depth of 2304.
+ * All tensors NHWC fp32.  No atomics: every sum over pixels goes through workspace slots whose count depends on the shape alone
+ * and is added in slot order in fp64, so two calls give equal bits.  An output given as NULL is not computed, the launches only
+ * it needs are left out and the other outputs keep their bits.  Argument errors return GDRNPP_EINVAL / GDRNPP_ELIMIT with
+ * gdrnpp_last_error text and launch nothing; every *_workspace_bytes query returns 0 for a shape its kernel does not take.
+ *  groupnorm_stats_nhwc : the statistics pass of gdrnpp_groupnorm_act_nhwc alone: gn_partials f64[N, P, G, 2] with P =
+ *                 gdrnpp_groupnorm_workspace_bytes(N, HW, G) / (16 N G); follow with gdrnpp_groupnorm_apply_nhwc.  The training
+ *                 forward keeps z and these partials for the backward.
+ *  groupnorm_act_backward : for y = act(gamma xhat + beta), xhat = (z - mean) rstd over the groups of GroupNorm(G, C, eps), act
+ *                 the exact GELU (act_gelu != 0) or nothing, and grad_y = dL/dy: dz f32[N,HW,C], dgamma, dbeta f32[C] (each may be
+ *                 NULL, not all).  z is the normalised layer's INPUT and gn_partials / P the forward's partial sums as
+ *                 gdrnpp_groupnorm_apply_nhwc takes them: mean and rstd are rebuilt by that kernel's expression, so xhat has the
+ *                 forward's bits; neither y nor the pre-activation is kept.  dA = grad_y gelu'(a), gelu'(x) = Phi(x) + x phi(x);
+ *                 dbeta = sum dA, dgamma = sum dA xhat, dz = rstd (gamma dA - (s1 + xhat s2) / m) with s1 / s2 the group's sums of
+ *                 gamma dA / gamma dA xhat and m = HW C / G.  Shapes of gdrnpp_groupnorm_act_nhwc: C % 4 == 0, (C / G) % 4 == 0,
+ *                 C / 4 divides 256, G <= 64, N <= 65535.
+ *  conv3x3_wgrad_f32 : dW[co][ci][ky][kx] = sum_{n,y,x} dz[n,y,x,co] x[n,y+ky-1,x+kx-1,ci] (zero outside the image), dW
+ *                 f32[Cout,Cin,3,3] contiguous, for dz f32[N,H,W,Cout] and x f32[N,H,W,Cin]; Cin % 128 == 0, Cout % 128 == 0.
+ *                 An implicit TN GEMM on the exact-f32 matrix instruction with gdrnpp_gemm_tn_f32's sums: rows are the N H W
+ *                 pixels in 512-row chunks dealt to at most min(64, 512 / (9 Cin Cout / 128^2)) slots, fp32 chains of at most
+ *                 128 rows carried in fp64, slots added in index order, one rounding.
+ *  upsample_bilinear2x_backward_nhwc : the adjoint of gdrnpp_upsample_bilinear2x_nhwc: dx f32[N,H,W,C] from grad_y
+ *                 f32[N,2H,2W,C], every input pixel summing the output pixels that read it with the forward's own fp32 index and
+ *                 lambda arithmetic, in (row, column) order, in fp64, rounded once.  C % 4 == 0.
+ *  deconv_im2col_nhwc : the adjoint of gdrnpp_deconv_col2im_nhwc: dcols f32[N,H,W,KS*KS,C] with dcols[n,h,w,ky,kx,c] =
+ *                 dy[n, h stride - pad + ky, w stride - pad + kx, c] or 0 outside dy f32[N,OH,OW,C] (values copied, nothing
+ *                 summed).  The transposed convolution's gradients are then two existing products: dx = gdrnpp_linear_f32_exact(dcols,
+ *                 Wmat) with Wmat f32[KS*KS*C, Cin], rows (ky, kx, co), and dW = gdrnpp_gemm_tn_f32(x, dcols).  C % 4 == 0. */
+int gdrnpp_groupnorm_stats_nhwc(const float* x, double* gn_partials, int N, int HW, int C, int G, void* stream);
+size_t gdrnpp_groupnorm_act_backward_workspace_bytes(int N, int HW, int C, int G);
+int gdrnpp_groupnorm_act_backward(const float* z, const double* gn_partials, int P, const float* gamma, const float* beta,
+                                  const float* grad_y, float* dz, float* dgamma, float* dbeta, int N, int HW, int C, int G,
+                                  float eps, int act_gelu, void* workspace, size_t workspace_bytes, void* stream);
+size_t gdrnpp_conv3x3_wgrad_f32_workspace_bytes(int N, int H, int W, int Cin, int Cout);
+int gdrnpp_conv3x3_wgrad_f32(const float* dz, const float* x, float* dW, int N, int H, int W, int Cin, int Cout, void* workspace,
+                             size_t workspace_bytes, void* stream);
+int gdrnpp_upsample_bilinear2x_backward_nhwc(const float* grad_y, float* dx, int N, int H, int W, int C, void* stream);
+int gdrnpp_deconv_im2col_nhwc(const float* dy, float* dcols, int N, int H, int W, int C, int KS, int stride, int pad, int out_pad,
+                              void* stream);
+
 /* ---- three-product form of the split GEMM ("fp16x2"): what hip_layers uses by default for large launches (a3) ----------------
  * Every fp32 operand is written as h + l with h = rn_f16(x), l = rn_f16(x - h): 22 significant bits; the products h*l, l*h, h*h
  * go through v_mfma_f32_32x32x16_f16 with fp32 accumulation — half the matrix work of the six-product form above.  The operand
