@@ -115,19 +115,50 @@ class GDRN_DoubleMask(nn.Module):
         full = out[:, m:2 * m] if self.double_mask else None
         return vis, full, out[:, k:k + 1], out[:, k + 1:k + 2], out[:, k + 2:k + 3], out[:, k + 3:]
 
-    def _fused_tail_ok(self, x, feat, roi_classes, coord2d, roi_extents) -> bool:
-        """The all-NHWC head tail (grouped class-sliced GEMM -> head_tail kernel -> Patch-PnP on the split convolution) covers
-        the GDRNPP BOP configuration: regression xyz, 64 regions, coord2d + region attention into Patch-PnP, no mask attention."""
+    def _tail_config_ok(self, feat, roi_classes, coord2d, roi_extents) -> bool:
+        """The configuration the all-NHWC head tail covers — the GDRNPP BOP one: regression xyz, 64 regions, coord2d + region
+        attention into Patch-PnP, no mask attention — whatever the mode (inference or training) it is asked in."""
         net_cfg = self.cfg.MODEL.POSE_NET
         pn = net_cfg.PNP_NET
-        return (hip_layers.enabled_for(x) and hip_layers.mlp_gemm() == "split" and self.fused_head_tail
-                and self.slice_classes is not None and self.xyz_out_dim == 3 and not self.exact_reference_order and not self.training
+        return (hip_layers.mlp_gemm() == "split" and self.fused_head_tail
+                and self.slice_classes is not None and self.xyz_out_dim == 3 and not self.exact_reference_order
                 and self.region_out_dim == 65 and self.mask_out_dim == (2 if self.double_mask else 1)
                 and pn.WITH_2D_COORD and pn.REGION_ATTENTION and pn.MASK_ATTENTION == "none"
                 and roi_classes is not None and coord2d is not None and roi_extents is not None
                 and self.pnp_net is not None and hasattr(self.pnp_net, "accepts_prepared_input") and self.pnp_net.accepts_prepared_input()
                 and feat.shape[1] % 32 == 0 and (feat.shape[2] * feat.shape[3]) % 256 == 0
                 and feat.shape[0] * feat.shape[2] * feat.shape[3] * feat.shape[1] * 4 < (1 << 32))
+
+    def _fused_tail_ok(self, x, feat, roi_classes, coord2d, roi_extents) -> bool:
+        """The all-NHWC head tail (grouped class-sliced GEMM -> head_tail kernel -> Patch-PnP on the split convolution) for
+        inference: the HIP layers' turn (no autograd), eval mode, the configuration of ``_tail_config_ok``."""
+        return hip_layers.enabled_for(x) and not self.training and self._tail_config_ok(feat, roi_classes, coord2d, roi_extents)
+
+    def _train_tail_ok(self, feat, roi_classes, coord2d, roi_extents) -> bool:
+        """The same tail under autograd (``hip_layers.HeadTail``): ``set_train_kernels(True)``, gradients enabled, the configuration of
+        ``_tail_config_ok`` in either mode, a trunk no deeper than the six-product kernel is measured for."""
+        return (hip_layers.head_tail_train_ok(feat, self.geo_head_net.out_layer)
+                and self._tail_config_ok(feat, roi_classes, coord2d, roi_extents))
+
+    def _train_tail(self, feat, roi_classes, coord2d, roi_extents, pose=None):
+        """``_fused_tail`` under autograd: the two launches of the inference tail inside ``HeadTail`` (their backward on HIP kernels),
+        Patch-PnP on the prepared input through PyTorch's graph."""
+        bs, _, h, wd = feat.shape
+        out, pnp_in, planes = hip_layers.head_tail(self.geo_head_net.out_layer, self._cls_rows, feat, roi_classes, coord2d, roi_extents,
+                                                   self.double_mask)
+        return self._tail_outputs(out, pnp_in, planes, bs, h, wd, self._cls_rows.shape[1], pose)
+
+    def _tail_outputs(self, out, pnp_in, planes, bs, h, wd, n70, pose):
+        """Patch-PnP on the prepared input and the maps of out_dict from the tail's three results."""
+        x96 = pnp_in.view(bs, h, wd, 96).permute(0, 3, 1, 2)        # [B,96,H,W] channels_last view
+        pred_rot_, pred_t_ = self.pnp_net.forward_prepared(x96, pose)
+        planes = planes.view(planes.shape[0], bs, 1, h, wd)
+        k = 2 if self.double_mask else 1
+        maps = {"mask": planes[0], "coor_x": planes[k], "coor_y": planes[k + 1], "coor_z": planes[k + 2],
+                "region": out.view(bs, h, wd, out.shape[1])[..., k + 3:n70].permute(0, 3, 1, 2)}
+        if self.double_mask:
+            maps["full_mask"] = planes[1]
+        return pred_rot_, pred_t_, maps
 
     def _fused_tail(self, feat, roi_classes, coord2d, roi_extents, pose=None):
         """feat [B,256,64,64] (channels_last) -> Patch-PnP outputs and the maps of out_dict, without leaving NHWC:
@@ -153,15 +184,7 @@ class GDRN_DoubleMask(nn.Module):
         x2d = feat.permute(0, 2, 3, 1).reshape(bs * h * wd, ch)     # a view of the NHWC memory
         out = hip_lib.linear_f32_split_grouped(x2d, w_pk, b128, roi_classes.to(torch.int32), h * wd, n_store=(n70 + 3) // 4 * 4)
         pnp_in, planes = hip_lib.head_tail_nhwc(out, coord2d.contiguous(), roi_extents.contiguous().float(), self.double_mask)
-        x96 = pnp_in.view(bs, h, wd, 96).permute(0, 3, 1, 2)        # [B,96,H,W] channels_last view
-        pred_rot_, pred_t_ = self.pnp_net.forward_prepared(x96, pose)
-        planes = planes.view(planes.shape[0], bs, 1, h, wd)
-        k = 2 if self.double_mask else 1
-        maps = {"mask": planes[0], "coor_x": planes[k], "coor_y": planes[k + 1], "coor_z": planes[k + 2],
-                "region": out.view(bs, h, wd, out.shape[1])[..., k + 3:n70].permute(0, 3, 1, 2)}
-        if self.double_mask:
-            maps["full_mask"] = planes[1]
-        return pred_rot_, pred_t_, maps
+        return self._tail_outputs(out, pnp_in, planes, bs, h, wd, n70, pose)
 
     def forward_maps(self, x, roi_classes=None, roi_coord_2d=None, roi_coord_2d_rel=None, roi_extents=None, pose=None):
         """Everything of ``forward`` up to the Patch-PnP outputs: pure PyTorch (also runs on CPU).  ``pose``: the pose request of
@@ -190,6 +213,8 @@ class GDRN_DoubleMask(nn.Module):
             coord2d = roi_coord_2d_rel if pnp_net_cfg.WITH_2D_COORD and pnp_net_cfg.COORD_2D_TYPE == "rel" else roi_coord_2d
             if self._fused_tail_ok(x, feat, sel, coord2d, roi_extents):
                 return self._fused_tail(feat, sel, coord2d, roi_extents, pose)
+            if self._train_tail_ok(feat, sel, coord2d, roi_extents):
+                return self._train_tail(feat, sel, coord2d, roi_extents, pose)
             if hip_layers.enabled_for(x):      # the module-path tail below is PyTorch operators (baddbmm, softmax, cat, gathers)
                 hip_layers.note_foreign_launch("GDRN_DoubleMask.forward_maps: head tail on the module path (configuration outside the fused NHWC tail)")
             if self.class_aware:

@@ -13,6 +13,7 @@ from __future__ import annotations
 
 import torch
 import torch.nn as nn
+import torch.nn.functional as F
 
 from . import hip_layers, weight_cache, x3_policy
 from .. import hip_lib
@@ -308,8 +309,13 @@ class ConvPnPNet(nn.Module):
 
     def forward_prepared(self, x96_cl, pose=None):
         """``x96_cl``: [B, 96, H, W] channels_last, channels 69..95 zero.  First convolution with its weight zero-padded to 96
-        input channels on the implicit-GEMM split kernel, the rest as ``forward``."""
+        input channels on the implicit-GEMM split kernel, the rest as ``forward``.  Under autograd (the prepared input then comes
+        from ``hip_layers.HeadTail``) that kernel has no gradient: the first convolution is PyTorch's on the 69 channels."""
         c0 = self.features[0]
+        if torch.is_grad_enabled():
+            hip_layers.note_foreign_launch("ConvPnPNet.forward_prepared: first convolution as F.conv2d under autograd (conv2d_f32_split has no gradient)")
+            x = F.conv2d(x96_cl[:, :69], c0.weight, None, c0.stride, c0.padding)
+            return self._fc_tail(run_features(self.features[1:], x), pose)
         cache = weight_cache.module_cache(c0)
         def w96(w):
             out = torch.zeros((w.shape[0], 96, 3, 3), dtype=w.dtype, device=w.device)

@@ -138,8 +138,9 @@ def _dwconv_hip_ok(conv: nn.Conv2d, x: torch.Tensor) -> bool:
 # with it off a forward under enable_grad runs PyTorch's operators, as it always has).  So far: dwconv_ln (DwConvLN) and convnext_mlp
 # (ConvNeXtMlp) — with both, a ConvNeXt block trains without a kernel that is not this library's — and the geometry head's layers:
 # conv3x3_groupnorm_act (Conv3x3GnAct), conv_transpose2d_groupnorm_act (ConvTranspose2dGn), groupnorm_act (GroupNormAct) and
-# upsample2x (Upsample2x).  The head's 1x1 output layer, the stem and downsample layers, the ResNet path and Patch-PnP keep
-# PyTorch's graph.
+# upsample2x (Upsample2x), and the head's tail — the class-sliced 1x1 output layer, the class gather, the region softmax, the xyz
+# de-normalisation and the concatenation into Patch-PnP's input (HeadTail).  Patch-PnP's own layers, the stem and downsample layers,
+# the ResNet path and AMP keep PyTorch's graph.
 _TRAIN_KERNELS = False
 
 
@@ -296,6 +297,75 @@ class Upsample2x(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_y):
         return hip_lib.upsample_bilinear2x_backward(_cl(grad_y))
+
+
+_HEAD_TAIL_MAX_DEPTH = 256     # the depth to which the six-product kernel of the forward is measured inside the gradient tests' bar
+
+
+class HeadTail(torch.autograd.Function):
+    """The geometry head's tail with its backward on HIP kernels (csrc/head_tail_bwd.hip): the class-sliced 1x1 output layer, the class
+    gather folded into it, the region softmax, the xyz de-normalisation and the concatenation that forms Patch-PnP's input.
+    feat2d f32[B hw, K] (the NHWC rows of the trunk's result), weight / bias = the output layer's own parameters, cls_rows i64[C, n]
+    (the rows of slice c), sel i32[B], coord2d f32[B,2,H,W], extents f32[B,3] -> (out2d f32[B hw, 128], pnp_in f32[B, hw, 96],
+    planes f32[P, B, hw]) — the two launches of the inference tail, bit for bit, with the sliced, 128-row padded six-product pack built
+    per call (the weights change every step).  Saved: feat2d, out2d, the sliced weight and the small tables; pnp_in is not saved (the
+    backward rebuilds the softmax from out2d) and no copy of feat is made.  The backward runs the tail's adjoint, then the data gradient and the weight / bias gradient as ``needs_input_grad`` asks:
+    a frozen output layer launches no weight-gradient kernel, a feat without gradient no data-gradient kernel."""
+
+    @staticmethod
+    def forward(ctx, feat2d, weight, bias, cls_rows, sel, coord2d, extents, double_mask):
+        w = weight.detach().view(weight.shape[0], -1)[cls_rows].contiguous()      # [C, n, K]
+        b = bias.detach()[cls_rows]                                               # [C, n]
+        C, n, k = w.shape
+        w128 = torch.zeros((C, 128, k), dtype=w.dtype, device=w.device)
+        w128[:, :n] = w
+        b128 = torch.zeros((C, 128), dtype=b.dtype, device=b.device)
+        b128[:, :n] = b
+        hw = coord2d.shape[2] * coord2d.shape[3]
+        out2d = hip_lib.linear_f32_split_grouped(feat2d, hip_lib.pack_weight_bf16x3(w128.view(C * 128, k)), b128, sel, hw, n_store=(n + 3) // 4 * 4)
+        pnp_in, planes = hip_lib.head_tail_nhwc(out2d, coord2d, extents, double_mask)
+        ctx.save_for_backward(feat2d, out2d, w, cls_rows, sel, extents)
+        ctx.layer = (tuple(weight.shape), hw, bool(double_mask))
+        ctx.set_materialize_grads(False)      # an output the loss does not use arrives as None, not as a tensor of zeros
+        return out2d, pnp_in, planes
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_out, g_pnp_in, g_planes):
+        feat2d, out2d, w, cls_rows, sel, extents = ctx.saved_tensors
+        w_shape, hw, double_mask = ctx.layer
+        need = ctx.needs_input_grad
+        dfeat = dw = db = None
+        if any(need[:3]) and not (g_out is None and g_pnp_in is None and g_planes is None):
+            g_out, g_pnp_in, g_planes = (None if g is None else g.contiguous() for g in (g_out, g_pnp_in, g_planes))
+            d_out = hip_lib.head_tail_backward(out2d, extents, double_mask, g_pnp_in, g_planes, g_out)
+            if need[0]:
+                dfeat = hip_lib.grouped_linear_dinput(d_out, w, sel, hw)
+            if need[1] or need[2]:
+                dw, db = hip_lib.grouped_linear_wgrad(d_out, feat2d, sel, cls_rows, w.shape[0], w_shape[0], hw, want=(need[1], need[2]))
+                dw = None if dw is None else dw.view(w_shape)
+        return dfeat, dw, db, None, None, None, None, None
+
+
+def head_tail_train_ok(feat: torch.Tensor, out_layer: nn.Module) -> bool:
+    """Shapes and state ``HeadTail`` takes: switch on, gradients enabled, an fp32 device tensor [B,K,H,W] with K a multiple of 128 up
+    to 256 and H W a multiple of 256, the 1x1 output layer with a bias on the device.  The head's configuration is the caller's to
+    check (GDRN_DoubleMask._tail_config_ok)."""
+    k = feat.shape[1] if feat.dim() == 4 else 0
+    return (_train_ok(feat) and _MLP_GEMM == "split" and isinstance(out_layer, nn.Conv2d) and out_layer.kernel_size == (1, 1)
+            and out_layer.bias is not None and out_layer.in_channels == k and k % 128 == 0 and k <= _HEAD_TAIL_MAX_DEPTH
+            and (feat.shape[2] * feat.shape[3]) % 256 == 0 and 0 < feat.shape[0] <= 65535
+            and feat.shape[0] * feat.shape[2] * feat.shape[3] < (1 << 31) - 128
+            and out_layer.weight.is_cuda and out_layer.weight.dtype == torch.float32)
+
+
+def head_tail(out_layer: nn.Conv2d, cls_rows: torch.Tensor, feat: torch.Tensor, sel: torch.Tensor, coord2d: torch.Tensor,
+              extents: torch.Tensor, double_mask: bool):
+    """``HeadTail`` on the trunk's result feat [B,K,H,W] -> (out2d, pnp_in, planes); after ``head_tail_train_ok``."""
+    bs, ch, h, wd = feat.shape
+    x2d = _cl(feat).permute(0, 2, 3, 1).reshape(bs * h * wd, ch)      # a view of the NHWC memory
+    return HeadTail.apply(x2d, out_layer.weight, out_layer.bias, cls_rows, sel.to(torch.int32).contiguous(), coord2d.contiguous().float(),
+                          extents.contiguous().float(), bool(double_mask))
 
 
 def _dwconv_train_ok(conv: nn.Conv2d, ln: nn.LayerNorm, x: torch.Tensor) -> bool:

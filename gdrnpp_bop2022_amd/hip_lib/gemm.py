@@ -192,6 +192,57 @@ def linear_f32_split_grouped(x2d, weight_packed_stack, bias_stack, group_sel, ro
     return out
 
 
+def _grouped_grad_shapes(what: str, d_out, n_out: int, group_sel, rows_per_group: int):
+    m, pitch = d_out.shape
+    if rows_per_group <= 0 or m % rows_per_group or group_sel.numel() != m // rows_per_group or not 0 < n_out <= pitch:
+        raise RuntimeError(f"{what}: d_out {tuple(d_out.shape)}, n_out={n_out}, {group_sel.numel()} selectors, rows_per_group={rows_per_group} do not fit")
+    return m, pitch
+
+
+def grouped_linear_dinput(d_out, weight_slices, group_sel, rows_per_group: int):
+    """Data gradient of ``linear_f32_split_grouped`` (``gdrnpp_grouped_linear_dinput_f32``): dfeat[m] = d_out[m, :n_out] @
+    W[sel[m // rows_per_group]] -> f32[M, K], for ``weight_slices`` f32[slices, n_out, K] (the sliced weight itself, nothing packed)
+    and ``d_out`` f32[M, pitch], whose columns from n_out on are never used.  One fp32 chain in column order on the exact-f32 matrix
+    instruction.  Rows whose selector is outside [0, slices) come back as NaN."""
+    n_slices, n_out, k = weight_slices.shape
+    m, pitch = _grouped_grad_shapes("grouped_linear_dinput", d_out, n_out, group_sel, rows_per_group)
+    dfeat = torch.empty((m, k), dtype=torch.float32, device=d_out.device)
+    launch("gdrnpp_grouped_linear_dinput_f32", f32_ptr(d_out, "d_out"), pitch, n_out, f32_ptr(weight_slices, "weight_slices"),
+           dev_ptr(group_sel, torch.int32, "group_sel"), n_slices, int(rows_per_group), dfeat.data_ptr(), m, k,
+           timed=("mfma_f32:grouped_dinput", 2.0 * m * n_out * k, 4.0 * m * (72 + k) + 4.0 * n_out * k * group_sel.numel()))
+    return dfeat
+
+
+def grouped_linear_wgrad(d_out, feat2d, group_sel, cls_rows, n_slices: int, out_rows: int, rows_per_group: int, want=(True, True)):
+    """Weight and bias gradient of ``linear_f32_split_grouped`` by slice (``gdrnpp_grouped_linear_wgrad_f32``) -> (dW f32[out_rows, K],
+    db f32[out_rows]), shaped like the layer's own parameters: row cls_rows[c, j] holds channel j of slice c, summed over the groups
+    with selector c in index order (fp64, fixed slots, one rounding).  ``cls_rows`` i64[slices, n_out] on the device.  Rows of a slice
+    no group selects are 0, as are rows ``cls_rows`` does not name; groups with a selector outside [0, slices) are left out.
+    ``want`` = (dW, db): an entry is None where its flag is false, the other keeps its bits; with neither nothing is launched."""
+    want_w, want_b = bool(want[0]), bool(want[1])
+    if not (want_w or want_b):
+        return None, None
+    n_out = cls_rows.shape[1]
+    m, pitch = _grouped_grad_shapes("grouped_linear_wgrad", d_out, n_out, group_sel, rows_per_group)
+    k = feat2d.shape[1]
+    b = m // rows_per_group
+    if feat2d.shape[0] != m or tuple(cls_rows.shape) != (n_slices, n_out):
+        raise RuntimeError(f"grouped_linear_wgrad: feat {tuple(feat2d.shape)} / cls_rows {tuple(cls_rows.shape)} do not fit d_out {tuple(d_out.shape)}")
+    nbytes = load().gdrnpp_grouped_linear_wgrad_f32_workspace_bytes(b, int(rows_per_group), k, n_out)
+    if nbytes == 0:
+        raise RuntimeError(f"grouped_linear_wgrad: rows_per_group={rows_per_group} must be a multiple of 256, K={k} of 128, n_out={n_out} <= 72")
+    ws = torch.empty((nbytes // 8,), dtype=torch.float64, device=d_out.device)
+    # rows the table does not name stay 0 (a table over all rows, as the class-aware and the class-agnostic heads have, leaves none)
+    alloc = torch.empty if cls_rows.numel() == out_rows else torch.zeros
+    dw = alloc((out_rows, k), dtype=torch.float32, device=d_out.device) if want_w else None
+    db = alloc((out_rows,), dtype=torch.float32, device=d_out.device) if want_b else None
+    launch("gdrnpp_grouped_linear_wgrad_f32", f32_ptr(d_out, "d_out"), pitch, n_out, f32_ptr(feat2d, "feat"),
+           dev_ptr(group_sel, torch.int32, "group_sel"), int(n_slices), dev_ptr(cls_rows, torch.int64, "cls_rows"), int(out_rows),
+           dw.data_ptr() if want_w else None, db.data_ptr() if want_b else None, b, int(rows_per_group), k, ws.data_ptr(), nbytes,
+           timed=("mfma_f32:grouped_wgrad", 2.0 * m * 128 * k if want_w else 0.0, 4.0 * m * (72 + (k if want_w else 0)) + 2.0 * nbytes))
+    return dw, db
+
+
 def linear_f32_splitk(x2d, weight_packed, bias, epilogue: str = "none", gamma=None, resid=None):
     """Same contract as linear_f32_split for problems with few output tiles: split-K with a deterministic reduction that
     also applies bias and epilogue."""

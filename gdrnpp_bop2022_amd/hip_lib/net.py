@@ -170,6 +170,29 @@ def head_tail_nhwc(out_nhwc, coord2d, extents, double_mask: bool):
     return pnp_in, planes
 
 
+def head_tail_backward(out_nhwc, extents, double_mask: bool, g_pnp_in=None, g_planes=None, g_out=None):
+    """Adjoint of ``head_tail_nhwc`` (``gdrnpp_head_tail_backward_nhwc``) -> d_out f32[B*HW, pitch]: the gradient of the class-sliced
+    output layer's result from the gradients of pnp_in f32[B, HW, 96], of planes f32[P, B, HW] and the one that reached ``out_nhwc``
+    directly (the region map is a view of it).  Each may be None: it contributes nothing and is not read.  The columns from the
+    layer's width on are 0."""
+    bhw, pitch = out_nhwc.shape
+    b = extents.shape[0]
+    hw = bhw // b
+    n_planes = 5 if double_mask else 4
+    if b * hw != bhw or tuple(extents.shape) != (b, 3):
+        raise RuntimeError(f"head_tail_backward: out {tuple(out_nhwc.shape)} does not fit extents {tuple(extents.shape)}")
+    for name, g, shape in (("g_pnp_in", g_pnp_in, (b * hw * 96,)), ("g_planes", g_planes, (n_planes * b * hw,)), ("g_out", g_out, (bhw * pitch,))):
+        if g is not None and g.numel() != shape[0]:
+            raise RuntimeError(f"head_tail_backward: {name} has {g.numel()} elements, {shape[0]} expected")
+    d_out = torch.empty((bhw, pitch), dtype=torch.float32, device=out_nhwc.device)
+    n_in = sum(g is not None for g in (g_pnp_in, g_planes, g_out))
+    launch("gdrnpp_head_tail_backward_nhwc", f32_ptr(out_nhwc, "out_nhwc"), pitch, f32_ptr(extents, "extents"), opt_f32_ptr(g_pnp_in, "g_pnp_in"),
+           opt_f32_ptr(g_planes, "g_planes"), opt_f32_ptr(g_out, "g_out"), d_out.data_ptr(), b, hw, 1 if double_mask else 0,
+           timed=("hbm:head_tail_bwd", 0.0, 4.0 * bhw * (pitch + (72 + 96 if g_pnp_in is not None else 0) + (n_planes if g_planes is not None else 0)
+                                                        + (72 if g_out is not None else 0)) if n_in else 4.0 * bhw * pitch))
+    return d_out
+
+
 def pnp_fc_heads(x, w_r, b_r, w_t, b_t):
     """Patch-PnP's output layers in one launch (``gdrnpp_pnp_fc_heads``): x f32[b,K] -> (fc_r(x) f32[b,rot_dim], fc_t(x) f32[b,3])."""
     b, k = x.shape

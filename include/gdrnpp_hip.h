@@ -675,6 +675,41 @@ int gdrnpp_linear_f32_split_grouped(const float* A, const void* W_packed_stack, 
  *          Cin padded to a multiple of 32), planes f32[3 + (double_mask ? 2 : 1)][b*hw] = vis, (full,) x, y, z of out_dict. */
 int gdrnpp_head_tail_nhwc(const float* out_nhwc, int pitch, const float* coord2d, const float* extents, float* pnp_in,
                           float* planes, int b, int hw, int double_mask, void* stream);
+/* Backward of those two launches for training (csrc/head_tail_bwd.hip).  No atomics; every sum over rows goes through slots whose
+ * count depends on the shape alone and is finished in fp64 in index order: two calls give equal bits.
+ *
+ * Adjoint of gdrnpp_head_tail_nhwc: d_out f32[b*hw][pitch] from out_nhwc (the forward's input: the region softmax is rebuilt from it
+ * with the forward's own expression), extents f32[b][3] and any of
+ *   g_pnp_in f32[b*hw][96]   gradient of pnp_in (channels 3, 4 and 69..95 — coord2d and the padding — are ignored),
+ *   g_planes f32[3 + (double_mask ? 2 : 1)][b*hw]   gradient of planes,
+ *   g_out    f32[b*hw][pitch]   a gradient that reached out_nhwc directly (the region map is a view of it); added in.
+ * Each may be NULL: it contributes nothing and is not read (out_nhwc and extents are read only with g_pnp_in).  With kx = the first
+ * xyz channel and p = softmax(region[1..64]):  d_vis, d_full = their planes;  d_xyz[c] = g_planes[kx + c] + g_pnp_in[c] extent[c];
+ * d_region[0] = 0;  d_region[j] = p_j (g_pnp_in[4 + j] - sum_i p_i g_pnp_in[4 + i]) — sums and combination in fp64, one rounding.
+ * Columns n_out = kx + 68 .. pitch-1 of d_out are written 0; those columns of g_out are never read.  pitch >= 72, a multiple of 4;
+ * hw a multiple of 64. */
+int gdrnpp_head_tail_backward_nhwc(const float* out_nhwc, int pitch, const float* extents, const float* g_pnp_in, const float* g_planes,
+                                   const float* g_out, float* d_out, int b, int hw, int double_mask, void* stream);
+/* Data gradient of gdrnpp_linear_f32_split_grouped:  dfeat[m][0..K) = sum_{c < n_out} d_out[m][c] W[group_sel[m / rows_per_group]][c][:]
+ * with W f32[n_slices][n_out][K] — the sliced weight as it lies, no packed image — and d_out f32[M][pitch] read at its pitch; columns
+ * >= n_out are never used (they may hold anything).  Exact-f32 matrix instruction, one fp32 chain in column order.  A group whose
+ * selector lies outside [0, n_slices) gets NaN rows, as the forward poisons it; nothing is read out of bounds.
+ * rows_per_group a multiple of 256 dividing M, K a multiple of 128, n_out <= 72 <= pitch, pitch a multiple of 4. */
+int gdrnpp_grouped_linear_dinput_f32(const float* d_out, int pitch, int n_out, const float* W, const int* group_sel, int n_slices,
+                                     int rows_per_group, float* dfeat, int M, int K, void* stream);
+/* Weight and bias gradient of gdrnpp_linear_f32_split_grouped by slice, written into tensors shaped like the layer's own parameters:
+ * for every slice c and channel j < n_out
+ *   dW[cls_rows[c][j]][0..K) = sum over the groups r with group_sel[r] == c of  d_out[r]^T feat[r]  (row j),   db[cls_rows[c][j]] =
+ *   the column sums of those d_out[r] — groups in index order, each group's row slots in index order, in fp64, rounded once.
+ * d_out f32[B*hw][pitch] (columns >= n_out never used), feat f32[B*hw][K], cls_rows device i64[n_slices][n_out] with values in
+ * [0, out_rows) (others are skipped), dW f32[out_rows][K] or NULL, db f32[out_rows] or NULL: with both NULL nothing is launched.
+ * The rows of a slice no group selects are written 0; groups with a selector outside [0, n_slices) are left out; rows of dW / db
+ * outside cls_rows are not written.  The slot count depends on (B, hw, K) alone.  hw a multiple of 256, K of 128, n_out <= 72 <= pitch.
+ * workspace: gdrnpp_grouped_linear_wgrad_f32_workspace_bytes (0 = a shape outside the kernel), 16-byte aligned. */
+size_t gdrnpp_grouped_linear_wgrad_f32_workspace_bytes(int B, int hw, int K, int n_out);
+int gdrnpp_grouped_linear_wgrad_f32(const float* d_out, int pitch, int n_out, const float* feat, const int* group_sel, int n_slices,
+                                    const long long* cls_rows, int out_rows, float* dW, float* db, int B, int hw, int K, void* workspace,
+                                    size_t workspace_bytes, void* stream);
 
 /* 3x3 / stride 1 / zero-pad 1 convolution of the geometry head (a3) as an implicit GEMM on the same kernel:
  * x f32 NHWC [n_img,H,W,Cin] -> y f32 NHWC [n_img,H,W,Cout]; W_packed = gdrnpp_pack_weight_bf16x3 of the weight
