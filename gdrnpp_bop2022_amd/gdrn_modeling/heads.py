@@ -310,8 +310,12 @@ class ConvPnPNet(nn.Module):
     def forward_prepared(self, x96_cl, pose=None):
         """``x96_cl``: [B, 96, H, W] channels_last, channels 69..95 zero.  First convolution with its weight zero-padded to 96
         input channels on the implicit-GEMM split kernel, the rest as ``forward``.  Under autograd (the prepared input then comes
-        from ``hip_layers.HeadTail``) that kernel has no gradient: the first convolution is PyTorch's on the 69 channels."""
+        from ``hip_layers.HeadTail``) with ``set_train_kernels(True)`` and the shipped configuration the whole net runs on
+        ``hip_layers.pnp_train`` — this library's kernels forward and backward, no foreign launch; otherwise that kernel has no
+        gradient and the first convolution is PyTorch's on the 69 channels."""
         c0 = self.features[0]
+        if hip_layers._pnp_train_ok(self, x96_cl):
+            return hip_layers.pnp_train(self, x96_cl)
         if torch.is_grad_enabled():
             hip_layers.note_foreign_launch("ConvPnPNet.forward_prepared: first convolution as F.conv2d under autograd (conv2d_f32_split has no gradient)")
             x = F.conv2d(x96_cl[:, :69], c0.weight, None, c0.stride, c0.padding)

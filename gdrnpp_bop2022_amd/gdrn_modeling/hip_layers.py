@@ -139,8 +139,11 @@ def _dwconv_hip_ok(conv: nn.Conv2d, x: torch.Tensor) -> bool:
 # (ConvNeXtMlp) — with both, a ConvNeXt block trains without a kernel that is not this library's — and the geometry head's layers:
 # conv3x3_groupnorm_act (Conv3x3GnAct), conv_transpose2d_groupnorm_act (ConvTranspose2dGn), groupnorm_act (GroupNormAct) and
 # upsample2x (Upsample2x), and the head's tail — the class-sliced 1x1 output layer, the class gather, the region softmax, the xyz
-# de-normalisation and the concatenation into Patch-PnP's input (HeadTail).  Patch-PnP's own layers, the stem and downsample layers,
-# the ResNet path and AMP keep PyTorch's graph.
+# de-normalisation and the concatenation into Patch-PnP's input (HeadTail) — and Patch-PnP in its shipped ConvNeXt configuration on
+# the prepared input: the three [conv3x3 / stride 2, GroupNorm, GELU] layers (Conv3x3S2GnAct), the NCHW flatten (FlattenNCHW), fc1 and
+# fc2 with their GELU (LinearGelu) and the two pose heads (PnPHeads).  The stem and downsample layers, the ResNet path, AMP and
+# Patch-PnP outside that configuration (act "relu", another norm, mask attention, odd sizes, the module path ``forward``) keep
+# PyTorch's graph.
 _TRAIN_KERNELS = False
 
 
@@ -366,6 +369,144 @@ def head_tail(out_layer: nn.Conv2d, cls_rows: torch.Tensor, feat: torch.Tensor, 
     x2d = _cl(feat).permute(0, 2, 3, 1).reshape(bs * h * wd, ch)      # a view of the NHWC memory
     return HeadTail.apply(x2d, out_layer.weight, out_layer.bias, cls_rows, sel.to(torch.int32).contiguous(), coord2d.contiguous().float(),
                           extents.contiguous().float(), bool(double_mask))
+
+
+class Conv3x3S2GnAct(torch.autograd.Function):
+    """Patch-PnP's [Conv2d 3x3/2/1 without bias, GroupNorm, GELU] with its backward on HIP kernels (csrc/pnp_bwd.hip).  x (N,ld,H,W)
+    channels_last whose first ``cin`` channels are the layer's input (the 96-pitch prepared input for the first layer, ld = cin
+    behind it) -> y (N,Cout,H/2,W/2) channels_last.  The forward is the fp32-MFMA convolution (``gdrnpp_conv_bias_act_f32``, stride 2),
+    the GroupNorm statistics and the apply pass: not the bits of the inference forward's six-product convolution, as in
+    ``Conv3x3GnAct``.  Saved: x, the convolution's output z and the statistics' partial sums.  dx has x's channels and pitch, zero from ``cin`` on."""
+
+    @staticmethod
+    def forward(ctx, x, cin, weight, gn_weight, gn_bias, groups, eps, gelu):
+        z = hip_lib.conv3x3s2_f32_mfma(x, hip_lib.conv3x3s2_weight_kn(weight))      # operand made per forward: the weight changes every step
+        y, part = hip_lib.groupnorm_act_train(z, gn_weight, gn_bias, groups, eps, gelu)
+        ctx.save_for_backward(x, z, part, weight, gn_weight, gn_bias)
+        ctx.cin, ctx.gn = cin, (groups, eps, gelu)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_y):
+        x, z, part, weight, gn_weight, gn_bias = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        conv = (need[0], need[2])
+        dx = dw = dg = dbeta = None
+        if any(conv) or need[3] or need[4]:
+            dz, dg, dbeta = hip_lib.groupnorm_act_backward(z, part, gn_weight, gn_bias, *ctx.gn, _cl(grad_y), want=(any(conv), need[3], need[4]))
+            if any(conv):
+                dx, dw = hip_lib.conv3x3s2_backward(x, ctx.cin, weight, dz, want=conv)
+        return dx, None, dw, dg, dbeta, None, None, None
+
+
+class FlattenNCHW(torch.autograd.Function):
+    """``x.flatten(1)`` of a channels_last tensor in NCHW order (the order Patch-PnP's fc1 was trained in) on
+    ``gdrnpp_nhwc_flatten_nchw``, and its inverse for the gradient; nothing is saved."""
+
+    @staticmethod
+    def forward(ctx, x):
+        ctx.chw = tuple(x.shape[1:])
+        return hip_lib.nhwc_flatten_nchw(x)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_y):
+        return hip_lib.nhwc_unflatten_nchw(grad_y.contiguous(), *ctx.chw)
+
+
+class LinearGelu(torch.autograd.Function):
+    """gelu(x W^T + b) on [M,K] rows with few rows and a long K (Patch-PnP's fc1 and fc2): ``linear_f32_exact`` + ``gelu_f32`` forward;
+    backward ``mlp_bwd_act_`` (dpre and the bias gradient), ``gemm_tn_f32`` (dW, its slot tiles in the persistent workspace) and
+    ``linear_f32_exact`` on the weight as it lies (dx).  Saved: x, the pre-activation and the weight."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias):
+        pre = hip_lib.linear_f32_exact(x, weight, bias)
+        ctx.save_for_backward(x, pre, weight)
+        return hip_lib.gelu_f32(pre)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_y):
+        x, pre, weight = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        dx = dw = db = None
+        if any(need[:3]):
+            dpre = torch.empty_like(pre)      # autograd's grad_y may be somebody else's too: the activation pass works in place on a copy
+            hip_lib.copy_d2d(dpre.data_ptr(), grad_y.contiguous())
+            _, db = hip_lib.mlp_bwd_act_(pre, dpre, want_h=False, want_db1=need[2])
+            if need[0]:
+                dx = hip_lib.linear_f32_exact(dpre, weight, weight_kn=True)
+            if need[1]:
+                dw = hip_lib.gemm_tn_f32(dpre, x, persistent_ws=True)
+        return dx, dw, db
+
+
+class PnPHeads(torch.autograd.Function):
+    """(fc_r(x), fc_t(x)) of Patch-PnP: ``gdrnpp_pnp_fc_heads`` forward, ``gdrnpp_pnp_fc_heads_backward`` backward.  A head the loss
+    does not use arrives as None and contributes nothing.  Saved: x and the two weights."""
+
+    @staticmethod
+    def forward(ctx, x, w_r, b_r, w_t, b_t):
+        ctx.save_for_backward(x, w_r, w_t)
+        ctx.set_materialize_grads(False)
+        return hip_lib.pnp_fc_heads(x, w_r.detach(), b_r.detach(), w_t.detach(), b_t.detach())
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_r, g_t):
+        x, w_r, w_t = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        if not any(need[:5]) or (g_r is None and g_t is None):
+            return (None,) * 5
+        g_r, g_t = (None if g is None else g.contiguous() for g in (g_r, g_t))
+        return hip_lib.pnp_fc_heads_backward(g_r, g_t, x, w_r, w_t, want=need[:5])
+
+
+def _param_ok(*tensors) -> bool:
+    return all(t is not None and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() for t in tensors)
+
+
+def _pnp_train_ok(net: nn.Module, x96_cl: torch.Tensor) -> bool:
+    """Shapes and state ``pnp_train`` takes: ``_train_ok`` plus the shipped ConvNeXt configuration of ConvPnPNet — the prepared 96-pitch
+    channels_last input, three [Conv2d 3x3/2/1 without bias, GroupNorm, exact GELU] to featdim % 128 == 0 channels, H and W
+    multiples of 8 that end at fc1's width, exact GELU behind fc1 and fc2, no mask attention, heads of at most 9 and of 3 rows."""
+    f = getattr(net, "features", ())
+    if not (_train_ok(x96_cl) and _MLP_GEMM == "split" and x96_cl.shape[1] == 96 and x96_cl.is_contiguous(memory_format=torch.channels_last)
+            and len(f) == 9 and net.mask_attention_type == "none" and net.accepts_prepared_input() and _exact_gelu_or_none(net.act)
+            and net.act is not None and x96_cl.shape[2] % 8 == 0 and x96_cl.shape[3] % 8 == 0):
+        return False
+    n, _, h, w = x96_cl.shape
+    cin = 69
+    for i in range(0, 9, 3):
+        conv, gn, act = f[i], f[i + 1], f[i + 2]
+        if not (isinstance(conv, nn.Conv2d) and isinstance(gn, nn.GroupNorm) and isinstance(act, nn.GELU) and _exact_gelu_or_none(act)
+                and conv.kernel_size == (3, 3) and conv.stride == (2, 2) and conv.padding == (1, 1) and conv.dilation == (1, 1)
+                and conv.groups == 1 and conv.padding_mode == "zeros" and conv.bias is None and conv.in_channels == cin
+                and conv.out_channels % 128 == 0 and gn.num_channels == conv.out_channels and _gn_train_shape_ok(gn, n)
+                and conv.weight.is_cuda and conv.weight.dtype == torch.float32      # any memory format: the operands are formed per call
+                and _param_ok(gn.weight, gn.bias) and n * h * w < (1 << 31) - 4096):
+            return False
+        cin, h, w = conv.out_channels, h // 2, w // 2
+    fc1, fc2, fc_r, fc_t = net.fc1, net.fc2, net.fc_r, net.fc_t
+    return (fc1.in_features == cin * h * w and fc1.out_features % 128 == 0 and fc2.in_features == fc1.out_features
+            and fc2.out_features % 128 == 0 and fc_r.in_features == fc_t.in_features == fc2.out_features <= 1024
+            and fc_r.out_features <= 9 and fc_t.out_features == 3
+            and _param_ok(fc1.weight, fc1.bias, fc2.weight, fc2.bias, fc_r.weight, fc_r.bias, fc_t.weight, fc_t.bias))
+
+
+def pnp_train(net: nn.Module, x96_cl: torch.Tensor):
+    """ConvPnPNet on the prepared input under autograd, every layer on this library's kernels forward and backward; after
+    ``_pnp_train_ok``.  -> (rot, t) as ``forward_prepared`` returns them."""
+    x, cin = x96_cl, 69
+    for i in range(0, 9, 3):
+        conv, gn = net.features[i], net.features[i + 1]
+        x = Conv3x3S2GnAct.apply(x, cin, conv.weight, gn.weight, gn.bias, gn.num_groups, gn.eps, True)
+        cin = conv.out_channels
+    x = LinearGelu.apply(FlattenNCHW.apply(x), net.fc1.weight, net.fc1.bias)
+    x = LinearGelu.apply(x, net.fc2.weight, net.fc2.bias)
+    return PnPHeads.apply(x, net.fc_r.weight, net.fc_r.bias, net.fc_t.weight, net.fc_t.bias)
 
 
 def _dwconv_train_ok(conv: nn.Conv2d, ln: nn.LayerNorm, x: torch.Tensor) -> bool:

@@ -28,6 +28,8 @@ from .gemm import (colsum_f32, convnext_mlp_backward, convnext_mlp_forward_train
 from .gemm import (conv3x3_backward, conv3x3_f32_mfma, conv3x3_weight_kn, conv3x3_weight_kn_flipped, conv3x3_wgrad_f32,  # noqa: F401
                    conv_transpose2d_backward, conv_transpose2d_train, deconv_im2col, deconv_weight_kn, groupnorm_apply)
 from .gemm import grouped_linear_dinput, grouped_linear_wgrad  # noqa: F401
+from .gemm import (conv3x3s2_backward, conv3x3s2_dinput_f32, conv3x3s2_dinput_weight, conv3x3s2_f32_mfma, conv3x3s2_weight_kn,  # noqa: F401
+                   conv3x3s2_wgrad_f32, nhwc_flatten_nchw, nhwc_unflatten_nchw, pnp_fc_heads_backward, workspace)
 from .net import (DENSE_MASK_TYPES, DENSE_SUMS, DENSE_XYZ_TYPES, LOSS_MASKS, PM_TYPES, POINT_PNP_TILE, ROT_DIMS, ROT_MODES, T_MODES,  # noqa: F401
                   bias_act_nhwc_, dwconv7x7_ln, dwconv7x7_ln_backward, gdrn_dense_losses, gdrn_dense_losses_backward, gdrn_pose_losses, groupnorm_act,
                   groupnorm_act_backward, groupnorm_act_train, head_tail_backward, head_tail_nhwc,

@@ -6,7 +6,7 @@ from __future__ import annotations
 import torch
 
 from . import dispatch
-from .abi import DEFINES, channels_last_f32, dev_ptr, f32_ptr, launch, load, opt_f32_ptr
+from .abi import DEFINES, channels_last_f32, current_stream, dev_ptr, f32_ptr, launch, load, opt_f32_ptr
 from .range_words import count_x3, x3_flag_ptr
 
 X3 = "_x3"   # LaunchTimer kind suffix of the three-product (fp16x2) kernels: 3 instead of 6 MFMA flops per fp32-equivalent flop
@@ -446,12 +446,13 @@ def mlp_bwd_act_(pre, dh, want_h: bool = True, want_db1: bool = True):
     return h, db1
 
 
-def gemm_tn_f32(a, b, row_scale=None, w=None, bias=None, sg=None, want_g: bool = True):
+def gemm_tn_f32(a, b, row_scale=None, w=None, bias=None, sg=None, want_g: bool = True, persistent_ws: bool = False):
     """G[N1,N2] = a^T b for a f32[M,N1], b f32[M,N2] (N1, N2 multiples of 128, any M >= 1) on the exact-f32 matrix instruction
     (``gdrnpp_gemm_tn_f32``): the weight-gradient product.  Deterministic: fixed slots, fp64 finalize, one rounding.
     ``row_scale`` f32[N1]: G[c,:] = fl(row_scale[c] * sum).  With ``w`` f32[N1,N2], ``bias`` f32[N1] and ``sg`` f64[N1] the result is
     (G, drow) with drow[c] = fl(sum_k w[c,k] sum[c,k] + bias[c] sg[c]), the layer-scale gradient, taken before G is rounded;
-    ``want_g`` False leaves G out (None)."""
+    ``want_g`` False leaves G out (None).  ``persistent_ws``: the slot tiles live in ``workspace`` (kept per device and stream) instead
+    of a tensor of this call."""
     m, n1 = a.shape
     if b.dim() != 2 or b.shape[0] != m:
         raise RuntimeError(f"gemm_tn_f32: b must have the {m} rows of a, got {tuple(b.shape)}")
@@ -464,7 +465,7 @@ def gemm_tn_f32(a, b, row_scale=None, w=None, bias=None, sg=None, want_g: bool =
     nbytes = load().gdrnpp_gemm_tn_f32_workspace_bytes(m, n1, n2)
     if nbytes == 0:
         raise RuntimeError(f"gemm_tn_f32: N1={n1} N2={n2} must be multiples of 128 (M={m} >= 1)")
-    ws = torch.empty((nbytes // 8,), dtype=torch.float64, device=a.device)
+    ws = workspace(a.device, nbytes) if persistent_ws else torch.empty((nbytes // 8,), dtype=torch.float64, device=a.device)
     g = torch.empty((n1, n2), dtype=torch.float32, device=a.device) if want_g else None
     drow = torch.empty((n1,), dtype=torch.float32, device=a.device) if layer_scale else None
     launch("gdrnpp_gemm_tn_f32", f32_ptr(a, "a"), f32_ptr(b, "b"), g.data_ptr() if want_g else None, m, n1, n2, opt_f32_ptr(row_scale, "row_scale"),
@@ -691,3 +692,152 @@ def groupnorm_apply(z_cl, part, gamma, beta, groups: int, eps: float = 1e-5, gel
     """y = GroupNorm(groups)(z) [-> GELU] from the partial sums f64[N,P,groups,2] a GEMM's epilogue or gather left (``gdrnpp_groupnorm_apply_nhwc``)."""
     n, c, h, w = channels_last_f32(z_cl, "groupnorm_apply")
     return _groupnorm_apply(z_cl, part, int(part.shape[1]), gamma, beta, n, h * w, c, groups, eps, gelu)
+
+
+# ---- training: Patch-PnP under autograd (csrc/pnp_bwd.hip) ------------------------------------------------------------------------
+# The forward convolutions run on gdrnpp_conv_bias_act_f32 (ks 3, stride 2) like the head's; the first layer reads the 96-pitch
+# prepared input with Cin rounded up to 72 and zero weight rows for the channels 69..71.
+_WORKSPACES = {}
+
+
+def workspace(device, nbytes: int):
+    """A float64 device buffer of at least ``nbytes`` bytes kept per (device, stream) and grown on demand: the slot tiles of a large
+    weight-gradient product (64 MB for Patch-PnP's fc1) are taken once, not once per step.  Its contents mean nothing between calls."""
+    key = (torch.device(device).index, current_stream())
+    buf = _WORKSPACES.get(key)
+    if buf is None or buf.numel() * 8 < nbytes:
+        buf = torch.empty(((max(nbytes, 16) + 7) // 8,), dtype=torch.float64, device=device)
+        _WORKSPACES[key] = buf
+    return buf
+
+
+def _s2_input(x_cl, cin: int, what: str):
+    n, ld, h, w = channels_last_f32(x_cl, what)
+    if not 0 < cin <= ld:
+        raise RuntimeError(f"{what}: cin={cin} outside the {ld} channels of x")
+    return n, ld, h, w
+
+
+def conv3x3s2_weight_kn(weight, cin_pad: int | None = None):
+    """nn.Conv2d weight [Cout,Cin,3,3] -> the forward operand of ``conv3x3s2_f32_mfma``: f32[9 cin_pad, Cout], row (ky 3 + kx) cin_pad
+    + ci, zero rows for ci >= Cin (``cin_pad``: Cin rounded up to a multiple of 4 unless given)."""
+    cout, cin = weight.shape[:2]
+    cin_pad = (cin + 3) // 4 * 4 if cin_pad is None else cin_pad
+    w = weight.detach().permute(2, 3, 1, 0)
+    if cin_pad == cin:
+        return w.reshape(9 * cin, cout).contiguous()
+    out = torch.zeros((3, 3, cin_pad, cout), dtype=weight.dtype, device=weight.device)
+    out[:, :, :cin] = w
+    return out.view(9 * cin_pad, cout)
+
+
+def conv3x3s2_f32_mfma(x_cl, weight_kn):
+    """3x3 / stride 2 / zero pad 1 convolution of the first ``weight_kn.shape[0] / 9`` channels of a channels_last tensor [N,ld,H,W]
+    with ``weight_kn`` (``conv3x3s2_weight_kn``) on ``gdrnpp_conv_bias_act_f32`` -> channels_last [N,Cout,H/2,W/2]."""
+    cin = weight_kn.shape[0] // 9
+    n, ld, h, w = _s2_input(x_cl, cin, "conv3x3s2_f32_mfma")
+    cout = weight_kn.shape[1]
+    if weight_kn.dim() != 2 or weight_kn.shape[0] != 9 * cin or cin % 4 or cout % 4 or ld % 4 or h % 2 or w % 2:
+        raise RuntimeError(f"conv3x3s2_f32_mfma: weight_kn {tuple(weight_kn.shape)} for x {tuple(x_cl.shape)}: channel counts multiples of 4, H and W even")
+    out = torch.empty((n, cout, h // 2, w // 2), dtype=torch.float32, device=x_cl.device, memory_format=torch.channels_last)
+    launch("gdrnpp_conv_bias_act_f32", x_cl.data_ptr(), ld, 0, f32_ptr(weight_kn, "weight_kn"), cout, None, None, 0, 0, out.data_ptr(), cout, 0, 0, 0,
+           n, h, w, cin, cout, 3, 2, _ACT_NONE, 0.0,
+           timed=("mfma_f32:conv3x3s2", 2.0 * n * (h // 2) * (w // 2) * cout * 9 * cin, 4.0 * n * (h * w * cin + (h // 2) * (w // 2) * cout) + 36.0 * cin * cout))
+    return out
+
+
+def conv3x3s2_wgrad_f32(dz_cl, x_cl, cin: int):
+    """dW f32[Cout,cin,3,3] of a 3x3 / stride 2 / zero pad 1 convolution for dz [N,Cout,H/2,W/2] and the first ``cin`` channels of its
+    input x [N,ld,H,W], both channels_last (``gdrnpp_conv3x3s2_wgrad_f32``).  What x holds in the channels from ``cin`` on does not matter."""
+    what = "conv3x3s2_wgrad_f32"
+    n, ld, h, w = _s2_input(x_cl, cin, what)
+    dn, cout, oh, ow = channels_last_f32(dz_cl, what)
+    if (dn, 2 * oh, 2 * ow) != (n, h, w):
+        raise RuntimeError(f"{what}: dz {tuple(dz_cl.shape)} does not fit x {tuple(x_cl.shape)}")
+    nbytes = load().gdrnpp_conv3x3s2_wgrad_f32_workspace_bytes(n, h, w, cin, ld, cout)      # 0: the entry point refuses the shape, in its words
+    ws = torch.empty((max(nbytes, 16) // 8,), dtype=torch.float64, device=x_cl.device)
+    dw = torch.empty((cout, cin, 3, 3), dtype=torch.float32, device=x_cl.device)
+    launch("gdrnpp_conv3x3s2_wgrad_f32", dz_cl.data_ptr(), x_cl.data_ptr(), ld, dw.data_ptr(), n, h, w, cin, cout, ws.data_ptr(), nbytes,
+           timed=("mfma_f32:conv3x3s2_wgrad", 2.0 * n * oh * ow * cout * 9 * cin, 4.0 * n * (h * w * cin + oh * ow * cout) + 36.0 * cin * cout))
+    return dw
+
+
+def conv3x3s2_dinput_weight(weight):
+    """nn.Conv2d weight [Cout,Cin,3,3] -> the operand of ``conv3x3s2_dinput_f32``: f32[9 Cout, ldw], row (ky 3 + kx) Cout + co, column
+    ci, ldw = Cin rounded up to a multiple of 4 (the columns from Cin on are not read as values)."""
+    cout, cin = weight.shape[:2]
+    w = weight.detach().permute(2, 3, 0, 1)
+    if cin % 4 == 0:
+        return w.reshape(9 * cout, cin).contiguous()
+    out = torch.zeros((3, 3, cout, (cin + 3) // 4 * 4), dtype=weight.dtype, device=weight.device)
+    out[..., :cin] = w
+    return out.view(9 * cout, -1)
+
+
+def conv3x3s2_dinput_f32(dz_cl, w_op, cin: int, ld: int | None = None):
+    """dx [N,ld,H,W] channels_last of a 3x3 / stride 2 / zero pad 1 convolution for dz [N,Cout,H/2,W/2] channels_last and ``w_op``
+    (``conv3x3s2_dinput_weight``): channels [0, cin) the gradient, [cin, ld) zero (``gdrnpp_conv3x3s2_dinput_f32``, by parity class)."""
+    what = "conv3x3s2_dinput_f32"
+    n, cout, oh, ow = channels_last_f32(dz_cl, what)
+    ld = cin if ld is None else ld
+    if w_op.dim() != 2 or w_op.shape[0] != 9 * cout or w_op.shape[1] < cin:
+        raise RuntimeError(f"{what}: w_op must be f32[{9 * cout}, >= {cin}], got {tuple(w_op.shape)}")
+    dx = torch.empty((n, ld, 2 * oh, 2 * ow), dtype=torch.float32, device=dz_cl.device, memory_format=torch.channels_last)
+    launch("gdrnpp_conv3x3s2_dinput_f32", dz_cl.data_ptr(), f32_ptr(w_op, "w_op"), w_op.shape[1], dx.data_ptr(), ld, n, 2 * oh, 2 * ow, cin, cout,
+           timed=("mfma_f32:conv3x3s2_dinput", 2.0 * n * oh * ow * cout * 9 * cin, 4.0 * n * oh * ow * (4 * ld + 4 * cout) + 36.0 * cin * cout))
+    return dx
+
+
+def conv3x3s2_backward(x_cl, cin: int, weight, dz_cl, want=(True, True)):
+    """Gradients of z = conv3x3 / stride 2 (x[:, :cin], weight) for dz = dL/dz -> (dx, dweight).  ``want``: two flags in that order — an
+    entry is None where its flag is false and its launches are left out; the other keeps its bits.  dx has the channels and the pitch
+    of x (zero from ``cin`` on); the data-gradient operand is formed here, per call (the weight changes every step)."""
+    want = tuple(bool(f) for f in want)
+    if len(want) != 2 or not any(want):
+        raise RuntimeError("conv3x3s2_backward: want must hold two flags, at least one of them set")
+    if weight.shape[1] != cin:
+        raise RuntimeError(f"conv3x3s2_backward: weight {tuple(weight.shape)} for cin={cin}")
+    dx = conv3x3s2_dinput_f32(dz_cl, conv3x3s2_dinput_weight(weight), cin, x_cl.shape[1]) if want[0] else None
+    dw = conv3x3s2_wgrad_f32(dz_cl, x_cl, cin) if want[1] else None
+    return dx, dw
+
+
+def nhwc_flatten_nchw(x_cl):
+    """``x.flatten(1)`` of a channels_last tensor [B,C,H,W] -> f32[B, C H W] in NCHW order (``gdrnpp_nhwc_flatten_nchw``)."""
+    b, c, h, w = channels_last_f32(x_cl, "nhwc_flatten_nchw")
+    out = torch.empty((b, c * h * w), dtype=torch.float32, device=x_cl.device)
+    launch("gdrnpp_nhwc_flatten_nchw", x_cl.data_ptr(), out.data_ptr(), b, h * w, c, 0, timed=("hbm:flatten_nchw", 0.0, 8.0 * out.numel()))
+    return out
+
+
+def nhwc_unflatten_nchw(x2d, c: int, h: int, w: int):
+    """The inverse of ``nhwc_flatten_nchw``: f32[B, c h w] in NCHW order -> channels_last [B,c,h,w]."""
+    b = x2d.shape[0]
+    if x2d.dim() != 2 or x2d.shape[1] != c * h * w:
+        raise RuntimeError(f"nhwc_unflatten_nchw: x must be f32[B,{c * h * w}], got {tuple(x2d.shape)}")
+    out = torch.empty((b, c, h, w), dtype=torch.float32, device=x2d.device, memory_format=torch.channels_last)
+    launch("gdrnpp_nhwc_flatten_nchw", f32_ptr(x2d, "x"), out.data_ptr(), b, h * w, c, 1, timed=("hbm:flatten_nchw", 0.0, 8.0 * out.numel()))
+    return out
+
+
+def pnp_fc_heads_backward(g_r, g_t, feat, w_r, w_t, want=(True,) * 5):
+    """Gradients of ``pnp_fc_heads`` (``gdrnpp_pnp_fc_heads_backward``) for g_r f32[B,rot_dim] and g_t f32[B,3], either of which may be
+    None (no gradient from that head) -> (dfeat, dw_r, db_r, dw_t, db_t).  ``want``: five flags in that order — an entry is None where
+    its flag is false, and a launch nothing asks for is left out."""
+    want = tuple(bool(f) for f in want)
+    if len(want) != 5:
+        raise RuntimeError("pnp_fc_heads_backward: want must hold five flags")
+    b, k = feat.shape
+    rd = w_r.shape[0]
+    for name, g, n in (("g_r", g_r, rd), ("g_t", g_t, 3)):
+        if g is not None and tuple(g.shape) != (b, n):
+            raise RuntimeError(f"pnp_fc_heads_backward: {name} must be f32[{b},{n}], got {tuple(g.shape)}")
+    dev = feat.device
+    shapes = ((b, k), (rd, k), (rd,), (3, k), (3,))
+    dfeat, dw_r, db_r, dw_t, db_t = (torch.empty(s, dtype=torch.float32, device=dev) if f else None for s, f in zip(shapes, want))
+    if any(want):
+        ptr = lambda t: None if t is None else t.data_ptr()      # noqa: E731
+        launch("gdrnpp_pnp_fc_heads_backward", opt_f32_ptr(g_r, "g_r"), opt_f32_ptr(g_t, "g_t"), f32_ptr(feat, "feat"), f32_ptr(w_r, "w_r"),
+               f32_ptr(w_t, "w_t"), ptr(dfeat), ptr(dw_r), ptr(dw_t), ptr(db_r), ptr(db_t), b, k, rd,
+               timed=("pnp_heads_bwd", 2.0 * b * k * (rd + 3) * (want[0] + (want[1] or want[3])), 4.0 * (2 * b * k + 2 * (rd + 3) * k)))
+    return dfeat, dw_r, db_r, dw_t, db_t

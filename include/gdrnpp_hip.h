@@ -814,6 +814,38 @@ int gdrnpp_upsample_bilinear2x_backward_nhwc(const float* grad_y, float* dx, int
 int gdrnpp_deconv_im2col_nhwc(const float* dy, float* dcols, int N, int H, int W, int C, int KS, int stride, int pad, int out_pad,
                               void* stream);
 
+/* ---- training Patch-PnP (ConvPnPNet): backward of the 3x3 / stride 2 / pad 1 convolutions, the NCHW flatten and the two pose heads
+ * (csrc/pnp_bwd.hip).  The rules of the section above hold: NHWC fp32, no atomics, fixed summation orders (two calls give equal
+ * bits), a NULL output is not computed and its launches are left out, argument errors return GDRNPP_EINVAL / GDRNPP_ELIMIT with
+ * gdrnpp_last_error text and launch nothing, a workspace query returns 0 for a shape outside its kernel.  The forward convolution is
+ * gdrnpp_conv_bias_act_f32 with ks = 3, stride = 2.
+ *  conv3x3s2_wgrad_f32 : dW[co][ci][ky][kx] = sum_{n,oy,ox} dz[n,oy,ox,co] x[n,2oy+ky-1,2ox+kx-1,ci] (zero outside the image), dW
+ *                 f32[Cout,Cin,3,3] contiguous, dz f32[N,H/2,W/2,Cout], x = channels [0, Cin) of f32[N,H,W,ldx].  H and W even,
+ *                 Cout % 128 == 0; Cin % 128 == 0 with ldx == Cin, or any Cin <= ldx with ldx % 32 == 0 (the channels are padded
+ *                 with zeros to a multiple of 128 inside the kernel, whatever x holds beyond Cin, and only the Cin real ones are
+ *                 stored).  The sums of gdrnpp_conv3x3_wgrad_f32 with the N H/2 W/2 output pixels as rows; workspace slots x 9 x
+ *                 Cin' x Cout doubles, Cin' = Cin rounded up to 128.
+ *  conv3x3s2_dinput_f32 : dx[n,y,x,ci] = sum dz[n,oy,ox,co] W[co,ci,ky,kx] over 2oy+ky-1 = y, 2ox+kx-1 = x, by the parity class of
+ *                 (y, x): 1, 2, 2 or 4 taps, none for oy = H/2 or ox = W/2.  w f32[9 Cout, ldw], row (ky 3 + kx) Cout + co, column
+ *                 ci (ldw % 4 == 0, >= Cin; columns from Cin on are ignored).  dx: channels [0, Cin) of rows of lddx channels, the
+ *                 channels [Cin, lddx) written 0; Cin / lddx as Cin / ldx above.  Exact-f32 matrix instruction, the depth in (ky,
+ *                 kx, co) order in fp32 chains of 128 carried in fp64, one rounding; the order does not depend on N.
+ *  nhwc_flatten_nchw : dst f32[B, C HW] = src f32[B, HW, C] transposed per image (x.flatten(1) of an NCHW tensor held NHWC);
+ *                 inverse != 0: dst f32[B, HW, C] from src f32[B, C HW].  Values are copied.
+ *  pnp_fc_heads_backward : for rot = feat w_r^T + b_r, t = feat w_t^T + b_t (gdrnpp_pnp_fc_heads) and g_r f32[B,rot_dim], g_t
+ *                 f32[B,3] (either may be NULL: no gradient from that head): dfeat f32[B,K] = g_r w_r + g_t w_t, dW_r
+ *                 f32[rot_dim,K] = g_r^T feat, dW_t f32[3,K], db_r, db_t the column sums of g; sums over B in index order in fp64,
+ *                 one rounding.  Every output may be NULL; the outputs of a head whose source is NULL are written 0.  K <= 1024,
+ *                 rot_dim <= 9. */
+size_t gdrnpp_conv3x3s2_wgrad_f32_workspace_bytes(int N, int H, int W, int Cin, int ldx, int Cout);
+int gdrnpp_conv3x3s2_wgrad_f32(const float* dz, const float* x, int ldx, float* dW, int N, int H, int W, int Cin, int Cout,
+                               void* workspace, size_t workspace_bytes, void* stream);
+int gdrnpp_conv3x3s2_dinput_f32(const float* dz, const float* w, int ldw, float* dx, int lddx, int N, int H, int W, int Cin, int Cout,
+                                void* stream);
+int gdrnpp_nhwc_flatten_nchw(const float* src, float* dst, int B, int HW, int C, int inverse, void* stream);
+int gdrnpp_pnp_fc_heads_backward(const float* g_r, const float* g_t, const float* feat, const float* w_r, const float* w_t, float* dfeat,
+                                 float* dW_r, float* dW_t, float* db_r, float* db_t, int B, int K, int rot_dim, void* stream);
+
 /* ---- three-product form of the split GEMM ("fp16x2"): what hip_layers uses by default for large launches (a3) ----------------
  * Every fp32 operand is written as h + l with h = rn_f16(x), l = rn_f16(x - h): 22 significant bits; the products h*l, l*h, h*h
  * go through v_mfma_f32_32x32x16_f16 with fp32 accumulation — half the matrix work of the six-product form above.  The operand
