@@ -14,6 +14,9 @@ integers in the output.
                 an fp16 number, h would absorb the fraction.)  Rows have rms >= 2: no range word;
   fine_lattice  +-(1 + c 2^-9 + d 2^-17): fills the m and l planes of the SIX-product (bf16 x 3) split of one operand.
 
+The fused ConvNeXt MLP (csrc/gemm_mlp_fused.hip; tests/test_gpu_mlp_fused_exact.py) is two such GEMMs around a GELU: its section at
+the end of this file says on which inputs the GELU is exact as well, and builds them.
+
 Every ``*_expected`` function asserts its exactness precondition on the actual operands before it returns (AssertionError: the
 inputs are no lattice for this K), so a test built on it cannot pass or fail by rounding."""
 import functools
@@ -357,3 +360,189 @@ def fine_case(k, side):
     f, t = fine_lattice(fine, gen), int_lattice(tern, 1, 0.3, gen)
     A, W = (f, t) if side == "A" else (t, f)
     return dict(A=A, W=W, want=fine_product_expected(A, W))
+
+
+# ---- the fused ConvNeXt MLP (csrc/gemm_mlp_fused.hip; tests/test_gpu_mlp_fused_exact.py) ------------------------------------------
+# gelu_erf (csrc/common.hpp) is max(x, 0) - u 2^q(u) with u = min(|x|, 5.9): for |x| >= 5.9 the subtracted term is 9.6e-9.  It
+# vanishes in the rounding of any x >= 6 (half an ulp there is 2.4e-7), and for x <= -6 the result -9.6e-9 is below half the
+# smallest fp16 subnormal (2.98e-8): both halves of fc2's operand are +-0.  On inputs with NO pre-activation in (-6, 6) the fused
+# MLP is therefore resid + gamma * (W2 . max(W1 x + b1, 0) + b2) under the three-product scheme, twice — one bit pattern.
+GELU_EXACT_FROM = 6.0
+GELU_DEAD_BELOW = 2.0 ** -25        # half the smallest fp16 subnormal: rn_f16 of anything smaller is +-0
+MLPF_M = (1, 31, 32, 33, 127, 128, 129, 255, 257, 513)      # one wave (32 pixels), one workgroup (128), a second one, a fifth
+MLPF_C = (128, 256)
+MLPF_KINDS = ("int", "xl", "w2l", "ll")
+
+
+def mlp_fused_preact(x, W1, b1):
+    """fc1(x) + b1 as the kernel has it in front of the GELU: float64[M, hidden], every stage asserted exact."""
+    return three_product_op(x, W1, _linear, b1)
+
+
+def mlp_fused_hidden(pre):
+    """The activation model: gelu_erf == max(., 0) for fc2's fp16 operand when no pre-activation lies in (-6, 6).  EVERY element
+    is held to that (AssertionError otherwise): the model is a condition on the inputs, not a tolerance."""
+    assert bool((pre.abs() >= GELU_EXACT_FROM).all()), \
+        f"pre-activation {float(pre[pre.abs() < GELU_EXACT_FROM][0])} inside (-6, 6): gelu_erf is not max(x, 0) there"
+    return pre.clamp_min(0.0)
+
+
+def mlp_fused_expected(x, W1, b1, W2, b2, gamma, resid):
+    """What gdrnpp_convnext_mlp_f32_fused must store: x f32[M, C], W1 f32[4C, C], W2 f32[C, 4C] -> float64[M, C] =
+    resid + gamma * ((hH lW2^T + lH hW2^T + hH hW2^T) 2^-e2 + b2), H = max((hx lW1^T + lx hW1^T + hx hW1^T) 2^-e1 + b1, 0) = hH + lH.
+    Each GEMM with its own weight scale, the l * l term dropped in both."""
+    hidden = mlp_fused_hidden(mlp_fused_preact(x, W1, b1))
+    return three_product_op(hidden.float(), W2, _linear, b2, gamma, resid)
+
+
+def _nonzero_ints(shape, vmax, gen):
+    shape = tuple(shape)
+    return (torch.randint(1, vmax + 1, shape, generator=gen) * (torch.randint(0, 2, shape, generator=gen) * 2 - 1)).float()
+
+
+def sparse_rows(rows, cols, nnz, values, gen):
+    """f32[rows, cols] with ``values`` [rows, nnz] (all non-zero) on exactly nnz columns per row.  Row r sits on columns
+    perm[(r mod S) + S i], S = cols / nnz, i < nnz, of one random permutation: with rows >= S every column is used."""
+    s = cols // nnz
+    assert s * nnz == cols and rows >= s and bool((values != 0).all())
+    perm = torch.randperm(cols, generator=gen)
+    col = perm[(torch.arange(rows) % s)[:, None] + s * torch.arange(nnz)[None, :]]
+    w = torch.zeros(rows, cols)
+    w[torch.arange(rows)[:, None], col] = values
+    return w
+
+
+def x_rows_in_range(x):
+    """The kernel's verdict on fc1's A rows: the sum of squares of the h halves of every NON-ZERO row is at least C / 256."""
+    ss = x.float().half().double().pow(2).sum(dim=1)
+    return bool(((ss == 0) | (ss >= x.shape[1] / 256.0)).all())
+
+
+@functools.lru_cache(maxsize=None)
+def mlp_fused_case(m, c, kind, seed=0):
+    """dict(x, W1, b1, W2, b2, gamma, resid, pre, want) of one fused-MLP launch, hidden = 4 c.  b1 comes from the data: unit j gets a
+    sign s_j and b1[j] = s_j (ceil(max_m |three-product(x, W1)[m, j]|) + 6) (ll: + 32) — about half the units are active (>= 6) for every
+    pixel, the others dead (<= -6) for every pixel.
+      int   x, W1, W2 dense small integers: l planes zero, the dense stress of indexing, weight ring and row tails;
+      xl    x and W1 on hl_lattice (W1: two non-zeros per row, so that the hidden values stay below 64 and are h + l), W2 integer
+            with 16 non-zeros per row: l planes of x, of W1 and of the hidden operand in use;
+      w2l   x integer, W1 integer with two non-zeros per row, W2 on hl_lattice with 8 non-zeros per row: l plane of W2 in use
+            (the hidden values are integers: l . l of fc2 is zero);
+      ll    x and W1 as in xl, W2 as in w2l: the l planes of the hidden operand AND of W2 in use, fc2's dropped l . l term is
+            non-zero — a kernel that adds it is wrong here and nowhere above."""
+    assert kind in MLPF_KINDS, kind
+    h = 4 * c
+    gen = _gen(100003 * m + 11 * c + seed + 1 + MLPF_KINDS.index(kind))
+    if kind == "int":
+        x, W1, W2 = (int_lattice(s, 5, 0.25, gen) for s in ((m, c), (h, c), (c, h)))
+    else:
+        if kind in ("xl", "ll"):
+            x = hl_lattice((m, c), gen)
+            W1 = sparse_rows(h, c, 2, hl_lattice((h, 2), gen, 0.0), gen)
+        else:
+            x = int_lattice((m, c), 5, 0.25, gen)
+            W1 = sparse_rows(h, c, 2, _nonzero_ints((h, 2), 5, gen), gen)
+        if kind == "xl":
+            W2 = sparse_rows(c, h, 16, _nonzero_ints((c, 16), 5, gen), gen)
+        else:
+            W2 = sparse_rows(c, h, 8, hl_lattice((c, 8), gen, 0.0), gen)
+    assert bool((W2 != 0).any(dim=0).all()), "a hidden unit no row of W2 reads"
+    assert x_rows_in_range(x), "a non-zero x row below the range of fc1's A operand"
+    sign = torch.randint(0, 2, (h,), generator=gen).float() * 2 - 1
+    # ll: active values from 32 on, where an fp16 ulp (2^-5) is above the lattice's fractions (< 2^-7) — the h halves of the
+    # hidden operand are integers, or h . l_W2 would need units of 2^-8 and the sums would leave 2^24
+    margin = 32.0 if kind == "ll" else GELU_EXACT_FROM
+    b1 = sign * (three_product_expected(x, W1).abs().amax(dim=0).ceil().float() + margin)
+    b2, gamma, resid = _small_ints((c,), gen), _gammas(c, gen), _small_ints((m, c), gen)
+    pre = mlp_fused_preact(x, W1, b1)
+    assert torch.equal(pre >= GELU_EXACT_FROM, (sign > 0).expand(m, h)) and 0 < int((sign > 0).sum()) < h      # every hidden row >= 36: in range
+    want = mlp_fused_expected(x, W1, b1, W2, b2, gamma, resid)
+    return dict(x=x, W1=W1, b1=b1, W2=W2, b2=b2, gamma=gamma, resid=resid, pre=pre, want=want)
+
+
+# ---- probes of the fused MLP: one launch per block q of C hidden units, gamma = 1, b2 = resid = 0 -------------------------------
+FC1_PROBE_B1 = 6.0                  # every unit active
+FC2_PROBE_T, FC2_PROBE_B = 7.0, 6.0    # the one live unit of a pixel holds 2 T - B = 8, all others -B
+
+
+def _codes(rows, cols):
+    """f32[rows, cols]: 1 + (row mod 61) cols + col, a distinct code per (row mod 61, col)."""
+    return (1 + (torch.arange(rows) % ONEHOT_MOD)[:, None] * cols + torch.arange(cols)[None, :]).float()
+
+
+def _decode(code, cols):
+    """(row class, col) per element of a tensor of codes (both -1 where the value is no code: a dropped or mixed term)."""
+    code = code - 1.0
+    ok = (code == code.round()) & (code >= 0) & (code < ONEHOT_MOD * cols)
+    code = torch.where(ok, code, torch.zeros_like(code)).long()
+    return torch.where(ok, code // cols, torch.full_like(code, -1)), torch.where(ok, code % cols, torch.full_like(code, -1))
+
+
+def _probe_x(M, C):
+    x = torch.zeros(M, C)
+    x[torch.arange(M), onehot_k(torch.arange(M), C)] = 2.0
+    return x
+
+
+def mlp_fc1_probe(M, C, q):
+    """Pixel m = 2 e_k(m) (row 0 needs the LAST k-step); W1[j, k] a code of (j mod 61, k); W2 selects hidden block q
+    (W2[o, C q + o] = 1) -> y[m, o] = 2 W1[C q + o, k(m)] + 6: an element names the hidden unit and the k the first GEMM used for
+    it — the x swizzle, the W1 fragment order and the accumulator-to-hidden map."""
+    H = 4 * C
+    x, W1, b1 = _probe_x(M, C), _codes(H, C), torch.full((H,), FC1_PROBE_B1)
+    W2 = torch.zeros(C, H)
+    W2[torch.arange(C), C * q + torch.arange(C)] = 1.0
+    b2, gamma, resid = torch.zeros(C), torch.ones(C), torch.zeros(M, C)
+    want = mlp_fused_expected(x, W1, b1, W2, b2, gamma, resid)
+    assert torch.equal(want, 2.0 * W1.double()[C * q:C * (q + 1), onehot_k(torch.arange(M), C)].t() + FC1_PROBE_B1)
+    return dict(x=x, W1=W1, b1=b1, W2=W2, b2=b2, gamma=gamma, resid=resid, want=want)
+
+
+def mlp_fc1_probe_decode(y, C):
+    """(hidden unit mod 61, k) the kernel used per element of y."""
+    return _decode((y.double() - FC1_PROBE_B1) / 2.0, C)
+
+
+def mlp_fc1_probe_report(y, want, C, q, limit=8):
+    bad = (y.double() != want).nonzero()
+    jmod, k = mlp_fc1_probe_decode(y, C)
+    lines = [f"{bad.shape[0]} of {want.numel()} elements differ"]
+    for m, o in bad[:limit].tolist():
+        lines.append(f"  (m={m}, o={o}): got {float(y[m, o])} = code of k {int(k[m, o])}, hidden class {int(jmod[m, o])}; "
+                     f"expected k {int(onehot_k(m, C))}, hidden unit {C * q + o} (class {(C * q + o) % ONEHOT_MOD})")
+    return "\n".join(lines)
+
+
+def mlp_fc2_probe(M, C, q):
+    """Pixel m has exactly ONE live hidden unit j(m) = C q + k(m) (W1[C q + k, k] = T, b1 = -B: 2 T - B = 8 there, -B <= -6
+    elsewhere); W2[o, j] a code of (o mod 61, j) -> y[m, o] = 8 W2[o, j(m)]: an element names the hidden unit the second GEMM
+    paired with that column of W2 — the W2 pack order against the accumulator order."""
+    H = 4 * C
+    x = _probe_x(M, C)
+    W1 = torch.zeros(H, C)
+    W1[C * q + torch.arange(C), torch.arange(C)] = FC2_PROBE_T
+    b1, W2 = torch.full((H,), -FC2_PROBE_B), _codes(C, H)
+    b2, gamma, resid = torch.zeros(C), torch.ones(C), torch.zeros(M, C)
+    want = mlp_fused_expected(x, W1, b1, W2, b2, gamma, resid)
+    live = 2.0 * FC2_PROBE_T - FC2_PROBE_B
+    assert torch.equal(want, live * W2.double()[:, mlp_fc2_probe_unit(torch.arange(M), C, q)].t())
+    return dict(x=x, W1=W1, b1=b1, W2=W2, b2=b2, gamma=gamma, resid=resid, want=want)
+
+
+def mlp_fc2_probe_unit(m, C, q):
+    return C * q + onehot_k(m, C)
+
+
+def mlp_fc2_probe_decode(y, C):
+    """(output channel mod 61, hidden unit) the kernel used per element of y."""
+    return _decode(y.double() / (2.0 * FC2_PROBE_T - FC2_PROBE_B), 4 * C)
+
+
+def mlp_fc2_probe_report(y, want, C, q, limit=8):
+    bad = (y.double() != want).nonzero()
+    omod, j = mlp_fc2_probe_decode(y, C)
+    lines = [f"{bad.shape[0]} of {want.numel()} elements differ"]
+    for m, o in bad[:limit].tolist():
+        lines.append(f"  (m={m}, o={o}): got {float(y[m, o])} = code of hidden unit {int(j[m, o])}, output class {int(omod[m, o])}; "
+                     f"expected hidden unit {int(mlp_fc2_probe_unit(m, C, q))}, output class {o % ONEHOT_MOD}")
+    return "\n".join(lines)
