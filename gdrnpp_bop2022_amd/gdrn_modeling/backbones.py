@@ -73,7 +73,7 @@ class ConvNeXtStage(nn.Module):
 
     def forward(self, x):
         if isinstance(self.downsample, nn.Sequential):   # LayerNorm2d -> 2x2 / stride-2 conv (implicit GEMM on the GPU)
-            x = hip_layers.conv2d(self.downsample[1], self.downsample[0](x))
+            x = hip_layers.downsample(self.downsample[0], self.downsample[1], x)
         return self.blocks(x)
 
 

@@ -112,13 +112,25 @@ def layernorm2d(ln: nn.LayerNorm, x: torch.Tensor) -> torch.Tensor:
     return y.permute(0, 3, 1, 2)
 
 
-def stem(conv: nn.Conv2d, ln: nn.LayerNorm, x: torch.Tensor) -> torch.Tensor:
-    """ConvNeXt stem: 4x4 / stride 4 convolution from 3 channels + LayerNorm2d.  One fused HIP kernel for the ConvNeXt-B shape
-    (NCHW-contiguous fp32 image, 128 output channels), else the module path."""
-    if (enabled_for(x) and _MLP_GEMM == "split" and x.dim() == 4 and x.is_contiguous() and x.dtype == torch.float32
+def _stem_shape_ok(conv: nn.Conv2d, ln: nn.LayerNorm, x: torch.Tensor) -> bool:
+    """Shapes the fused 4x4 stem kernel takes, forward and backward."""
+    return (_MLP_GEMM == "split" and x.dim() == 4 and x.is_contiguous() and x.dtype == torch.float32
             and conv.in_channels == 3 and conv.out_channels == 128 and conv.kernel_size == (4, 4) and conv.stride == (4, 4)
             and conv.padding == (0, 0) and conv.dilation == (1, 1) and conv.groups == 1 and ln.elementwise_affine
-            and x.shape[2] % 4 == 0 and x.shape[3] % 16 == 0 and x.shape[3] <= 1024):
+            and x.shape[2] % 4 == 0 and x.shape[3] % 16 == 0 and x.shape[3] <= 1024)
+
+
+def stem(conv: nn.Conv2d, ln: nn.LayerNorm, x: torch.Tensor) -> torch.Tensor:
+    """ConvNeXt stem: 4x4 / stride 4 convolution from 3 channels + LayerNorm2d.  One fused HIP kernel for the ConvNeXt-B shape
+    (NCHW-contiguous fp32 image, 128 output channels), else the module path.  With gradients enabled and ``set_train_kernels(True)``
+    the layer is ``StemConvLN`` when the image itself needs no gradient."""
+    if _train_ok(x):
+        if (_stem_shape_ok(conv, ln, x) and not x.requires_grad and not torch.is_autocast_enabled() and conv.padding_mode == "zeros"
+                and tuple(ln.normalized_shape) == (128,) and conv.weight.is_cuda and conv.weight.dtype == torch.float32
+                and (conv.bias is None or _param_ok(conv.bias)) and _param_ok(ln.weight, ln.bias)):
+            return StemConvLN.apply(x, conv.weight, conv.bias, ln.weight, ln.bias, ln.eps)
+        note_foreign_launch("stem: under autograd outside StemConvLN (image with a gradient, AMP, shape or layout outside the fused 4x4 stem kernel)")
+    if enabled_for(x) and _stem_shape_ok(conv, ln, x):
         cache = module_cache(conv)
         # the kernel reads [co][ci][ky][kx]; the module may hold the weight channels_last
         hit = cached(cache, "w_oihw", weight_tag(conv.weight),
@@ -136,12 +148,13 @@ def _dwconv_hip_ok(conv: nn.Conv2d, x: torch.Tensor) -> bool:
 
 # Training: layers that have a backward on this library's kernels take it under autograd when this switch is on (off by default:
 # with it off a forward under enable_grad runs PyTorch's operators, as it always has).  So far: dwconv_ln (DwConvLN) and convnext_mlp
-# (ConvNeXtMlp) — with both, a ConvNeXt block trains without a kernel that is not this library's — and the geometry head's layers:
+# (ConvNeXtMlp) — with both, a ConvNeXt block trains without a kernel that is not this library's — the stem (StemConvLN, for an image
+# that needs no gradient) and the stage entries (downsample: DownsampleLNConv), which close the ConvNeXt backbone, and the geometry head's layers:
 # conv3x3_groupnorm_act (Conv3x3GnAct), conv_transpose2d_groupnorm_act (ConvTranspose2dGn), groupnorm_act (GroupNormAct) and
 # upsample2x (Upsample2x), and the head's tail — the class-sliced 1x1 output layer, the class gather, the region softmax, the xyz
 # de-normalisation and the concatenation into Patch-PnP's input (HeadTail) — and Patch-PnP in its shipped ConvNeXt configuration on
 # the prepared input: the three [conv3x3 / stride 2, GroupNorm, GELU] layers (Conv3x3S2GnAct), the NCHW flatten (FlattenNCHW), fc1 and
-# fc2 with their GELU (LinearGelu) and the two pose heads (PnPHeads).  The stem and downsample layers, the ResNet path, AMP and
+# fc2 with their GELU (LinearGelu) and the two pose heads (PnPHeads).  The ResNet path, AMP and
 # Patch-PnP outside that configuration (act "relu", another norm, mask attention, odd sizes, the module path ``forward``) keep
 # PyTorch's graph.
 _TRAIN_KERNELS = False
@@ -507,6 +520,82 @@ def pnp_train(net: nn.Module, x96_cl: torch.Tensor):
     x = LinearGelu.apply(FlattenNCHW.apply(x), net.fc1.weight, net.fc1.bias)
     x = LinearGelu.apply(x, net.fc2.weight, net.fc2.bias)
     return PnPHeads.apply(x, net.fc_r.weight, net.fc_r.bias, net.fc_t.weight, net.fc_t.bias)
+
+
+class StemConvLN(torch.autograd.Function):
+    """The ConvNeXt stem [Conv2d(3 -> 128, 4x4/4), LayerNorm2d] with its backward on a HIP kernel (csrc/backbone_bwd.hip).  x (N,3,H,W)
+    NCHW without a gradient of its own -> y (N,128,H/4,W/4) channels_last, the bits of the inference forward.  The backward recomputes
+    the pre-norm activation and the statistics from x; saved are x and the parameters (the weight as the [co][ci][ky][kx] copy the
+    forward read)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, ln_weight, ln_bias, eps):
+        w = weight.detach().contiguous()      # the module may hold the weight channels_last; made per forward: the weight changes every step
+        ctx.save_for_backward(x, w, bias, ln_weight)
+        ctx.eps = eps
+        return hip_lib.stem_conv4x4_ln(x, w, bias, ln_weight, ln_bias, eps)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_y):
+        x, w, bias, ln_weight = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        grads = (None,) * 4
+        if any(need[1:5]):
+            grads = hip_lib.stem_conv4x4_ln_backward(x, w, bias, ln_weight, ctx.eps, _cl(grad_y), want=need[1:5])
+        return (None, *grads, None)
+
+
+class DownsampleLNConv(torch.autograd.Function):
+    """A ConvNeXt stage entry [LayerNorm2d(C), Conv2d(C -> Cout, 2x2/2)] with its backward on this library's kernels.  x (N,C,H,W)
+    channels_last -> z (N,Cout,H/2,W/2) channels_last.  The forward writes the LayerNorm's result in patch order (``layernorm_patch2x2``:
+    the bits of the inference LayerNorm) and runs the convolution as A Wp^T + b on ``linear_f32_exact`` (a depth of 4 C >= 512: past
+    the six-product kernel's accuracy) — not the bits of the inference forward's three-product convolution, as in
+    ``Conv3x3GnAct``.  Saved: x, the LayerNorm's weight, the convolution's weight and, when that weight takes a gradient, A (the
+    weight gradient's operand; kept, not recomputed: it is x's size and the forward has it in hand)."""
+
+    @staticmethod
+    def forward(ctx, x, ln_weight, ln_bias, eps, weight, bias):
+        n, _, h, w = x.shape
+        a = hip_lib.layernorm_patch2x2(x, ln_weight, ln_bias, eps)
+        z = hip_lib.linear_f32_exact(a, hip_lib.downsample_weight_nk(weight), bias)      # operand made per forward: the weight changes every step
+        ctx.save_for_backward(x, a if ctx.needs_input_grad[4] else None, ln_weight, weight)
+        ctx.eps = eps
+        return z.view(n, h // 2, w // 2, weight.shape[0]).permute(0, 3, 1, 2)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_z):
+        x, a, ln_weight, weight = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        want = (need[0], need[1], need[2], need[4], need[5])
+        dx = dg = dbeta = dw = db = None
+        if any(want):
+            dx, dg, dbeta, dw, db = hip_lib.downsample_backward(x, a, ln_weight, ctx.eps, weight, _cl(grad_z), want=want)
+        return dx, dg, dbeta, None, dw, db
+
+
+def _downsample_train_ok(ln: nn.Module, conv: nn.Module, x: torch.Tensor) -> bool:
+    """Shapes and state ``DownsampleLNConv`` takes: ``_train_ok``, no autocast, LayerNorm with weight and bias over C = 128, 256, 512 or
+    1024 channels, a dense 2x2 / stride 2 convolution without padding to a multiple of 128 channels, even H and W."""
+    if not (_train_ok(x) and not torch.is_autocast_enabled() and isinstance(ln, nn.LayerNorm) and isinstance(conv, nn.Conv2d)):
+        return False
+    c = x.shape[1]
+    return (ln.elementwise_affine and tuple(ln.normalized_shape) == (c,) and _param_ok(ln.weight, ln.bias) and c in (128, 256, 512, 1024)
+            and conv.in_channels == c and conv.out_channels % 128 == 0 and conv.kernel_size == (2, 2) and conv.stride == (2, 2)
+            and conv.padding == (0, 0) and conv.dilation == (1, 1) and conv.groups == 1 and conv.padding_mode == "zeros"
+            and conv.weight.is_cuda and conv.weight.dtype == torch.float32 and (conv.bias is None or _param_ok(conv.bias))
+            and x.shape[2] % 2 == 0 and x.shape[3] % 2 == 0 and 0 < x.shape[0] * x.shape[2] * x.shape[3] < (1 << 31) - 4096)
+
+
+def downsample(ln: nn.LayerNorm, conv: nn.Conv2d, x: torch.Tensor) -> torch.Tensor:
+    """A ConvNeXt stage entry: LayerNorm2d, then the 2x2 / stride 2 convolution — ``conv2d(conv, ln(x))``, the inference kernels or the
+    module path as those two decide.  With gradients enabled and ``set_train_kernels(True)`` the pair is ``DownsampleLNConv``."""
+    if _downsample_train_ok(ln, conv, x):
+        return DownsampleLNConv.apply(_cl(x), ln.weight, ln.bias, ln.eps, conv.weight, conv.bias)
+    if _TRAIN_KERNELS and _ENABLED and torch.is_grad_enabled() and x.is_cuda:
+        note_foreign_launch("downsample: under autograd outside DownsampleLNConv (odd size, another kernel, no affine LayerNorm, AMP)")
+    return conv2d(conv, ln(x))
 
 
 def _dwconv_train_ok(conv: nn.Conv2d, ln: nn.LayerNorm, x: torch.Tensor) -> bool:

@@ -34,6 +34,8 @@ from .net import (DENSE_MASK_TYPES, DENSE_SUMS, DENSE_XYZ_TYPES, LOSS_MASKS, PM_
                   bias_act_nhwc_, dwconv7x7_ln, dwconv7x7_ln_backward, gdrn_dense_losses, gdrn_dense_losses_backward, gdrn_pose_losses, groupnorm_act,
                   groupnorm_act_backward, groupnorm_act_train, head_tail_backward, head_tail_nhwc,
                   layernorm_nhwc, pnp_fc_heads, pnp_fc_heads_pose, point_pnp_fc, point_pnp_pool, stem_conv4x4_ln, upsample_bilinear2x, upsample_bilinear2x_backward)
+from .net import (downsample_backward, downsample_weight_nk, layernorm_patch2x2, layernorm_patch2x2_backward,  # noqa: F401
+                  stem_conv4x4_ln_backward)
 from .net import (RANGER_COEFS, RANGER_LONG_ROW, RANGER_LOOKAHEAD, RANGER_NAN_TO_NUM, RANGER_RECTIFIED, RANGER_TENSOR, RANGER_TILE,  # noqa: F401
                   RANGER_WORK, RangerTables, ranger_plan, ranger_same_layout, ranger_step, ranger_tensor_ok)
 from .pose import (GT_INFO_COLUMNS, XYZ_CROP_COLUMNS, MeshSet, bop_errors, decode_correspondences, depth_refine, epnp_batched, epnp_ransac,  # noqa: F401

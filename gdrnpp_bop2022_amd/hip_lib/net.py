@@ -6,6 +6,7 @@ import numpy as np
 import torch
 
 from .abi import DEFINES, STRUCTS, channels_last_f32, dev_ptr, f32_ptr, launch, load, nhwc_ptr, opt_f32_ptr
+from .gemm import colsum_f32, gemm_tn_f32, linear_f32_exact
 
 
 def dwconv7x7_ln(x, w49c, bias, ln_w=None, ln_b=None, eps: float = 1e-6, y_rows: bool = False):
@@ -154,6 +155,125 @@ def stem_conv4x4_ln(x_nchw, weight, bias, ln_weight, ln_bias, eps: float):
     launch("gdrnpp_stem_conv4x4_ln", f32_ptr(x_nchw, "x"), f32_ptr(weight, "weight"), opt_f32_ptr(bias, "bias"), f32_ptr(ln_weight, "ln_weight"),
            f32_ptr(ln_bias, "ln_bias"), out.data_ptr(), n, h, w, cout, float(eps))
     return out
+
+
+def _want(what: str, want, n: int):
+    want = tuple(bool(f) for f in want)
+    if len(want) != n or not any(want):
+        raise RuntimeError(f"{what}: want must hold {n} flags, at least one of them set")
+    return want
+
+
+def stem_conv4x4_ln_backward(x_nchw, weight, bias, ln_weight, eps: float, grad_y, want=(True,) * 4):
+    """``gdrnpp_stem_conv4x4_ln_backward``: the parameter gradients of ``stem_conv4x4_ln(x, ...)`` for grad_y = dL/dy (N,128,H/4,W/4)
+    channels_last -> (dweight [128,3,4,4], dbias, dln_weight, dln_bias).  ``want``: four flags in the order of the result — an entry is
+    None where its flag is false; without dweight the kernel runs without its matrix instructions.  ``ln_weight`` None: no LayerNorm
+    (du = grad_y; the last two flags must be false).  The pre-norm activation and the statistics are recomputed from x; the gradient with
+    respect to x is not formed.  Fixed summation order: two calls give the same bits."""
+    what = "stem_conv4x4_ln_backward"
+    want = _want(what, want, 4)
+    if ln_weight is None and (want[2] or want[3]):
+        raise RuntimeError(f"{what}: dln_weight / dln_bias asked for without a LayerNorm")
+    px = f32_ptr(x_nchw, "x")
+    if x_nchw.dim() != 4 or x_nchw.shape[1] != 3:
+        raise RuntimeError(f"{what}: x must be f32[N,3,H,W] (NCHW), got {tuple(x_nchw.shape)}")
+    n, _, h, w = x_nchw.shape
+    cout = weight.shape[0]
+    if tuple(weight.shape) != (cout, 3, 4, 4):
+        raise RuntimeError(f"{what}: weight must be f32[Cout,3,4,4], got {tuple(weight.shape)}")
+    nbytes = load().gdrnpp_stem_conv4x4_ln_backward_workspace_bytes(n, h, w, cout)
+    if nbytes == 0:
+        raise RuntimeError(f"{what}: N={n} H={h} W={w} Cout={cout} is outside the kernel (H % 4 == 0, W % 16 == 0, W <= 1024, Cout = 128)")
+    if not isinstance(grad_y, torch.Tensor) or tuple(grad_y.shape) != (n, cout, h // 4, w // 4):
+        raise RuntimeError(f"{what}: grad_y must be f32[{n},{cout},{h // 4},{w // 4}] channels_last, got {tuple(getattr(grad_y, 'shape', ()))}")
+    pg = nhwc_ptr(grad_y, "grad_y")
+    ws = torch.empty((nbytes // 8,), dtype=torch.float64, device=x_nchw.device)
+    dweight = torch.empty((cout, 3, 4, 4), dtype=torch.float32, device=x_nchw.device) if want[0] else None
+    dbias, dln_w, dln_b = (torch.empty((cout,), dtype=torch.float32, device=x_nchw.device) if f else None for f in want[1:])
+    m = n * (h // 4) * (w // 4)
+    launch("gdrnpp_stem_conv4x4_ln_backward", px, f32_ptr(weight, "weight"), opt_f32_ptr(bias, "bias"), opt_f32_ptr(ln_weight, "ln_weight"), pg,
+           *(t.data_ptr() if t is not None else None for t in (dweight, dbias, dln_w, dln_b)), n, h, w, cout, float(eps), ws.data_ptr(), nbytes,
+           timed=("mfma_f32:stem_bwd" if want[0] else "hbm:stem_bwd", 2.0 * m * cout * 48 * (want[0] + (ln_weight is not None)),
+                  4.0 * (x_nchw.numel() + grad_y.numel())))
+    return dweight, dbias, dln_w, dln_b
+
+
+def _patch_shape(what: str, x):
+    px = nhwc_ptr(x, "x")
+    n, c, h, w = x.shape
+    if load().gdrnpp_layernorm_patch2x2_backward_workspace_bytes(n, h, w, c) == 0:
+        raise RuntimeError(f"{what}: x {tuple(x.shape)} is outside the kernel (H, W even; C = 128, 256, 512 or 1024)")
+    return px, n, c, h, w
+
+
+def layernorm_patch2x2(x, ln_weight=None, ln_bias=None, eps: float = 1e-6):
+    """x (N,C,H,W) channels_last -> A f32[N H/2 W/2, 4 C]: LayerNorm over C per pixel — the bits of ``layernorm_nhwc`` — stored as the
+    operand of a 2x2 / stride 2 convolution run as a product: row = output pixel, column = (ky, kx, ci)
+    (``gdrnpp_layernorm_patch2x2_nhwc``).  ``ln_weight`` and ``ln_bias`` None: the space-to-depth copy alone."""
+    what = "layernorm_patch2x2"
+    px, n, c, h, w = _patch_shape(what, x)
+    if (ln_weight is None) != (ln_bias is None) or (ln_weight is not None and (ln_weight.numel() != c or ln_bias.numel() != c)):
+        raise RuntimeError(f"{what}: ln_weight and ln_bias must be f32[{c}], or both None")
+    a = torch.empty((n * (h // 2) * (w // 2), 4 * c), dtype=torch.float32, device=x.device)
+    launch("gdrnpp_layernorm_patch2x2_nhwc", px, opt_f32_ptr(ln_weight, "ln_weight"), opt_f32_ptr(ln_bias, "ln_bias"), a.data_ptr(), n, h, w, c,
+           float(eps), timed=("hbm:ln_patch2x2", 0.0, 8.0 * x.numel()))
+    return a
+
+
+def layernorm_patch2x2_backward(x, ln_weight, eps: float, d_a, want=(True,) * 3):
+    """``gdrnpp_layernorm_patch2x2_backward``: the adjoint of ``layernorm_patch2x2`` for d_a = dL/dA f32[N H/2 W/2, 4 C] -> (dx (N,C,H,W)
+    channels_last, dln_weight, dln_bias).  ``want``: three flags in that order, an entry is None where its flag is false.  The statistics
+    are recomputed from x.  ``ln_weight`` None: the inverse copy (dx alone; x gives the shape)."""
+    what = "layernorm_patch2x2_backward"
+    want = _want(what, want, 3)
+    px, n, c, h, w = _patch_shape(what, x)
+    if ln_weight is None and want != (True, False, False):
+        raise RuntimeError(f"{what}: without a LayerNorm dx alone is formed")
+    if not isinstance(d_a, torch.Tensor) or tuple(d_a.shape) != (n * (h // 2) * (w // 2), 4 * c):
+        raise RuntimeError(f"{what}: d_a must be f32[{n * (h // 2) * (w // 2)},{4 * c}], got {tuple(getattr(d_a, 'shape', ()))}")
+    nbytes = load().gdrnpp_layernorm_patch2x2_backward_workspace_bytes(n, h, w, c)
+    ws = torch.empty((nbytes // 8,), dtype=torch.float64, device=x.device)
+    dx = torch.empty_like(x, memory_format=torch.channels_last) if want[0] else None
+    dln_w, dln_b = (torch.empty((c,), dtype=torch.float32, device=x.device) if f else None for f in want[1:])
+    launch("gdrnpp_layernorm_patch2x2_backward", px, opt_f32_ptr(ln_weight, "ln_weight"), f32_ptr(d_a, "d_a"),
+           *(t.data_ptr() if t is not None else None for t in (dx, dln_w, dln_b)), n, h, w, c, float(eps), ws.data_ptr(), nbytes,
+           timed=("hbm:ln_patch2x2_bwd", 0.0, 4.0 * x.numel() * (2 + want[0])))
+    return dx, dln_w, dln_b
+
+
+def downsample_weight_nk(weight):
+    """nn.Conv2d weight [Cout,C,2,2] -> Wp f32[Cout, 4 C], column (ky, kx, ci): the nn.Linear form of the convolution over
+    ``layernorm_patch2x2``'s rows.  A view when the weight is held channels_last."""
+    cout, c = weight.shape[:2]
+    return weight.detach().permute(0, 2, 3, 1).reshape(cout, 4 * c).contiguous()
+
+
+def downsample_backward(x, a, ln_weight, eps: float, weight, dz, want=(True,) * 5):
+    """Gradients of z = conv2x2/2(LayerNorm2d(x)) run as z2d = A Wp^T + b with A = ``layernorm_patch2x2(x, ...)`` and Wp =
+    ``downsample_weight_nk(weight)``, for dz = dL/dz (N,Cout,H/2,W/2) channels_last -> (dx, dln_weight, dln_bias, dweight [Cout,C,2,2],
+    dbias).  ``want``: five flags in that order — an entry is None where its flag is false and the launches only it needs are left out;
+    the others keep their bits.  dA = dz Wp on ``linear_f32_exact``, then ``layernorm_patch2x2_backward``; dWp = dz^T A on
+    ``gemm_tn_f32`` (its slot tiles in the persistent workspace), returned as the [Cout,C,2,2] view of [Cout,2,2,C]; dbias =
+    ``colsum_f32``.  ``a`` is needed for dweight alone (None otherwise)."""
+    what = "downsample_backward"
+    want = _want(what, want, 5)
+    n, c, h, w = x.shape
+    cout = weight.shape[0]
+    if tuple(weight.shape) != (cout, c, 2, 2) or tuple(dz.shape) != (n, cout, h // 2, w // 2):
+        raise RuntimeError(f"{what}: weight {tuple(weight.shape)} / dz {tuple(dz.shape)} do not fit x {tuple(x.shape)}")
+    nhwc_ptr(dz, "dz")
+    dz2d = dz.permute(0, 2, 3, 1).reshape(n * (h // 2) * (w // 2), cout)      # a view of the NHWC memory
+    dx = dln_w = dln_b = dweight = dbias = None
+    if any(want[:3]):
+        d_a = linear_f32_exact(dz2d, downsample_weight_nk(weight), weight_kn=True)
+        dx, dln_w, dln_b = layernorm_patch2x2_backward(x, ln_weight, eps, d_a, want=want[:3])
+    if want[3]:
+        if a is None or tuple(a.shape) != (dz2d.shape[0], 4 * c):
+            raise RuntimeError(f"{what}: dweight needs a f32[{dz2d.shape[0]},{4 * c}]")
+        dweight = gemm_tn_f32(dz2d, a, persistent_ws=True).view(cout, 2, 2, c).permute(0, 3, 1, 2)
+    if want[4]:
+        dbias = colsum_f32(dz2d)[1]
+    return dx, dln_w, dln_b, dweight, dbias
 
 
 def head_tail_nhwc(out_nhwc, coord2d, extents, double_mask: bool):

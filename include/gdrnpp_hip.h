@@ -556,6 +556,36 @@ int gdrnpp_dwconv7x7_ln_backward(const float* x, const float* w49c, const float*
                                  const float* grad_y, float* dx, float* dw, float* db, float* dln_w,
                                  float* dln_b, int N, int H, int W, int C, float eps, void* workspace,
                                  size_t workspace_bytes, void* stream);
+/* Training kernels of the ConvNeXt stem and downsample layers (csrc/backbone_bwd.hip).  No atomics: partial sums go to fixed slots
+ * of the workspace, whose count depends on the shape alone, and are added in fp64 in a fixed order — two calls give equal bits.
+ *  stem_conv4x4_ln_backward : the parameter gradients of gdrnpp_stem_conv4x4_ln for grad_y = dL/dy f32 NHWC [N,H/4,W/4,128]: dw
+ *                 f32[128,3,4,4], db, dln_w, dln_b f32[128]; an output given as NULL is not computed (dw NULL: the kernel without its
+ *                 matrix instructions).  The pre-norm activation and the LayerNorm statistics are recomputed from x with the forward's
+ *                 own fma chain in (ci, ky, kx) order, carried in fp64; du, the LayerNorm backward of grad_y, stays in LDS; x and grad_y are read once.
+ *                 dw = du^T patches(x), [128 x M] [M x 48] with M = N H/4 W/4, on the exact-f32 matrix instruction with
+ *                 gemm_tn_f32's sums: fp32 chains of 32 rows (at most 128 is that kernel's rule) carried in fp64, the rows dealt to at
+ *                 most 256 slots (256-row chunks), an fp64 finalize.  ln_w == NULL: no LayerNorm, du = grad_y (weight and bias are then not read, dln_w and
+ *                 dln_b must be NULL).  bias may be NULL.  The gradient with respect to x is not formed.  Shapes of the forward:
+ *                 H % 4 == 0, W % 16 == 0, W <= 1024, Cout = 128.  workspace: gdrnpp_stem_conv4x4_ln_backward_workspace_bytes(N,H,W,Cout)
+ *                 bytes (slots x 6528 doubles), 16-byte aligned; 0 for a shape outside the kernel.
+ *  layernorm_patch2x2_nhwc : x f32 NHWC [N,H,W,C] -> A f32[N H/2 W/2, 4 C], row = output pixel of a 2x2 / stride 2 convolution, column
+ *                 = (ky, kx, ci): the values of gdrnpp_layernorm_nhwc bit for bit, stored in patch order.  ln_w == ln_b == NULL: the
+ *                 space-to-depth copy alone.  H, W even; C = 128, 256, 512 or 1024; N H W < 2^31 - 4096.  Every pointer of this and of
+ *                 the next entry point 16-byte aligned.
+ *  layernorm_patch2x2_backward : its adjoint for dA in the same layout: dx f32 NHWC, dln_w, dln_b f32[C] (each may be NULL), the
+ *                 statistics recomputed from x in fp64.  ln_w == NULL: the inverse copy (dx alone; x is not read, no workspace).
+ *                 workspace: gdrnpp_layernorm_patch2x2_backward_workspace_bytes(N,H,W,C) bytes (at most 512 x 2 C doubles), 16-byte
+ *                 aligned; 0 for a shape outside the kernel. */
+size_t gdrnpp_stem_conv4x4_ln_backward_workspace_bytes(int N, int H, int W, int Cout);
+int gdrnpp_stem_conv4x4_ln_backward(const float* x_nchw, const float* weight, const float* bias, const float* ln_w,
+                                    const float* grad_y, float* dw, float* db, float* dln_w, float* dln_b, int N, int H,
+                                    int W, int Cout, float eps, void* workspace, size_t workspace_bytes, void* stream);
+int gdrnpp_layernorm_patch2x2_nhwc(const float* x, const float* ln_w, const float* ln_b, float* A, int N, int H, int W,
+                                   int C, float eps, void* stream);
+size_t gdrnpp_layernorm_patch2x2_backward_workspace_bytes(int N, int H, int W, int C);
+int gdrnpp_layernorm_patch2x2_backward(const float* x, const float* ln_w, const float* dA, float* dx, float* dln_w,
+                                       float* dln_b, int N, int H, int W, int C, float eps, void* workspace,
+                                       size_t workspace_bytes, void* stream);
 /* Backward of the ConvNeXt MLP tail y = s + gamma (.) (gelu(x W1^T + b1) W2^T + b2) (csrc/mlp_bwd.hip): the kernels beside
  * gdrnpp_linear_f32_split, which runs the two data-gradient products dh = g (diag(gamma) W2) and dx = dpre W1 as it is.
  *  pack_weight_bf16x3_t : the image gdrnpp_pack_weight_bf16x3 makes of T = (diag(row_scale) W)^T, f32[K,R], read from W f32[R,K]
