@@ -306,7 +306,7 @@ __global__ __launch_bounds__(64) void pnp_iter_kernel(const float* __restrict__ 
                                                       const float* __restrict__ t_net, float* __restrict__ R_out,
                                                       float* __restrict__ t_out, int* __restrict__ info) {
   const int bi = blockIdx.x;
-  const int pn = count[bi];
+  const int pn = min(count[bi], stride);  // like every kernel of epnp_ransac.hip: never past this problem's rows
   const float* p2 = img_pts + (size_t)bi * stride * 2;
   const float* p3 = mdl_pts + (size_t)bi * stride * 3;
   const float* K = Kb + 9 * (size_t)bi;

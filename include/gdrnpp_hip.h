@@ -182,7 +182,8 @@ int gdrnpp_epnp_batched(const float* img_pts, const float* mdl_pts, int n, const
  * with the network pose = Levenberg-Marquardt on the plain reprojection error.  OpenCV's own LM is third-party and
  * not in the tree; the same restated LM as gdrnpp_uncertainty_pnp_batched is used with identity weights (both
  * converge to the minimiser of the same cost).  img_pts f32[b,stride,2], mdl_pts f32[b,stride,3] and count i32[b]
- * are the outputs of gdrnpp_decode_correspondences (stride = hw).  Reference fallbacks kept: count < 4 -> network
+ * are the outputs of gdrnpp_decode_correspondences (stride = hw); a count above stride is clamped to stride, as in
+ * gdrnpp_epnp_ransac, so a problem never reads another problem's rows.  Reference fallbacks kept: count < 4 -> network
  * pose (:355-358); |t_est - t_net| > 1 m -> network translation (:347-351, info status += 100).
  * K f32[b,9], R_net f32[b,9], t_net f32[b,3] -> R_out f32[b,9], t_out f32[b,3], info i32[b,2] or NULL. */
 int gdrnpp_pnp_iter_from_correspondences(const float* img_pts, const float* mdl_pts,

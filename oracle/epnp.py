@@ -50,12 +50,17 @@ class CvRNG:
 
 
 def get_subset(rng_next, count, model_points=5, max_attempts=1000):
-    """ptsetreg.cpp getSubset: model_points distinct indices, each ``next() % count``, redrawn while it repeats."""
+    """ptsetreg.cpp getSubset: model_points distinct indices, each ``next() % count``, redrawn while it repeats.  A finite word
+    source that runs dry (``rng_next`` raises StopIteration) ends the subset like the attempt cap does: None, and the caller makes
+    no further hypotheses — the meaning the device gives an injected stream that is shorter than the sets it is asked for."""
     idx = []
     iters = 0
     i = 0
     while i < model_points and iters < max_attempts:
-        cand = int(rng_next() % count)
+        try:
+            cand = int(rng_next() % count)
+        except StopIteration:
+            return None
         iters += 1            # OpenCV counts an attempt per full subset; a per-draw cap is unreachable for count >= 5 anyway
         if cand in idx:
             continue
