@@ -1,8 +1,13 @@
-"""The YOLOX detector: PAFPN over CSPDarknet, decoupled head; inference only.
+"""The YOLOX detector: PAFPN over CSPDarknet, decoupled head.
 
 ``forward(x)`` on an eval-mode model returns ``{"det_preds": f32[B, A, 5 + num_classes]}`` — the tensor
 ``det.yolox.utils.boxes.postprocess`` takes.  On the GPU with the HIP layers enabled the whole forward runs on
-csrc/yolox_net.hip (``hip_forward``); everywhere else it is the plain-PyTorch module path."""
+csrc/yolox_net.hip (``hip_forward``); everywhere else it is the plain-PyTorch module path.
+
+``forward(x, targets)`` on a train-mode model returns the reference's ``(out_dict, loss_dict)`` with ``loss_iou``, ``loss_conf``,
+``loss_l1`` and ``loss_cls``; ``targets`` f32[B,G,5] = (class, cx, cy, w, h) in pixels of ``x``, zero rows behind an image's gts.  The
+SimOTA assignment and the losses run on csrc/yolox_loss.hip (``losses.yolox_losses``); the network layers under the loss
+(convolutions, BatchNorm with batch statistics) stay on PyTorch's graph in training mode."""
 import torch.nn as nn
 
 from ....gdrn_modeling import hip_layers
@@ -28,8 +33,12 @@ class YOLOX(nn.Module):
     def forward(self, x, targets=None, augment=False, cfg=None):
         if augment:
             raise NotImplementedError("augment=True (multi-scale test: needs scale_img's interpolation) is not implemented")
-        if targets is not None or self.training:
-            raise NotImplementedError("training mode (targets / self.training: the SimOTA assignment and losses) is not implemented")
+        if self.training and targets is None:
+            raise NotImplementedError("training mode needs targets: model(x, targets) returns (out_dict, loss_dict)")
+        if targets is not None and not self.training:
+            raise NotImplementedError("targets are only taken in training mode (model.train()); eval mode returns det_preds")
+        if self.training:
+            return self.head(self.backbone(x), targets, x)
         if hip_layers.enabled_for(x) and hip_forward.supported(self, x):
             return hip_forward.forward(self, x)
         hip_layers.foreign("YOLOX: forward outside the HIP path (PyTorch operators)", x)

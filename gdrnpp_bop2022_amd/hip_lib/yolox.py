@@ -1,5 +1,5 @@
-"""The YOLOX detector: its forward on NHWC slice buffers (csrc/yolox_net.hip) and its two ends, letterbox and
-post-processing (csrc/yolox_pre.hip)."""
+"""The YOLOX detector: its forward on NHWC slice buffers (csrc/yolox_net.hip), its two ends, letterbox and
+post-processing (csrc/yolox_pre.hip), and its training: SimOTA assignment and losses (csrc/yolox_loss.hip)."""
 from __future__ import annotations
 
 import torch
@@ -118,3 +118,79 @@ def yolox_letterbox(images_u8, test_size=(640, 640), out=None, y_off: int = 0, f
     launch("gdrnpp_yolox_letterbox", dev_ptr(images_u8, torch.uint8, "images"), b, H, W, rh, rw, f32_ptr(out, "out"), ht, wt,
            1 if focus else 0, out.shape[-1] if focus else 0, int(y_off) if focus else 0)
     return out, r
+
+
+YOLOX_IOU_LOSSES = {"iou": 0, "giou": 1}
+YOLOX_CLS_LOSSES = {"bce": 0, "focal": 1}
+YOLOX_LOSS_KEYS = ("loss_iou", "loss_conf", "loss_l1", "loss_cls")      # the order of ``yolox_losses``'s result and of ``scale``
+
+
+def _yolox_train_args(what: str, raw, anchors, labels):
+    if raw.dim() != 3 or raw.shape[-1] < 6:
+        raise RuntimeError(f"{what}: raw must be f32[B,A,5+C], got {tuple(raw.shape)}")
+    b, a, s = raw.shape
+    if tuple(anchors.shape) != (a, 3):
+        raise RuntimeError(f"{what}: anchors must be f32[{a},3] (x_shift, y_shift, stride), got {tuple(anchors.shape)}")
+    if labels.dim() != 3 or labels.shape[0] != b or labels.shape[2] != 5:
+        raise RuntimeError(f"{what}: labels must be f32[{b},G,5] (class, cx, cy, w, h), got {tuple(labels.shape)}")
+    return (f32_ptr(raw, "raw"), f32_ptr(anchors, "anchors"), f32_ptr(labels, "labels")), b, a, s - 5, labels.shape[1]
+
+
+def yolox_assign(raw, anchors, labels):
+    """``gdrnpp_yolox_assign``: SimOTA for the whole batch, nothing read back.  raw f32[B,A,5+C] (the head's undecoded rows), anchors
+    f32[A,3], labels f32[B,G,5] -> (matched_gt i32[B,A] with -1 = background, matched_iou f32[B,A], num_fg i32[B], num_gt i32[B])."""
+    what = "yolox_assign"
+    ptrs, b, a, c, g = _yolox_train_args(what, raw, anchors, labels)
+    dev = raw.device
+    nbytes = load().gdrnpp_yolox_assign_workspace_bytes(b, a)
+    if nbytes == 0:
+        raise RuntimeError(f"{what}: B = {b}, A = {a}: too many anchors for one launch")
+    ws = torch.empty((nbytes // 4,), dtype=torch.float32, device=dev)
+    matched_gt = torch.empty((b, a), dtype=torch.int32, device=dev)
+    matched_iou = torch.empty((b, a), dtype=torch.float32, device=dev)
+    num_fg = torch.empty((b,), dtype=torch.int32, device=dev)
+    num_gt = torch.empty((b,), dtype=torch.int32, device=dev)
+    launch("gdrnpp_yolox_assign", *ptrs, b, a, c, g, matched_gt.data_ptr(), matched_iou.data_ptr(), num_fg.data_ptr(), num_gt.data_ptr(),
+           ws.data_ptr(), nbytes)
+    return matched_gt, matched_iou, num_fg, num_gt
+
+
+def _yolox_loss_opts(what: str, iou_loss_type: str, cls_loss_type: str, fl_alpha: float, fl_gamma: float, use_l1: bool):
+    if iou_loss_type not in YOLOX_IOU_LOSSES or cls_loss_type not in YOLOX_CLS_LOSSES:
+        raise NotImplementedError(f"{what}: iou_loss_type {iou_loss_type!r} / cls_loss_type {cls_loss_type!r}: the kernel has "
+                                  f"{tuple(YOLOX_IOU_LOSSES)} and {tuple(YOLOX_CLS_LOSSES)}")
+    return YOLOX_IOU_LOSSES[iou_loss_type], YOLOX_CLS_LOSSES[cls_loss_type], float(fl_alpha), float(fl_gamma), 1 if use_l1 else 0
+
+
+def yolox_losses(raw, anchors, labels, matched_gt, num_fg, num_gt, *, iou_loss_type: str = "iou", cls_loss_type: str = "bce",
+                 fl_alpha: float = 0.25, fl_gamma: float = 2.0, use_l1: bool = False):
+    """``gdrnpp_yolox_losses`` on ``yolox_assign``'s result -> out f64[6]: the four losses in the order of ``YOLOX_LOSS_KEYS`` (already
+    divided by num_fg, loss_iou already times 5), max(sum num_fg, 1), sum num_gt."""
+    what = "yolox_losses"
+    ptrs, b, a, c, g = _yolox_train_args(what, raw, anchors, labels)
+    opts = _yolox_loss_opts(what, iou_loss_type, cls_loss_type, fl_alpha, fl_gamma, use_l1)
+    if tuple(matched_gt.shape) != (b, a) or num_fg.numel() != b or num_gt.numel() != b:
+        raise RuntimeError(f"{what}: matched_gt i32[{b},{a}], num_fg / num_gt i32[{b}], got {tuple(matched_gt.shape)}, {tuple(num_fg.shape)}, "
+                           f"{tuple(num_gt.shape)}")
+    nbytes = load().gdrnpp_yolox_losses_workspace_bytes(b, a)
+    ws = torch.empty((nbytes // 8,), dtype=torch.float64, device=raw.device)
+    out = torch.empty((6,), dtype=torch.float64, device=raw.device)
+    launch("gdrnpp_yolox_losses", *ptrs, dev_ptr(matched_gt, torch.int32, "matched_gt"), dev_ptr(num_fg, torch.int32, "num_fg"),
+           dev_ptr(num_gt, torch.int32, "num_gt"), b, a, c, g, *opts, out.data_ptr(), ws.data_ptr(), nbytes)
+    return out
+
+
+def yolox_losses_backward(raw, anchors, labels, matched_gt, out, scale, *, iou_loss_type: str = "iou", cls_loss_type: str = "bce",
+                          fl_alpha: float = 0.25, fl_gamma: float = 2.0, use_l1: bool = False):
+    """``gdrnpp_yolox_losses_backward``: grad_raw f32[B,A,5+C] = the gradient of sum_k scale[k] * loss_k by raw, recomputed from the
+    forward's inputs.  out f64[6]: ``yolox_losses``'s result; scale f32[4] in the order of ``YOLOX_LOSS_KEYS``.  Both stay on the device."""
+    what = "yolox_losses_backward"
+    ptrs, b, a, c, g = _yolox_train_args(what, raw, anchors, labels)
+    opts = _yolox_loss_opts(what, iou_loss_type, cls_loss_type, fl_alpha, fl_gamma, use_l1)
+    if tuple(matched_gt.shape) != (b, a) or out.numel() != 6 or scale.numel() != 4:
+        raise RuntimeError(f"{what}: matched_gt i32[{b},{a}], out f64[6], scale f32[4], got {tuple(matched_gt.shape)}, {tuple(out.shape)}, "
+                           f"{tuple(scale.shape)}")
+    grad = torch.empty_like(raw)
+    launch("gdrnpp_yolox_losses_backward", *ptrs, dev_ptr(matched_gt, torch.int32, "matched_gt"), dev_ptr(out, torch.float64, "out"),
+           f32_ptr(scale, "scale"), b, a, c, g, *opts, grad.data_ptr())
+    return grad

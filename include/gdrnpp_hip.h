@@ -1157,6 +1157,42 @@ typedef struct gdrnpp_ranger_long_row {
 int gdrnpp_ranger_step(const gdrnpp_ranger_tensor* tensors, int n_tensors, const gdrnpp_ranger_work* work, int n_work,
                        const gdrnpp_ranger_long_row* long_rows, int n_long_rows, float* long_means, void* stream);
 
+/* ---- YOLOX training (csrc/yolox_loss.hip) — get_losses / get_assignments / get_in_boxes_info / dynamic_k_matching of
+ * det/yolox/models/yolo_head.py:256-627 and IOUloss of det/yolox/models/losses.py, for the whole batch with no host round trip ----
+ * raw f32[B,A,5+C]: the head's undecoded rows (reg 4, objectness logit, C class logits), levels concatenated in level order, each
+ * level row-major.  anchors f32[A,3] = (x_shift, y_shift, stride).  labels f32[B,G,5] = (class, cx, cy, w, h); the gts of an image
+ * are its first num_gt rows, num_gt = the number of rows whose five values sum to more than 0 (the reference's rule).
+ *
+ * gdrnpp_yolox_assign (no gradient): decode xy = (raw + shift) stride, wh = exp(raw) stride; candidates = anchors whose cell centre
+ * lies inside any gt box or any gt's 2.5-stride centre square; per (gt, candidate) the IoU of bboxes_iou(xyxy=False) and
+ *   cost = sum_c BCE(sqrt(sigmoid(cls_c) sigmoid(obj)), onehot) [logs clamped at -100] + 3 (-log(iou + 1e-8)) + 1e5 [not (in box and in centre)]
+ * all in fp32, every product and sum rounded on its own.  Per gt dynamic_k = max(1, int(sum of the 10 largest IoUs)) and the dynamic_k
+ * lowest-cost candidates are chosen; an anchor chosen by several gts goes to the argmin of the cost over ALL gts of the image; ties
+ * go to the lowest index.  -> matched_gt i32[B,A] (-1 = background), matched_iou f32[B,A] (0 on background), num_fg i32[B],
+ * num_gt i32[B].  A gt without any candidate anchor gets no foreground (the reference raises there); a class outside [0, C) has no
+ * positive class term (the reference's one_hot raises there).  workspace: gdrnpp_yolox_assign_workspace_bytes(B, A) bytes. */
+size_t gdrnpp_yolox_assign_workspace_bytes(int B, int A);
+int gdrnpp_yolox_assign(const float* raw, const float* anchors, const float* labels, int B, int A, int C, int G, int* matched_gt,
+                        float* matched_iou, int* num_fg, int* num_gt, void* workspace, size_t workspace_bytes, void* stream);
+
+/* gdrnpp_yolox_losses: out f64[6] = loss_iou, loss_conf, loss_l1, loss_cls, num_fg = max(sum of num_fg[b], 1), sum of num_gt[b] with
+ *   loss_iou  = 5 sum_fg IOUloss(decoded box, gt box) / num_fg     iou_type 0: 1 - iou^2 (1e-16 in the denominator), 1: giou with its clamps
+ *   loss_conf = sum over all anchors of BCEWithLogits(obj, [foreground]) / num_fg
+ *   loss_cls  = sum_fg,c BCEWithLogits(cls_c, onehot_c iou of the match) / num_fg     cls_type 1: fvcore's sigmoid_focal_loss(fl_alpha, fl_gamma)
+ *   loss_l1   = sum_fg |raw reg - (gt_xy / stride - shift, log(gt_wh / stride + 1e-8))| / num_fg with use_l1, else 0
+ * Per-anchor terms in fp64 from the fp32 inputs (the decode and the match's IoU included), per-workgroup partials (workspace) added in
+ * a fixed tree and then in workgroup order: equal bits on every run.
+ * gdrnpp_yolox_losses_backward: recomputes from the same inputs and writes grad_raw f32[B,A,5+C] = the gradient of
+ * scale[0] loss_iou + scale[1] loss_conf + scale[2] loss_l1 + scale[3] loss_cls by raw, the decode's chain rule inside; the match, its
+ * IoU and num_fg are constants.  out: the forward's result; scale f32[4]; both read on the device. */
+size_t gdrnpp_yolox_losses_workspace_bytes(int B, int A);
+int gdrnpp_yolox_losses(const float* raw, const float* anchors, const float* labels, const int* matched_gt, const int* num_fg,
+                        const int* num_gt, int B, int A, int C, int G, int iou_type, int cls_type, float fl_alpha, float fl_gamma, int use_l1,
+                        double* out, void* workspace, size_t workspace_bytes, void* stream);
+int gdrnpp_yolox_losses_backward(const float* raw, const float* anchors, const float* labels, const int* matched_gt, const double* out,
+                                 const float* scale, int B, int A, int C, int G, int iou_type, int cls_type, float fl_alpha, float fl_gamma,
+                                 int use_l1, float* grad_raw, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

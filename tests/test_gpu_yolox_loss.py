@@ -1,0 +1,190 @@
+"""-m gpu: YOLOX's SimOTA assignment and detection losses on the device — ``gdrnpp_yolox_assign``, ``gdrnpp_yolox_losses`` and
+``gdrnpp_yolox_losses_backward`` (csrc/yolox_loss.hip) through ``det.yolox.models.losses.yolox_losses`` and the head's training mode.
+The yardstick is tests/yolox_loss_ref.py in fp64 on the CPU, which tests/test_yolox_loss_cpu.py ties to the reference's own get_losses
+(tests/golden/yolox_loss_golden_<case>.npz).
+
+Bars.  The assignment (matched_gt, the matched_iou > 0 pattern, num_fg, num_gt) is EQUAL to the fixture's: its inputs have asserted
+selection margins of 1e-3 against a host fp32 cost distance e_cost of 4e-5.  Each loss and each element of the raw-output gradient:
+|ours - ref64| <= 2 e_ref + one fp32 ulp of the value, e_ref = the reference's own fp32 distance from ref64 as stored per case; the factor
+2 is for the device's transcendental functions.  matched_iou values: an fp32 IoU is a quotient of products of differences of corners;
+corners carry <= 3 ulp of a coordinate <= 160 px (expf <= 2 ulp, one product, one sum), and the matched pairs' intersections are >= 2 px
+wide, so the cancellation amplifies by <= 80: 256 ulp of 1 = 1.5e-5 bounds it.
+Measured on an MI355X (all four cases): every loss and every gradient element within 0.5 fp32 ulp of ref64 (the kernels form every
+term in fp64 and round once; largest loss distance 7.0e-7 at loss_conf = 23.4 against a bar of 3.3e-6, largest gradient distance
+1.4e-8 against e_ref 7e-8 .. 2.5e-7); max |matched_iou - ref64| = 4.5e-7, the reference's own fp32 distance to the digit."""
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from gdrnpp_bop2022_amd import hip_lib
+from gdrnpp_bop2022_amd.det.yolox import models as M
+from gdrnpp_bop2022_amd.det.yolox.models import losses as L
+from gdrnpp_bop2022_amd.gdrn_modeling import hip_layers
+from tests import yolox_loss_ref as R
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda"
+HERE = os.path.dirname(os.path.abspath(__file__))
+CASES = ("a_iou_bce", "a_giou_focal_l1", "b_iou_bce_l1", "b21_giou_focal")
+_CACHE = {}
+
+
+def ulp32(v):
+    return np.spacing(np.abs(np.asarray(v, np.float64)).astype(np.float32)).astype(np.float64)
+
+
+def case_data(case):
+    """Fixture, options, anchors and the fp64 yardstick (losses, gradient, matched_iou) of a case: computed once, shared, never changed."""
+    if case not in _CACHE:
+        z = np.load(os.path.join(HERE, "golden", f"yolox_loss_golden_{case}.npz"))
+        opts = dict(iou_loss_type=str(z["iou_loss_type"]), cls_loss_type=str(z["cls_loss_type"]), use_l1=bool(z["use_l1"]),
+                    fl_alpha=float(z["fl_alpha"]), fl_gamma=float(z["fl_gamma"]))
+        anchors = R.anchor_table([tuple(r) for r in z["hw"].tolist()], z["strides"].tolist())
+        leaf = torch.from_numpy(z["raw"]).double().requires_grad_(True)
+        l64, info = R.losses(leaf, anchors, torch.from_numpy(z["labels"]).double(), **opts)
+        sum(l64.values()).backward()
+        _CACHE[case] = (z, opts, anchors, {k: float(v.detach()) for k, v in l64.items()}, leaf.grad.numpy().copy(), info["matched_iou"].numpy().copy())
+    return _CACHE[case]
+
+
+def run_device(z, opts, anchors, labels=None):
+    raw = torch.from_numpy(z["raw"]).to(DEV).requires_grad_(True)
+    labels = torch.from_numpy(z["labels"] if labels is None else labels).to(DEV)
+    losses, info = L.yolox_losses(raw, anchors.float().to(DEV), labels, **opts)
+    sum(losses.values()).backward()
+    return losses, info, raw.grad
+
+
+@pytest.mark.parametrize("case", CASES)
+def test_assignment_losses_and_gradient_against_fixture_and_fp64(case):
+    z, opts, anchors, l64, g64, iou64 = case_data(case)
+    before = hip_layers.fallback_launches()
+    losses, info, grad = run_device(z, opts, anchors)
+    assert hip_layers.fallback_launches() == before        # nothing of the loss ran on PyTorch operators
+    assert list(losses) == ["loss_iou", "loss_conf", "loss_l1", "loss_cls"]
+    matched_gt, matched_iou = info["matched_gt"].cpu().numpy(), info["matched_iou"].cpu().numpy()
+    assert matched_gt.dtype == np.int32 and np.array_equal(matched_gt, z["matched_gt"])
+    assert np.array_equal(matched_iou > 0, z["matched_iou"] > 0) and np.array_equal(matched_gt >= 0, z["fg_mask"])
+    assert np.array_equal(info["num_fg"].cpu().numpy(), z["num_fg"]) and np.array_equal(info["num_gt"].cpu().numpy(), z["num_gt"])
+    d_iou = float(np.abs(matched_iou - iou64).max())
+    print(f"{case}: max |matched_iou - ref64| = {d_iou:.3g} (reference fp32: {float(z['e_ref_iou']):.3g})")
+    assert d_iou <= 256 * 2.0 ** -24
+    for k in R.KEYS:
+        d, bar = abs(float(losses[k].detach()) - l64[k]), 2 * float(z[f"e_ref_{k}"]) + float(ulp32(l64[k]))
+        print(f"{case}: {k} = {float(losses[k].detach()):.8g}, |ours - ref64| = {d:.3g}, bar {bar:.3g} (e_ref {float(z[f'e_ref_{k}']):.3g})")
+        assert d <= bar, (k, d, bar)
+    g = grad.cpu().numpy().astype(np.float64)
+    d, bar = np.abs(g - g64), 2 * float(z["e_ref_grad"]) + ulp32(g64)
+    print(f"{case}: gradient max |ours - ref64| = {d.max():.3g}, in fp32 ulps of the value {np.max(d / ulp32(g64)):.3g}, e_ref {float(z['e_ref_grad']):.3g}")
+    assert np.all(d <= bar), float((d - bar).max())
+    want_ratio = max(int(z["num_fg"].sum()), 1) / max(int(z["num_gt"].sum()), 1)
+    assert abs(float(info["num_fg_ratio"]) - want_ratio) <= 1e-6 * want_ratio
+
+
+@pytest.mark.parametrize("case", ("a_giou_focal_l1", "b_iou_bce_l1"))
+def test_two_runs_are_bit_equal(case):
+    z, opts, anchors = case_data(case)[:3]
+    l1, i1, g1 = run_device(z, opts, anchors)
+    l2, i2, g2 = run_device(z, opts, anchors)
+    assert all(torch.equal(l1[k], l2[k]) for k in l1) and torch.equal(g1, g2)
+    assert all(torch.equal(i1[k], i2[k]) for k in ("matched_gt", "matched_iou", "num_fg", "num_gt"))
+
+
+@pytest.mark.parametrize("case", ("a_iou_bce", "b21_giou_focal"))
+def test_one_images_labels_do_not_reach_the_other_images(case):
+    z, opts, anchors = case_data(case)[:3]
+    _, base, _ = run_device(z, opts, anchors)
+    labels = z["labels"].copy()
+    crowded = int(np.argmax(z["num_gt"]))
+    labels[crowded] = 0.0
+    labels[crowded, 0] = labels[(crowded + 1) % len(labels), 0] if z["num_gt"][(crowded + 1) % len(labels)] else [1.0, 40.3, 30.3, 20.2, 20.2]
+    _, changed, _ = run_device(z, opts, anchors, labels)
+    others = [b for b in range(len(labels)) if b != crowded]
+    for k in ("matched_gt", "matched_iou"):
+        assert torch.equal(base[k][others], changed[k][others]), k
+    assert not torch.equal(base["matched_gt"][crowded], changed["matched_gt"][crowded])
+    assert int(changed["num_gt"][crowded]) == 1
+
+
+def test_binding_checks_and_edge_inputs():
+    z, opts, anchors = case_data("a_iou_bce")[:3]
+    raw, anc = torch.from_numpy(z["raw"]).to(DEV), anchors.float().to(DEV)
+    # no label rows, only empty rows, a gt without a candidate anchor: no foreground, objectness alone over num_fg = 1
+    far = torch.zeros(raw.shape[0], 2, 5, device=DEV)
+    far[0, 0] = torch.tensor([1.0, 2000.0, 2000.0, 4.0, 4.0])
+    for labels, n_gt in ((torch.zeros(raw.shape[0], 0, 5, device=DEV), 0), (torch.zeros(raw.shape[0], 3, 5, device=DEV), 0), (far, 1)):
+        losses, info = L.yolox_losses(raw, anc, labels)
+        assert int((info["matched_gt"] >= 0).sum()) == 0 and int(info["num_fg"].sum()) == 0 and int(info["num_gt"].sum()) == n_gt
+        want = torch.nn.functional.binary_cross_entropy_with_logits(raw[..., 4].double(), torch.zeros_like(raw[..., 4]).double(), reduction="sum")
+        assert abs(float(losses["loss_conf"]) - float(want)) <= float(ulp32(float(want)))
+        assert float(losses["loss_iou"]) == 0.0 and float(losses["loss_cls"]) == 0.0 and float(losses["loss_l1"]) == 0.0
+    labels = torch.from_numpy(z["labels"]).to(DEV)
+    # the reference's rule: num_gt counts the rows with sum > 0 and the gts are the FIRST num_gt rows.  With an empty row between two
+    # valid ones the second valid row is counted but is no gt: its values reach nothing
+    gap = labels.clone()
+    gap[3] = 0.0
+    gap[3, 0], gap[3, 2] = labels[3, 0], labels[3, 1]
+    moved = gap.clone()
+    moved[3, 2] = torch.tensor([2.0, 50.3, 20.3, 30.2, 16.2], device=DEV)
+    (l_gap, i_gap), (l_moved, i_moved) = L.yolox_losses(raw, anc, gap, use_l1=True), L.yolox_losses(raw, anc, moved, use_l1=True)
+    assert i_gap["num_gt"].tolist() == [0, 1, 6, 2] and int((i_gap["matched_gt"][3] == 2).sum()) == 0
+    assert all(torch.equal(l_gap[k], l_moved[k]) for k in l_gap) and torch.equal(i_gap["matched_gt"], i_moved["matched_gt"])
+    # more label rows than a workgroup has threads (the gt count strides over them): 300 rows, the same gts, the same bits
+    wide = torch.zeros(raw.shape[0], 300, 5, device=DEV)
+    wide[:, :labels.shape[1]] = labels
+    (l_base, i_base), (l_wide, i_wide) = L.yolox_losses(raw, anc, labels), L.yolox_losses(raw, anc, wide)
+    assert all(torch.equal(l_base[k], l_wide[k]) for k in l_base)
+    assert all(torch.equal(i_base[k], i_wide[k]) for k in ("matched_gt", "matched_iou", "num_fg", "num_gt"))
+    with pytest.raises(RuntimeError, match="anchors"):
+        hip_lib.yolox_assign(raw, anc[:-1].contiguous(), labels)
+    with pytest.raises(RuntimeError, match="labels"):
+        hip_lib.yolox_assign(raw, anc, labels[:, :, :4].contiguous())
+    with pytest.raises(RuntimeError, match="float32"):
+        hip_lib.yolox_assign(raw.double(), anc, labels)
+    # the torch path on the device is counted as foreign, the kernels are not
+    before = hip_layers.fallback_launches()
+    L.yolox_losses(raw.double(), anc.double(), labels.double())
+    assert hip_layers.fallback_launches() == before + 1
+
+
+def test_head_in_training_mode_gives_the_direct_calls_losses():
+    torch.manual_seed(0)
+    net = M.build_yolox(0.33, 0.5, 3).to(DEV).train()
+    net.head.use_l1 = True
+    x = torch.randn(2, 3, 64, 96, device=DEV)
+    targets = torch.zeros(2, 4, 5, device=DEV)
+    targets[0, 0] = torch.tensor([1.0, 30.4, 28.3, 24.2, 30.1])
+    targets[0, 1] = torch.tensor([2.0, 65.4, 40.3, 20.2, 18.1])
+    targets[1, 0] = torch.tensor([0.0, 20.4, 40.3, 30.2, 22.1])
+    feats = net.backbone(x)
+    seen, inner = {}, net.head.get_losses
+
+    def spy(raw, labels):
+        seen["raw"] = raw
+        return inner(raw, labels)
+
+    net.head.get_losses = spy
+    before = hip_layers.fallback_launches()
+    out_dict, loss_dict = net.head(feats, targets, x)
+    raw = seen["raw"]
+    # the rows the head handed over are its layers' undecoded outputs in anchor order (BatchNorm and MIOpen do not promise equal bits
+    # from call to call: the layout is what is checked here) ...
+    with torch.no_grad():
+        rows = []
+        for k, f in enumerate(feats):
+            f = net.head.stems[k](f)
+            cls_feat, reg_feat = net.head.cls_convs[k](f), net.head.reg_convs[k](f)
+            rows.append(torch.cat([net.head.reg_preds[k](reg_feat), net.head.obj_preds[k](reg_feat), net.head.cls_preds[k](cls_feat)], 1).flatten(2))
+        assert tuple(raw.shape) == (2, 126, 8) and torch.allclose(raw, torch.cat(rows, 2).permute(0, 2, 1), rtol=1e-3, atol=1e-4)
+    # ... and the direct call on those rows gives the head's losses bit for bit
+    anchors = R.anchor_table([(8, 12), (4, 6), (2, 3)], [8, 16, 32]).float().to(DEV)
+    direct, info = L.yolox_losses(raw.detach(), anchors, targets, use_l1=True)
+    assert hip_layers.fallback_launches() == before
+    assert list(loss_dict) == ["loss_iou", "loss_conf", "loss_l1", "loss_cls"]
+    for k in loss_dict:
+        assert torch.equal(loss_dict[k], direct[k]), k
+    assert torch.equal(out_dict["num_fg"], info["num_fg_ratio"]) and int(info["num_fg"].sum()) > 0
+    sum(loss_dict.values()).backward()
+    assert all(p.grad is not None and torch.isfinite(p.grad).all() for p in net.parameters())
