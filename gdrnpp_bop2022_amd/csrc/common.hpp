@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdarg>
+#include <cstdint>
 #include <cstdlib>
 #include "../../include/gdrnpp_hip.h"
 
@@ -59,6 +60,16 @@ __device__ __forceinline__ float gelu_erf(float x) {
   const float r = fmaf(-u, __builtin_amdgcn_exp2f(q), fmaxf(x, 0.f));
   return x != x ? x : r;
 }
+
+// gelu'(x) = Phi(x) + x phi(x), the formula of PyTorch's backward, with ocml's erff / expf.  At |x| = FLT_MAX x^2 is inf, phi 0
+// and x phi 0: the derivative is Phi = 0 or 1.
+__device__ __forceinline__ float gelu_grad(float x) {
+  const float cdf = 0.5f * (1.0f + erff(x * 0.70710678118654752440f));
+  const float pdf = expf(-0.5f * x * x) * 0.39894228040143267794f;
+  return fmaf(x, pdf, cdf);
+}
+
+inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 // Device scratch of the host-pointer shims of the reference ABI (farthest_point_sampling, uncertainty_pnp): grow-only, one
 // block per host thread, re-allocated when the thread switches device; kept for the life of the process (no hipMalloc /

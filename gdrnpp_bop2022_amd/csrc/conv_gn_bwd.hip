@@ -10,35 +10,24 @@
 //   gn_bwd      pass 1: fp64 partial sums of dA and dA xhat per (image, slot, channel); finalize: slots in index order -> per-image
 //               channel sums, the group sums s1 / s2, and dgamma / dbeta over the images in index order; pass 2: dz.  y and a are
 //               recomputed from z with the forward's own expression; mean and rstd from the forward's partials by gn_apply_kernel's.
-//   wgrad       gemm_tn_kernel (mlp_bwd.hip) with the tap as a grid dimension: rows are the N H W pixels, the x operand is read at
-//               the tap's shifted pixel, zero outside the image.  fp32 chains of 128 rows, fp64 carries, slots added in index order.
+//   wgrad       the exact-f32 scheme of exact_gemm_device.hpp with the tap as a grid dimension: rows are the N H W pixels, the x
+//               operand is read at the tap's shifted pixel, zero outside the image.  fp32 chains of 128 rows, fp64 carries, slots
+//               added in index order.
 //   up_bwd      the adjoint of upsample2x_kernel (net_kernels.hip) in gather form.
 //   im2col      the adjoint of deconv_col2im_kernel (net_kernels.hip): the operand of the transposed convolution's two gradient GEMMs.
 // No atomics and no scratch; every sum has a fixed order, so two calls give equal bits.
-#include "gemm_split.hpp"
+#include "exact_gemm_device.hpp"
 #include <algorithm>
 #include <cstdint>
 
 namespace {
 
+using namespace gdrnpp::exactgemm;
+using gdrnpp::aligned16;
 using gdrnpp::gelu_erf;
-using gdrnpp::splitgemm::f32x16;
-using f4 = __attribute__((ext_vector_type(4))) float;
-__device__ __forceinline__ f4 ld4v(const float* p) { return *reinterpret_cast<const f4*>(p); }
-__device__ __forceinline__ void st4v(float* p, f4 v) { *reinterpret_cast<f4*>(p) = v; }
-
-constexpr int kThreads = 256;
-
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+using gdrnpp::gelu_grad;
 
 // ---- GroupNorm (+ GELU) backward ------------------------------------------------------------------------------------------------
-// gelu'(x) = Phi(x) + x phi(x) as mlp_bwd.hip's activation pass evaluates it (restated: it lives in that file's unnamed namespace)
-__device__ __forceinline__ float gelu_grad(float x) {
-  const float cdf = 0.5f * (1.0f + erff(x * 0.70710678118654752440f));
-  const float pdf = expf(-0.5f * x * x) * 0.39894228040143267794f;
-  return fmaf(x, pdf, cdf);
-}
-
 // mean and rstd of image n's groups into LDS: gn_apply_kernel's expression and summation order (net_kernels.hip), so that xhat has
 // the forward's bits.  256 threads; the caller synchronises.
 __device__ __forceinline__ void gn_group_stats(const double* __restrict__ part, int n, int P, int G, int HW, int cpg, float eps,
@@ -223,42 +212,35 @@ __global__ __launch_bounds__(kThreads) void gn_bwd_dz_kernel(const float* __rest
   }
 }
 
-// ---- slot plan of the weight gradient: mlp_bwd.hip's tn_plan with the nine taps counted as tiles ---------------------------------
-// At most min(64, 512 / tiles) slots: the grid stays within two workgroups per CU (a workgroup holds a CU's registers), and every
-// slot costs 9 Cin Cout doubles written and read once.
-constexpr int kBK = 32, kPitch = 132, kChainStages = 4, kSlotRows = 512, kSlotCap = 64, kTnGrid = 512;
-struct TnPlan { int slots; long rows; };
-inline TnPlan wgrad_plan(long M, int Cin, int Cout) {
-  const long tiles = 9l * (Cout / 128) * (Cin / 128);
-  const long cap = std::max<long>(1, std::min<long>(kSlotCap, kTnGrid / tiles));
-  const long chunks = (M + kSlotRows - 1) / kSlotRows;
-  const long per = (chunks + cap - 1) / cap;
-  return TnPlan{(int)((chunks + per - 1) / per), per * kSlotRows};
+// ---- slot plan of the weight gradient: row_slot_plan (exact_gemm_device.hpp) with the nine taps counted as tiles -----------------
+// At most min(64, 512 / tiles) slots, rounded down: the grid stays within two workgroups per CU (a workgroup holds a CU's registers),
+// and every slot costs 9 Cin Cout doubles written and read once.
+constexpr int kSlotRows = 512, kSlotCap = 64, kTnGrid = 512;
+inline SlotPlan wgrad_plan(long M, int Cin, int Cout) {
+  return row_slot_plan(M, 9l * (Cout / 128) * (Cin / 128), kSlotRows, kSlotCap, kTnGrid, false);
 }
 
 // ---- wgrad ----------------------------------------------------------------------------------------------------------------------
 // part[slot][tap][co][ci] (fp64) = sum over the slot's pixels of dz[pix][co] x[pix + tap][ci].  grid (co tile x ci tile, slot, tap);
-// the workgroup, the LDS images, the operand map and the sums are gemm_tn_kernel's.  A pixel whose shifted neighbour is outside its
-// image contributes nothing: both operands of that row are staged as zero (so a NaN in dz there stays out of the sum, as in the
-// definition).  Rows are pixels of the whole batch: a chunk may end mid image row or span images.
+// the workgroup, the LDS images, the operand map and the sums are exact_gemm_device.hpp's.  A pixel whose shifted neighbour is
+// outside its image contributes nothing: both operands of that row are staged as zero (so a NaN in dz there stays out of the sum,
+// as in the definition).  Rows are pixels of the whole batch: a chunk may end mid image row or span images.
 __global__ __launch_bounds__(kThreads) void conv3x3_wgrad_kernel(const float* __restrict__ dz, const float* __restrict__ x,
                                                                   double* __restrict__ part, int M, int H, int W, int Cin, int Cout,
                                                                   long rows_per_slot) {
   __shared__ float sA[kBK * kPitch];
   __shared__ float sB[kBK * kPitch];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave >> 1, wn = wave & 1;
   const int tiles2 = Cin / 128;
   const int n1_0 = ((int)blockIdx.x / tiles2) * 128, n2_0 = ((int)blockIdx.x % tiles2) * 128;
   const int tap = blockIdx.z, dy = tap / 3 - 1, dx = tap % 3 - 1, HW = H * W;
   const long r0 = (long)blockIdx.y * rows_per_slot, r1 = r0 + rows_per_slot < M ? r0 + rows_per_slot : M;
-  const int srow = tid >> 5, scol = (tid & 31) * 4;
-  const float* ap = dz + (size_t)n1_0 + scol;
-  const float* bp = x + (size_t)n2_0 + scol;
+  const float* ap = dz + (size_t)n1_0 + stage_col();
+  const float* bp = x + (size_t)n2_0 + stage_col();
   f4 ra[4], rb[4];
   auto fetch = [&](long r) {
 #pragma unroll
     for (int p = 0; p < 4; ++p) {
-      const long m = r + srow + 8 * p;
+      const long m = r + stage_row() + 8 * p;
       bool in = m < r1;
       if (in) {
         const int pix = (int)(m % HW), yy = pix / W + dy, xx = pix % W + dx;
@@ -268,62 +250,12 @@ __global__ __launch_bounds__(kThreads) void conv3x3_wgrad_kernel(const float* __
       rb[p] = in ? ld4v(bp + (size_t)(m + dy * W + dx) * Cin) : f4{0.f, 0.f, 0.f, 0.f};
     }
   };
-  f32x16 acc[2][2];
-  double carry[2][2][16];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f, carry[i][j][e] = 0.0;
-  auto fold = [&]() {
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) carry[i][j][e] += (double)acc[i][j][e], acc[i][j][e] = 0.f;
-  };
-  const float* la = sA + (lane >> 5) * kPitch + wm * 64 + (lane & 31);
-  const float* lb = sB + (lane >> 5) * kPitch + wn * 64 + (lane & 31);
+  Tile t;
+  t.clear();
   if (r0 < r1) fetch(r0);
-  int stage = 0;
-  for (long r = r0; r < r1; r += kBK) {
-    __syncthreads();  // every wave has read the previous stage
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-      st4v(sA + (srow + 8 * p) * kPitch + scol, ra[p]);
-      st4v(sB + (srow + 8 * p) * kPitch + scol, rb[p]);
-    }
-    __syncthreads();
-    if (r + kBK < r1) fetch(r + kBK);
-#pragma unroll 4
-    for (int s = 0; s < kBK / 2; ++s) {
-      const float a0 = la[2 * s * kPitch], a1 = la[2 * s * kPitch + 32];
-      const float b0 = lb[2 * s * kPitch], b1 = lb[2 * s * kPitch + 32];
-      acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
-      acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
-      acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
-      acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
-    }
-    if (++stage == kChainStages) {
-      fold();
-      stage = 0;
-    }
-  }
-  fold();
-  // D: column = lane & 31 (ci), row = (e & 3) + 8 (e >> 2) + 4 (lane >> 5) (co)
+  k_loop<kPitch, kPitch>(t, sA, sB, r0, r1, kBK, fetch, [&] { store_stage<false, false>(sA, sB, ra, rb); });
   double* out = part + ((size_t)blockIdx.y * 9 + tap) * Cout * Cin;
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const int n1 = n1_0 + wm * 64 + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5);
-        const int n2 = n2_0 + wn * 64 + j * 32 + (lane & 31);
-        out[(size_t)n1 * Cin + n2] = carry[i][j][e];
-      }
+  for_each_d(n1_0, n2_0, [=, &t](int i, int j, int e, int co, int ci) { out[(size_t)co * Cin + ci] = t.carry[i][j][e]; });
 }
 
 // dW[co][ci][tap] = fl(the slots in index order).  Thread i = (tap, co, ci), ci fastest: coalesced reads of every slot's plane.
@@ -482,11 +414,11 @@ int gdrnpp_conv3x3_wgrad_f32(const float* dz, const float* x, float* dW, int N, 
   const size_t need = gdrnpp_conv3x3_wgrad_f32_workspace_bytes(N, H, W, Cin, Cout);
   GDRNPP_REQUIRE(workspace_bytes >= need, GDRNPP_EINVAL, "%s: workspace of %zu bytes, %zu needed", what, workspace_bytes, need);
   const int M = N * H * W;
-  const TnPlan p = wgrad_plan(M, Cin, Cout);
+  const SlotPlan p = wgrad_plan(M, Cin, Cout);
   hipStream_t st = (hipStream_t)stream;
   double* part = (double*)workspace;
   hipLaunchKernelGGL(conv3x3_wgrad_kernel, dim3((unsigned)((Cout / 128) * (Cin / 128)), (unsigned)p.slots, 9), dim3(kThreads), 0, st, dz, x, part, M,
-                     H, W, Cin, Cout, p.rows);
+                     H, W, Cin, Cout, p.rows_per_slot);
   const size_t n = (size_t)9 * Cin * Cout;
   hipLaunchKernelGGL(conv3x3_wgrad_finalize_kernel, dim3((unsigned)((n + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, part, p.slots, Cin, Cout, dW);
   return gdrnpp::check_launch(what);

@@ -34,19 +34,6 @@ using namespace gdrnpp::splitgemm;
 #define SPLIT_OCC 2
 #endif
 
-// two fp32 -> three packed bf16 pairs with x = h + m + l exactly
-struct Split3 { unsigned h, m, l; };
-__device__ __forceinline__ Split3 split_pair(float x0, float x1) {
-  Split3 o;
-  f32x2 v = {x0, x1};
-  o.h = __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
-  f32x2 r = {x0 - __uint_as_float(o.h << 16), x1 - __uint_as_float(o.h & 0xffff0000u)};
-  o.m = __builtin_bit_cast(unsigned, __builtin_convertvector(r, bf16x2));
-  f32x2 q = {r[0] - __uint_as_float(o.m << 16), r[1] - __uint_as_float(o.m & 0xffff0000u)};
-  o.l = __builtin_bit_cast(unsigned, __builtin_convertvector(q, bf16x2));
-  return o;
-}
-
 // W f32[N][K] -> packed bf16 [N/128][K/16][3][2][128][8]; one thread per (row, k-block) = 8 consecutive k
 __global__ void pack_weight_kernel(const float* __restrict__ W, uint4* __restrict__ packed, int N, int K) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;

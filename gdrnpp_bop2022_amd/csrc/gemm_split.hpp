@@ -19,6 +19,19 @@ constexpr int OPER_SLOTS = 3 * KB * PLANE;  // uint4 slots per operand image (re
 constexpr int W_TILE_SLOTS = 3 * KB * BN;   // uint4 slots of one packed 128x16 weight tile
 enum { EPI_BIAS = 0, EPI_GELU = 1, EPI_SCALE_RES = 2 };
 
+// two fp32 -> three packed bf16 pairs with x = h + m + l exactly (both subtractions exact)
+struct Split3 { unsigned h, m, l; };
+__device__ __forceinline__ Split3 split_pair(float x0, float x1) {
+  Split3 o;
+  f32x2 v = {x0, x1};
+  o.h = __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
+  f32x2 r = {x0 - __uint_as_float(o.h << 16), x1 - __uint_as_float(o.h & 0xffff0000u)};
+  o.m = __builtin_bit_cast(unsigned, __builtin_convertvector(r, bf16x2));
+  f32x2 q = {r[0] - __uint_as_float(o.m << 16), r[1] - __uint_as_float(o.m & 0xffff0000u)};
+  o.l = __builtin_bit_cast(unsigned, __builtin_convertvector(q, bf16x2));
+  return o;
+}
+
 // Order of the six partial products inside one k-tile, identical in every split-GEMM kernel so that their results are
 // bitwise equal: grouped by the weight split (l, m, m, h, h, h) so that a kernel needs at most two of the three weight
 // fragment sets in registers at a time, small terms first inside a group.  (A split index, B split index): 0 = h, 1 = m, 2 = l.

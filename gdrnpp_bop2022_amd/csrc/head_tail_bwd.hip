@@ -6,23 +6,20 @@
 //
 //   tail     d_out  = the adjoint of head_tail_kernel from (g_pnp_in, g_planes) + g_out, one pass;
 //   dinput   dfeat[m] = d_out[m][0..n_out) W[sel[m / hw]]  on the exact-f32 matrix instruction, one fp32 chain in column order;
-//   wgrad    per ROI r the fp64 tile d_out[r]^T feat[r] and the fp64 column sums of d_out[r] through fixed row slots (gemm_tn's
-//            staging and sums, mlp_bwd.hip), then per class the ROIs in index order, the slots in index order, one rounding, written
-//            through the row table into gradients shaped like the output layer's parameters.
+//   wgrad    per ROI r the fp64 tile d_out[r]^T feat[r] and the fp64 column sums of d_out[r] through fixed row slots (the staging
+//            and sums of exact_gemm_device.hpp), then per class the ROIs in index order, the slots in index order, one rounding,
+//            written through the row table into gradients shaped like the output layer's parameters.
 // No floating-point atomics; slot counts depend on the shape alone: two calls give equal bits, and the rows of a class do not depend
 // on which other classes the batch holds.
-#include "gemm_split.hpp"
+#include "exact_gemm_device.hpp"
 #include <algorithm>
 #include <cstdint>
 
 namespace {
 
-using gdrnpp::splitgemm::f32x16;
-using f4 = __attribute__((ext_vector_type(4))) float;
-__device__ __forceinline__ f4 ld4v(const float* p) { return *reinterpret_cast<const f4*>(p); }
-__device__ __forceinline__ void st4v(float* p, f4 v) { *reinterpret_cast<f4*>(p) = v; }
+using namespace gdrnpp::exactgemm;
+using gdrnpp::aligned16;
 
-constexpr int kThreads = 256;
 constexpr int kMaxOut = 72;      // deepest sliced layer: 2 masks + xyz + 65 regions = 70, stored in 72 columns
 
 // ---- tail -----------------------------------------------------------------------------------------------------------------------
@@ -130,19 +127,20 @@ __global__ __launch_bounds__(kThreads) void head_tail_bwd_kernel(const float* __
 // ---- dinput ---------------------------------------------------------------------------------------------------------------------
 // dfeat[m][k] = sum_c d_out[m][c] W[s][c][k], c < n_out <= 72, on v_mfma_f32_32x32x2_f32: bit for bit one fmaf chain in column order
 // (72 terms with the zero-filled tail; the project's rule is chains of at most 128, so there are no fp64 carries here).
-//   workgroup   128 rows x 128 columns of dfeat, 4 waves of 64 x 64, the depth in three stages of 24.  hw % 256 == 0: the 128 rows lie
-//               in one ROI, the selector is uniform.  A selector outside [0, n_slices) writes NaN rows and reads no weight.
+//   workgroup   exact_gemm_device.hpp's 128 rows x 128 columns of dfeat, the depth in three stages of 24, each loaded and stored in
+//               one step.  hw % 256 == 0: the 128 rows lie in one ROI, the selector is uniform.  A selector outside [0, n_slices)
+//               writes NaN rows and reads no weight.
 //   d_out       read at its pitch, float4; elements at and beyond column n_out are replaced by 0 before they reach the LDS; stored
-//               transposed into the [c][row] image gemm_rows reads (pitch 133).
+//               transposed into the [c][row] image (pitch 133).
 //   W           read as it lies: row c of slice s is the B operand's k-row, 128 consecutive floats; rows at and beyond n_out are
 //               zero-filled and not read.
-constexpr int kDiBK = 24, kDiStages = kMaxOut / kDiBK, kPitchT = 133, kPitchN = 132;
+constexpr int kDiBK = 24, kDiStages = kMaxOut / kDiBK;
 __global__ __launch_bounds__(kThreads) void grouped_dinput_kernel(const float* __restrict__ d_out, int pitch, int n_out,
                                                                    const float* __restrict__ W, const int* __restrict__ sel, int n_slices,
                                                                    int hw, float* __restrict__ dfeat, int K) {
   __shared__ float sA[kDiBK * kPitchT];
-  __shared__ float sB[kDiBK * kPitchN];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave >> 1, wn = wave & 1;
+  __shared__ float sB[kDiBK * kPitch];
+  const int tid = threadIdx.x;
   const int tiles_n = K / 128;
   const long m0 = (long)(blockIdx.x / tiles_n) * 128;
   const int n0 = ((int)blockIdx.x % tiles_n) * 128;
@@ -154,15 +152,10 @@ __global__ __launch_bounds__(kThreads) void grouped_dinput_kernel(const float* _
     return;
   }
   const float* Ws = W + (size_t)s * n_out * K + n0;
-  f32x16 acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
-  const float* la = sA + (lane >> 5) * kPitchT + wm * 64 + (lane & 31);
-  const float* lb = sB + (lane >> 5) * kPitchN + wn * 64 + (lane & 31);
+  Acc t;      // one fp32 chain: no carries
+  t.clear();
+  const float* la = lane_a<kPitchT>(sA);
+  const float* lb = lane_b<kPitch>(sB);
   for (int st = 0; st < kDiStages; ++st) {
     const int k0 = st * kDiBK;
     __syncthreads();      // every wave has read the previous stage
@@ -178,54 +171,30 @@ __global__ __launch_bounds__(kThreads) void grouped_dinput_kernel(const float* _
       {   // B: 24 k-rows x 32 float4
         const int kr = idx >> 5, c4 = idx & 31;
         const f4 v = k0 + kr < n_out ? ld4v(Ws + (size_t)(k0 + kr) * K + 4 * c4) : f4{0.f, 0.f, 0.f, 0.f};
-        st4v(sB + kr * kPitchN + 4 * c4, v);
+        st4v(sB + kr * kPitch + 4 * c4, v);
       }
     }
     __syncthreads();
-#pragma unroll 4
-    for (int ks = 0; ks < kDiBK / 2; ++ks) {
-      const float a0 = la[2 * ks * kPitchT], a1 = la[2 * ks * kPitchT + 32];
-      const float b0 = lb[2 * ks * kPitchN], b1 = lb[2 * ks * kPitchN + 32];
-      acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
-      acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
-      acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
-      acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
-    }
+    t.mma<kPitchT, kPitch, kDiBK>(la, lb);
   }
-  // D: column = lane & 31, row = (e & 3) + 8 (e >> 2) + 4 (lane >> 5)
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int n = n0 + wn * 64 + j * 32 + (lane & 31);
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const long m = m0 + wm * 64 + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5);
-        dfeat[(size_t)m * K + n] = acc[i][j][e];
-      }
-    }
+  for_each_d(m0, n0, [=, &t](int i, int j, int e, long m, int n) { dfeat[(size_t)m * K + n] = t.acc[i][j][e]; });
 }
 
 // ---- wgrad ----------------------------------------------------------------------------------------------------------------------
 // Workgroup (column tile kt of K, row slot y, ROI r): the fp64 tile  d_out[r]^T feat[r]  [n_out padded to 128][128] over the slot's
-// rows of the ROI, with gemm_tn_kernel's staging and sums (mlp_bwd.hip): rows staged 32 at a time, global -> registers (the next
-// stage's loads fly under this stage's MFMAs) -> LDS [32][132] per operand, fp32 chains of 128 rows folded into fp64 carries.
+// rows of the ROI, by the scheme of exact_gemm_device.hpp with both operands staged as they lie.  The loop is written out here: the
+// column sums read the A image between the MFMAs and the fold, and a launch that wants no dW runs no MFMAs.
 //   d_out   read at its pitch; elements at and beyond column n_out (and whole float4s at and beyond the pitch) are zero-filled in the
 //           staging and never reach a sum.  Rows at and beyond the slot's end — the next slot's, or the next ROI's — are zero-filled and
 //           not read.
 //   db      the workgroups of column tile 0 also add the staged d_out rows column by column in fp64, in row order.
-//   slots   wgrad_plan: chunks of 512 rows dealt to at most 16 slots per ROI, and no more than bring the grid to 1024 workgroups; from
-//           (B, hw, K) alone.
+//   slots   wgrad_plan: chunks of 512 rows dealt to at most 16 slots per ROI, and no more than bring the grid to 1024 workgroups
+//           (rounded up); from (B, hw, K) alone.
 //   out     workspace  tiles f64[B][slots][n_out][K]  then  sums f64[B][slots][128].  A ROI whose selector is outside [0, n_slices)
 //           does nothing; the finalize never reads its part.
-constexpr int kWgBK = 32, kWgChainStages = 4, kWgSlotRows = 512, kWgSlotCap = 16, kWgGrid = 1024;
-struct WgPlan { int slots; long rows; };
-inline WgPlan wgrad_plan(int B, int hw, int K) {
-  const long tiles = (long)B * (K / 128);
-  const long cap = std::max<long>(1, std::min<long>(kWgSlotCap, (kWgGrid + tiles - 1) / tiles));
-  const long chunks = ((long)hw + kWgSlotRows - 1) / kWgSlotRows;
-  const long per = (chunks + cap - 1) / cap;
-  return WgPlan{(int)((chunks + per - 1) / per), per * kWgSlotRows};
+constexpr int kWgSlotRows = 512, kWgSlotCap = 16, kWgGrid = 1024;
+inline SlotPlan wgrad_plan(int B, int hw, int K) {
+  return row_slot_plan(hw, (long)B * (K / 128), kWgSlotRows, kWgSlotCap, kWgGrid, true);
 }
 
 template <bool WANT_W, bool WANT_B>
@@ -233,15 +202,13 @@ __global__ __launch_bounds__(kThreads) void grouped_wgrad_kernel(const float* __
                                                                   const float* __restrict__ feat, int K, const int* __restrict__ sel,
                                                                   int n_slices, int hw, long rows_per_slot, double* __restrict__ ws_w,
                                                                   double* __restrict__ ws_b) {
-  __shared__ float sA[kWgBK * kPitchN];
-  __shared__ float sB[kWgBK * kPitchN];
+  __shared__ float sA[kBK * kPitch];
+  __shared__ float sB[kBK * kPitch];
   const int r = blockIdx.z, slot = blockIdx.y, slots = gridDim.y, kt = blockIdx.x;
   const int cls = sel[r];
   if (cls < 0 || cls >= n_slices) return;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave >> 1, wn = wave & 1;
+  const int tid = threadIdx.x, scol = stage_col();
   const long r0 = (long)slot * rows_per_slot, r1 = r0 + rows_per_slot < hw ? r0 + rows_per_slot : hw;
-  // staging: thread -> rows (tid >> 5) + 8 p, p < 4, columns 4 (tid & 31) .. + 3
-  const int srow = tid >> 5, scol = (tid & 31) * 4;
   const float* ap = d_out + (size_t)r * hw * pitch + scol;
   const float* bp = feat + (size_t)r * hw * K + (size_t)kt * 128 + scol;
   const bool a_in = scol < pitch && scol < n_out;      // pitch % 4 == 0: the float4 lies inside the row
@@ -249,7 +216,7 @@ __global__ __launch_bounds__(kThreads) void grouped_wgrad_kernel(const float* __
   auto fetch = [&](long row) {
 #pragma unroll
     for (int p = 0; p < 4; ++p) {
-      const long m = row + srow + 8 * p;
+      const long m = row + stage_row() + 8 * p;
       const bool in = m < r1;
       f4 a = in && a_in ? ld4v(ap + (size_t)m * pitch) : f4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -258,73 +225,43 @@ __global__ __launch_bounds__(kThreads) void grouped_wgrad_kernel(const float* __
       if (WANT_W) rb[p] = in ? ld4v(bp + (size_t)m * K) : f4{0.f, 0.f, 0.f, 0.f};
     }
   };
-  f32x16 acc[2][2];
-  double carry[2][2][16];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f, carry[i][j][e] = 0.0;
-  auto fold = [&]() {
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) carry[i][j][e] += (double)acc[i][j][e], acc[i][j][e] = 0.f;
-  };
-  const float* la = sA + (lane >> 5) * kPitchN + wm * 64 + (lane & 31);
-  const float* lb = sB + (lane >> 5) * kPitchN + wn * 64 + (lane & 31);
+  Tile t;
+  t.clear();
+  const float* la = lane_a<kPitch>(sA);
+  const float* lb = lane_b<kPitch>(sB);
   const bool sums = WANT_B && kt == 0 && tid < 128;
   double colsum = 0.0;
   if (r0 < r1) fetch(r0);
   int stage = 0;
-  for (long row = r0; row < r1; row += kWgBK) {
+  for (long row = r0; row < r1; row += kBK) {
     __syncthreads();      // every wave has read the previous stage
 #pragma unroll
     for (int p = 0; p < 4; ++p) {
-      st4v(sA + (srow + 8 * p) * kPitchN + scol, ra[p]);
-      if (WANT_W) st4v(sB + (srow + 8 * p) * kPitchN + scol, rb[p]);
+      store_natural(sA, p, ra[p]);
+      if (WANT_W) store_natural(sB, p, rb[p]);
     }
     __syncthreads();
-    if (row + kWgBK < r1) fetch(row + kWgBK);
+    if (row + kBK < r1) fetch(row + kBK);
     if (WANT_W) {
-#pragma unroll 4
-      for (int s = 0; s < kWgBK / 2; ++s) {
-        const float a0 = la[2 * s * kPitchN], a1 = la[2 * s * kPitchN + 32];
-        const float b0 = lb[2 * s * kPitchN], b1 = lb[2 * s * kPitchN + 32];
-        acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
-        acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
-        acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
-        acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
-      }
-      if (++stage == kWgChainStages) {
-        fold();
+      t.mma<kPitch, kPitch, kBK>(la, lb);
+      if (++stage == kChainStages) {
+        t.fold();
         stage = 0;
       }
     }
     if (sums) {
 #pragma unroll 8
-      for (int k = 0; k < kWgBK; ++k) colsum += (double)sA[k * kPitchN + tid];
+      for (int k = 0; k < kBK; ++k) colsum += (double)sA[k * kPitch + tid];
     }
   }
   const size_t part = (size_t)r * slots + slot;
   if (sums) ws_b[part * 128 + tid] = colsum;
   if (WANT_W) {
-    fold();
-    // D: column = lane & 31 (k), row = (e & 3) + 8 (e >> 2) + 4 (lane >> 5) (output channel)
-    double* o = ws_w + part * n_out * K + (size_t)kt * 128;
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-          const int n1 = wm * 64 + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5);
-          const int n2 = wn * 64 + j * 32 + (lane & 31);
-          if (n1 < n_out) o[(size_t)n1 * K + n2] = carry[i][j][e];
-        }
+    t.fold();
+    double* o = ws_w + part * n_out * K;
+    for_each_d(0, kt * 128, [=, &t](int i, int j, int e, int n1, int n2) {
+      if (n1 < n_out) o[(size_t)n1 * K + n2] = t.carry[i][j][e];
+    });
   }
 }
 
@@ -358,8 +295,6 @@ __global__ __launch_bounds__(kThreads) void grouped_wgrad_finalize_kernel(const 
     db[row] = (float)s;
   }
 }
-
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 bool grouped_shape_ok(int B, int hw, int K, int n_out, int pitch) {
   return B > 0 && B <= 65535 && hw > 0 && hw % 256 == 0 && K > 0 && K % 128 == 0 && n_out > 0 && n_out <= kMaxOut && pitch >= kMaxOut &&
@@ -419,20 +354,20 @@ int gdrnpp_grouped_linear_wgrad_f32(const float* d_out, int pitch, int n_out, co
   GDRNPP_REQUIRE(workspace_bytes >= need && aligned16(workspace) && aligned16(d_out) && aligned16(feat), GDRNPP_EINVAL,
                  "gdrnpp_grouped_linear_wgrad_f32: workspace of %zu bytes, %zu needed; d_out, feat and the workspace 16-byte aligned",
                  workspace_bytes, need);
-  const WgPlan p = wgrad_plan(B, hw, K);
+  const SlotPlan p = wgrad_plan(B, hw, K);
   hipStream_t st = (hipStream_t)stream;
   double* ws_w = (double*)workspace;
   double* ws_b = ws_w + (size_t)B * p.slots * n_out * K;
   const dim3 grid((unsigned)(dW ? K / 128 : 1), (unsigned)p.slots, (unsigned)B);
   if (dW && db)
     hipLaunchKernelGGL((grouped_wgrad_kernel<true, true>), grid, dim3(kThreads), 0, st, d_out, pitch, n_out, feat, K, group_sel, n_slices, hw,
-                       p.rows, ws_w, ws_b);
+                       p.rows_per_slot, ws_w, ws_b);
   else if (dW)
     hipLaunchKernelGGL((grouped_wgrad_kernel<true, false>), grid, dim3(kThreads), 0, st, d_out, pitch, n_out, feat, K, group_sel, n_slices, hw,
-                       p.rows, ws_w, ws_b);
+                       p.rows_per_slot, ws_w, ws_b);
   else
     hipLaunchKernelGGL((grouped_wgrad_kernel<false, true>), grid, dim3(kThreads), 0, st, d_out, pitch, n_out, feat, K, group_sel, n_slices, hw,
-                       p.rows, ws_w, ws_b);
+                       p.rows_per_slot, ws_w, ws_b);
   hipLaunchKernelGGL(grouped_wgrad_finalize_kernel, dim3((unsigned)n_out, (unsigned)n_slices), dim3(kThreads), 0, st, ws_w, ws_b, group_sel, B,
                      p.slots, n_out, K, cls_rows, out_rows, dW, db);
   return gdrnpp::check_launch("gdrnpp_grouped_linear_wgrad_f32");

@@ -15,37 +15,19 @@
 //   gemm_tn    G[N1,N2] = sum_m A[m,N1] B[m,N2] on the exact-f32 matrix instruction, the weight-gradient product.
 // No floating-point atomics: every sum over rows goes to workspace slots whose count depends on the shape alone and is added in
 // slot order in fp64, so two calls give equal bits.
+#include "exact_gemm_device.hpp"
 #include "gemm_split.hpp"
 #include <algorithm>
 #include <cstdint>
 
 namespace {
 
+using namespace gdrnpp::exactgemm;
+using gdrnpp::aligned16;
 using gdrnpp::gelu_erf;
-using gdrnpp::splitgemm::bf16x2;
-using gdrnpp::splitgemm::f32x16;
-using gdrnpp::splitgemm::f32x2;
-using f4 = __attribute__((ext_vector_type(4))) float;
-__device__ __forceinline__ f4 ld4v(const float* p) { return *reinterpret_cast<const f4*>(p); }
-__device__ __forceinline__ void st4v(float* p, f4 v) { *reinterpret_cast<f4*>(p) = v; }
-
-constexpr int kThreads = 256;
+using gdrnpp::gelu_grad;
 
 // ---- pack_t ---------------------------------------------------------------------------------------------------------------------
-// The exact three-way bf16 split of gemm_split.hip (x = h + m + l, both subtractions exact), restated: it lives in that file's
-// unnamed namespace, and the split GEMMs are not to be touched.  The types are gemm_split.hpp's; the tests hold the two byte-equal.
-struct Split3 { unsigned h, m, l; };
-__device__ __forceinline__ Split3 split_pair(float x0, float x1) {
-  Split3 o;
-  f32x2 v = {x0, x1};
-  o.h = __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
-  f32x2 r = {x0 - __uint_as_float(o.h << 16), x1 - __uint_as_float(o.h & 0xffff0000u)};
-  o.m = __builtin_bit_cast(unsigned, __builtin_convertvector(r, bf16x2));
-  f32x2 q = {r[0] - __uint_as_float(o.m << 16), r[1] - __uint_as_float(o.m & 0xffff0000u)};
-  o.l = __builtin_bit_cast(unsigned, __builtin_convertvector(q, bf16x2));
-  return o;
-}
-
 // W f32[R][K] -> the packed image [K/128][R/16][3][2][128][8] of T = (diag(s) W)^T, T[n][r] = s[r] W[r][n] (one fp32 product, as
 // the ATen multiply it replaces).  One thread per (8 consecutive r, n), n fastest: a wave reads 64 consecutive floats of a row of W
 // eight times and writes 64 consecutive 16-byte slots three times.
@@ -79,14 +61,8 @@ __global__ __launch_bounds__(kThreads) void gelu_kernel(const float* __restrict_
 }
 
 // ---- act / colsum ---------------------------------------------------------------------------------------------------------------
-// gelu'(x) = Phi(x) + x phi(x), the formula of PyTorch's backward, with ocml's erff / expf: the pass moves 16 or 20 bytes per
-// element, the ~60 instructions hide behind them.  At |x| = FLT_MAX x^2 is inf, phi 0 and x phi 0: the derivative is Phi = 0 or 1.
-__device__ __forceinline__ float gelu_grad(float x) {
-  const float cdf = 0.5f * (1.0f + erff(x * 0.70710678118654752440f));
-  const float pdf = expf(-0.5f * x * x) * 0.39894228040143267794f;
-  return fmaf(x, pdf, cdf);
-}
-
+// gelu_grad (common.hpp) runs on ocml's erff / expf: the pass moves 16 or 20 bytes per element, the ~60 instructions hide behind
+// them.
 // A workgroup = 4 waves; lane l of every wave owns column quad 64 blockIdx.y + l, wave w the rows r0 + w, r0 + w + 4, ... of slot
 // blockIdx.x; a wave reads 1 KB of a row at a time.  Sums in fp64 per thread, the four waves added in wave order, one partial
 // [cols] per slot.
@@ -170,110 +146,39 @@ int launch_colsum(bool act, const float* x, float* io, float* h, const float* sc
 }
 
 // ---- gemm_tn --------------------------------------------------------------------------------------------------------------------
-// G[n1][n2] = sum_m A[m][n1] B[m][n2] on v_mfma_f32_32x32x2_f32.  With the sum over ROWS of two row-major operands the
-// instruction's operand map is the natural one: at k-step s lanes 0..31 hold 32 consecutive columns of row 2s, lanes 32..63 of row
-// 2s + 1, for A (the i index of D) and for B (the j index) alike — contiguous row reads, nothing transposed.
-//   workgroup   128 x 128 of G, 4 waves of 64 x 64 (2 x 2 accumulators of 32 x 32), rows staged 32 at a time: global -> registers
-//               (the next stage's loads fly under this stage's MFMAs) -> LDS [32][132] per operand -> one ds_read_b32 per operand
-//               tile and k-step.  ds_read_b32 banks by 32-lane halves, each half reads 32 consecutive floats: conflict-free; the
-//               pitch of 132 floats (not 128) keeps the two halves, a whole row apart, off one another's banks as well.
-//   rows        slot y of the grid owns rows [y R, (y + 1) R), R a multiple of 512 and the slot count at most 64, both from the shape
-//               alone (tn_plan).  Rows at and beyond the slot's end are zero-filled in the staging and never read.
-//   sums        the MFMA is bit for bit a k-ordered fmaf chain.  After kChain = 128 rows the fp32 accumulators are added into fp64
-//               carries (registers) and cleared: the fp32 chain never exceeds 128 terms whatever M, which is at or below the
-//               in-register chain of a blocked CPU sgemm (the yardstick of the tests' bar, K blocks of 256 and more) — and costs 64
-//               v_add_f64 per wave against 256 MFMAs.  Each slot's fp64 tile goes to the workspace; the finalize adds the slots in
-//               index order in fp64 and rounds once.
-constexpr int kTnBK = 32, kTnPitch = 132, kTnChainStages = 4, kTnSlotRows = 512, kTnSlotCap = 64, kTnGrid = 512;
-struct TnPlan { int slots; long rows; };
-// at most min(64, what brings the grid to 512 workgroups) slots: a problem with many tiles of G fills the chip without cutting M, and
-// every slot costs N1 x N2 doubles written and read once
-inline TnPlan tn_plan(long M, int N1, int N2) {
-  const long tiles = (long)(N1 / 128) * (N2 / 128);
-  const long cap = std::max<long>(1, std::min<long>(kTnSlotCap, (kTnGrid + tiles - 1) / tiles));
-  const long chunks = (M + kTnSlotRows - 1) / kTnSlotRows;
-  const long per = (chunks + cap - 1) / cap;
-  return TnPlan{(int)((chunks + per - 1) / per), per * kTnSlotRows};
+// G[n1][n2] = sum_m A[m][n1] B[m][n2]: the scheme of exact_gemm_device.hpp as it stands, both operands staged as they lie.  Slot y of
+// the grid owns rows [y R, (y + 1) R), R a multiple of 512 and the slot count at most min(64, what brings the grid to 512
+// workgroups), rounded up; each slot's fp64 tile goes to the workspace.
+constexpr int kTnSlotRows = 512, kTnSlotCap = 64, kTnGrid = 512;
+inline SlotPlan tn_plan(long M, int N1, int N2) {
+  return row_slot_plan(M, (long)(N1 / 128) * (N2 / 128), kTnSlotRows, kTnSlotCap, kTnGrid, true);
 }
 
 __global__ __launch_bounds__(kThreads) void gemm_tn_kernel(const float* __restrict__ A, const float* __restrict__ B,
                                                             double* __restrict__ part, int M, int N1, int N2, long rows_per_slot) {
-  __shared__ float sA[kTnBK * kTnPitch];
-  __shared__ float sB[kTnBK * kTnPitch];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave >> 1, wn = wave & 1;
+  __shared__ float sA[kBK * kPitch];
+  __shared__ float sB[kBK * kPitch];
   const int tiles2 = N2 / 128;
   const int n1_0 = ((int)blockIdx.x / tiles2) * 128, n2_0 = ((int)blockIdx.x % tiles2) * 128;
   const long r0 = (long)blockIdx.y * rows_per_slot, r1 = r0 + rows_per_slot < M ? r0 + rows_per_slot : M;
-  // staging: thread -> rows (tid >> 5) + 8 p, p < 4, columns 4 (tid & 31) .. + 3
-  const int srow = tid >> 5, scol = (tid & 31) * 4;
-  const float* ap = A + (size_t)n1_0 + scol;
-  const float* bp = B + (size_t)n2_0 + scol;
+  const float* ap = A + (size_t)n1_0 + stage_col();
+  const float* bp = B + (size_t)n2_0 + stage_col();
   f4 ra[4], rb[4];
   auto fetch = [&](long r) {
 #pragma unroll
     for (int p = 0; p < 4; ++p) {
-      const long m = r + srow + 8 * p;
+      const long m = r + stage_row() + 8 * p;
       const bool in = m < r1;
       ra[p] = in ? ld4v(ap + (size_t)m * N1) : f4{0.f, 0.f, 0.f, 0.f};
       rb[p] = in ? ld4v(bp + (size_t)m * N2) : f4{0.f, 0.f, 0.f, 0.f};
     }
   };
-  f32x16 acc[2][2];
-  double carry[2][2][16];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f, carry[i][j][e] = 0.0;
-  auto fold = [&]() {
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) carry[i][j][e] += (double)acc[i][j][e], acc[i][j][e] = 0.f;
-  };
-  const float* la = sA + (lane >> 5) * kTnPitch + wm * 64 + (lane & 31);
-  const float* lb = sB + (lane >> 5) * kTnPitch + wn * 64 + (lane & 31);
+  Tile t;
+  t.clear();
   if (r0 < r1) fetch(r0);
-  int stage = 0;
-  for (long r = r0; r < r1; r += kTnBK) {
-    __syncthreads();  // every wave has read the previous stage
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-      st4v(sA + (srow + 8 * p) * kTnPitch + scol, ra[p]);
-      st4v(sB + (srow + 8 * p) * kTnPitch + scol, rb[p]);
-    }
-    __syncthreads();
-    if (r + kTnBK < r1) fetch(r + kTnBK);
-#pragma unroll 4
-    for (int s = 0; s < kTnBK / 2; ++s) {
-      const float a0 = la[2 * s * kTnPitch], a1 = la[2 * s * kTnPitch + 32];
-      const float b0 = lb[2 * s * kTnPitch], b1 = lb[2 * s * kTnPitch + 32];
-      acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
-      acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
-      acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
-      acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
-    }
-    if (++stage == kTnChainStages) {
-      fold();
-      stage = 0;
-    }
-  }
-  fold();
-  // D: column = lane & 31 (n2), row = (e & 3) + 8 (e >> 2) + 4 (lane >> 5) (n1)
+  k_loop<kPitch, kPitch>(t, sA, sB, r0, r1, kBK, fetch, [&] { store_stage<false, false>(sA, sB, ra, rb); });
   double* out = part + (size_t)blockIdx.y * N1 * N2;
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const int n1 = n1_0 + wm * 64 + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5);
-        const int n2 = n2_0 + wn * 64 + j * 32 + (lane & 31);
-        out[(size_t)n1 * N2 + n2] = carry[i][j][e];
-      }
+  for_each_d(n1_0, n2_0, [=, &t](int i, int j, int e, int n1, int n2) { out[(size_t)n1 * N2 + n2] = t.carry[i][j][e]; });
 }
 
 // One workgroup per row c of G; thread t takes the columns t, t + 256, ...: the slots in index order in fp64, then
@@ -311,17 +216,16 @@ __global__ __launch_bounds__(kThreads) void gemm_tn_finalize_kernel(const double
 // Out[m][n] = epilogue(sum_k A[m][k] Bop[k][n]) for the DEEP forward-shaped products of the tail (fc2, dx; from K = 512 on), on the same
 // instruction with the same fp64 carries as gemm_tn: measured, gdrnpp_linear_f32_split's fp32 accumulation of six partial products
 // per k-tile is 1.4x the error of a CPU sgemm at K = 256 and 2.5 - 3.4x at K = 1024, beyond the factor 2 the tests' bar allows.
-//   A     [M,K] row-major: k is contiguous, so a stage [128 rows][32 k] is stored TRANSPOSED into the [k][row] image gemm_tn reads
-//         (float4 global loads, 8 lanes per 128-byte row segment; four ds_write_b32 each, image pitch 133: 2-way conflicts at worst);
-//         rows at and beyond M are zero-filled, never read, and their results not stored.
-//   B     B_NK: the weight as nn.Linear holds it, [N,K], staged transposed the same way;  else [K,N] row-major, gemm_tn's natural
-//         staging, times row_scale[k] (optional; one fp32 product, as pack_weight_t_kernel does).
+//   A     [M,K] row-major: k is contiguous, so a stage [128 rows][32 k] is stored transposed (exact_gemm_device.hpp); rows at and
+//         beyond M are zero-filled, never read, and their results not stored.
+//   B     B_NK: the weight as nn.Linear holds it, [N,K], staged transposed the same way;  else [K,N] row-major, staged as it lies,
+//         times row_scale[k] (optional; one fp32 product, as pack_weight_t_kernel does).
 //   sums  fp32 chains of 128, fp64 carries, then in fp64  v = sum + bias[n];  out = fl(v)  or, with gamma,  out = fl(resid[m][n] +
 //         gamma[n] v) — one rounding.  With one depth slot the workgroup does that itself and there is no workspace.
 //   depth a launch with fewer than 256 output tiles (small batches in the deep stages) cuts K into slots of a multiple of 128 until the
 //         grid reaches 256 workgroups (rows_plan: from the shape alone); slot y writes its fp64 tile to part[y][M][N] and
 //         gemm_rows_finalize_kernel adds the slots in index order and applies the epilogue.
-constexpr int kRowsPitchT = 133, kRowsGrid = 256;
+constexpr int kRowsGrid = 256;
 struct RowsPlan { int slots, depth; };
 inline RowsPlan rows_plan(int M, int N, int K) {
   const long tiles = (long)((M + 127) / 128) * (N / 128);
@@ -353,100 +257,41 @@ __global__ __launch_bounds__(kThreads) void gemm_rows_kernel(const float* __rest
                                                               const float* __restrict__ gamma, const float* __restrict__ resid,
                                                               float* __restrict__ out, double* __restrict__ part, int M, int N, int K,
                                                               int slot_depth) {
-  constexpr int PB = B_NK ? kRowsPitchT : kTnPitch;
-  __shared__ float sA[kTnBK * kRowsPitchT];
-  __shared__ float sB[kTnBK * PB];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave >> 1, wn = wave & 1;
+  constexpr int PB = B_NK ? kPitchT : kPitch;
+  __shared__ float sA[kBK * kPitchT];
+  __shared__ float sB[kBK * PB];
   const int tiles_n = N / 128;
   const int m0 = ((int)blockIdx.x / tiles_n) * 128, n0 = ((int)blockIdx.x % tiles_n) * 128;
-  // transposed staging: thread -> rows (tid >> 3) + 32 p, p < 4, k 4 (tid & 7) .. + 3;  natural: rows (tid >> 5) + 8 p, columns 4 (tid & 31) .. + 3
-  const int trow = tid >> 3, tk = (tid & 7) * 4, srow = tid >> 5, scol = (tid & 31) * 4;
   f4 ra[4], rb[4];
   auto fetch = [&](int k) {
 #pragma unroll
     for (int p = 0; p < 4; ++p) {
-      const int m = m0 + trow + 32 * p;
-      ra[p] = m < M ? ld4v(A + (size_t)m * K + k + tk) : f4{0.f, 0.f, 0.f, 0.f};
+      const int m = m0 + stage_row_t() + 32 * p;
+      ra[p] = m < M ? ld4v(A + (size_t)m * K + k + stage_k_t()) : f4{0.f, 0.f, 0.f, 0.f};
       if (B_NK) {
-        rb[p] = ld4v(B + (size_t)(n0 + trow + 32 * p) * K + k + tk);
+        rb[p] = ld4v(B + (size_t)(n0 + stage_row_t() + 32 * p) * K + k + stage_k_t());
       } else {
-        const int kk = k + srow + 8 * p;
-        rb[p] = ld4v(B + (size_t)kk * N + n0 + scol);
+        const int kk = k + stage_row() + 8 * p;
+        rb[p] = ld4v(B + (size_t)kk * N + n0 + stage_col());
         if (row_scale) rb[p] = rb[p] * row_scale[kk];
       }
     }
   };
-  f32x16 acc[2][2];
-  double carry[2][2][16];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f, carry[i][j][e] = 0.0;
-  auto fold = [&]() {
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) carry[i][j][e] += (double)acc[i][j][e], acc[i][j][e] = 0.f;
-  };
-  const float* la = sA + (lane >> 5) * kRowsPitchT + wm * 64 + (lane & 31);
-  const float* lb = sB + (lane >> 5) * PB + wn * 64 + (lane & 31);
+  Tile t;
+  t.clear();
   const int k0 = (int)blockIdx.y * slot_depth, k1 = k0 + slot_depth < K ? k0 + slot_depth : K;  // k0 < K: rows_plan leaves no empty slot
   fetch(k0);
-  int stage = 0;
-  for (int k = k0; k < k1; k += kTnBK) {
-    __syncthreads();  // every wave has read the previous stage
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) sA[(tk + j) * kRowsPitchT + trow + 32 * p] = ra[p][j];
-      if (B_NK) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) sB[(tk + j) * PB + trow + 32 * p] = rb[p][j];
-      } else {
-        st4v(sB + (srow + 8 * p) * PB + scol, rb[p]);
-      }
-    }
-    __syncthreads();
-    if (k + kTnBK < k1) fetch(k + kTnBK);
-#pragma unroll 4
-    for (int s = 0; s < kTnBK / 2; ++s) {
-      const float a0 = la[2 * s * kRowsPitchT], a1 = la[2 * s * kRowsPitchT + 32];
-      const float b0 = lb[2 * s * PB], b1 = lb[2 * s * PB + 32];
-      acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
-      acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
-      acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
-      acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
-    }
-    if (++stage == kTnChainStages) {
-      fold();
-      stage = 0;
-    }
-  }
-  fold();
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int n = n0 + wn * 64 + j * 32 + (lane & 31);
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const int m = m0 + wm * 64 + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5);
-        if (m >= M) continue;
-        const size_t at = (size_t)m * N + n;
-        if (part)
-          part[(size_t)blockIdx.y * M * N + at] = carry[i][j][e];
-        else
-          out[at] = rows_epilogue(carry[i][j][e], at, n, bias, gamma, resid);
-      }
-    }
+  k_loop<kPitchT, PB>(t, sA, sB, k0, k1, kBK, fetch, [&] { store_stage<true, B_NK>(sA, sB, ra, rb); });
+  double* slot = part + (size_t)blockIdx.y * M * N;
+  for_each_d(m0, n0, [=, &t](int i, int j, int e, int m, int n) {
+    if (m >= M) return;
+    const size_t at = (size_t)m * N + n;
+    if (part)
+      slot[at] = t.carry[i][j][e];
+    else
+      out[at] = rows_epilogue(t.carry[i][j][e], at, n, bias, gamma, resid);
+  });
 }
-
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 }  // namespace
 
 extern "C" {
@@ -547,11 +392,11 @@ int gdrnpp_gemm_tn_f32(const float* A, const float* B, float* G, int M, int N1, 
   GDRNPP_REQUIRE(aligned16(A) && aligned16(B) && aligned16(workspace), GDRNPP_EINVAL, "gdrnpp_gemm_tn_f32: A, B and the workspace must be 16-byte aligned");
   const size_t need = gdrnpp_gemm_tn_f32_workspace_bytes(M, N1, N2);
   GDRNPP_REQUIRE(workspace_bytes >= need, GDRNPP_EINVAL, "gdrnpp_gemm_tn_f32: workspace of %zu bytes, %zu needed", workspace_bytes, need);
-  const TnPlan p = tn_plan(M, N1, N2);
+  const SlotPlan p = tn_plan(M, N1, N2);
   hipStream_t st = (hipStream_t)stream;
   double* part = (double*)workspace;
   hipLaunchKernelGGL(gemm_tn_kernel, dim3((unsigned)((N1 / 128) * (N2 / 128)), (unsigned)p.slots), dim3(kThreads), 0, st, A, B, part, M, N1, N2,
-                     p.rows);
+                     p.rows_per_slot);
   hipLaunchKernelGGL(gemm_tn_finalize_kernel, dim3((unsigned)N1), dim3(kThreads), 0, st, part, p.slots, N1, N2, row_scale, G, drow ? W : nullptr,
                      b, sg, drow);
   return gdrnpp::check_launch("gdrnpp_gemm_tn_f32");

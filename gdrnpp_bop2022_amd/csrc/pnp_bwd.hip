@@ -5,7 +5,7 @@
 //   dW[co][ci][ky][kx] = sum_{n,oy,ox} dz[n,oy,ox,co] x[n, 2oy+ky-1, 2ox+kx-1, ci]
 //   dx[n,y,x,ci]       = sum dz[n,oy,ox,co] W[co,ci,ky,kx] over the (oy, ky) with 2oy+ky-1 = y and the (ox, kx) with 2ox+kx-1 = x
 //
-//   wgrad     conv3x3_wgrad_kernel (conv_gn_bwd.hip) with the rows = the N OH OW OUTPUT pixels and the x operand read at the tap's
+//   wgrad     the scheme of exact_gemm_device.hpp with the rows = the N OH OW OUTPUT pixels and the x operand read at the tap's
 //             pixel of the input at its pitch; channels at and beyond Cin are staged as zero whatever the memory holds.  fp32 chains of
 //             128 rows, fp64 carries, slots added in index order, one rounding.  The stride-1 kernel is left as it is.
 //   dinput    by the parity of the input pixel: (even, even) is reached by one tap, (even, odd) and (odd, even) by two, (odd, odd) by
@@ -15,58 +15,47 @@
 //   flatten   f32[B,HW,C] <-> f32[B,C HW]: a tiled transpose per image, values copied.
 //   heads     dfeat = g_r W_r + g_t W_t, dW = g^T feat, db = colsum(g): fp64 sums over B in index order, one rounding.
 // No atomics and no scratch; every sum has a fixed order, so two calls give equal bits.
-#include "gemm_split.hpp"
+#include "exact_gemm_device.hpp"
 #include <algorithm>
 #include <cstdint>
 
 namespace {
 
-using gdrnpp::splitgemm::f32x16;
-using f4 = __attribute__((ext_vector_type(4))) float;
-__device__ __forceinline__ f4 ld4v(const float* p) { return *reinterpret_cast<const f4*>(p); }
-__device__ __forceinline__ void st4v(float* p, f4 v) { *reinterpret_cast<f4*>(p) = v; }
+using namespace gdrnpp::exactgemm;
+using gdrnpp::aligned16;
 
-constexpr int kThreads = 256;
-constexpr int kBK = 32, kPitch = 132, kPitchT = 133, kChainStages = 4, kSlotRows = 512, kSlotCap = 64, kTnGrid = 512;
+constexpr int kSlotRows = 512, kSlotCap = 64, kTnGrid = 512;
 
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 inline int pad128(int c) { return (c + 127) / 128 * 128; }
 
 // ---- wgrad ----------------------------------------------------------------------------------------------------------------------
-// conv_gn_bwd.hip's wgrad_plan with the padded channel count
-struct TnPlan { int slots; long rows; };
-inline TnPlan wgrad_plan(long M, int CinP, int Cout) {
-  const long tiles = 9l * (Cout / 128) * (CinP / 128);
-  const long cap = std::max<long>(1, std::min<long>(kSlotCap, kTnGrid / tiles));
-  const long chunks = (M + kSlotRows - 1) / kSlotRows;
-  const long per = (chunks + cap - 1) / cap;
-  return TnPlan{(int)((chunks + per - 1) / per), per * kSlotRows};
+// row_slot_plan (exact_gemm_device.hpp) with the nine taps of the padded channel count as tiles, rounded down as the stride-1 wgrad
+inline SlotPlan wgrad_plan(long M, int CinP, int Cout) {
+  return row_slot_plan(M, 9l * (Cout / 128) * (CinP / 128), kSlotRows, kSlotCap, kTnGrid, false);
 }
 
 // part[slot][tap][co][ci < CinP] (fp64) = sum over the slot's output pixels of dz[pix][co] x[2 pix + tap - 1][ci].  grid (co tile x ci
-// tile, slot, tap); workgroup, LDS images, operand map and sums are conv3x3_wgrad_kernel's.  A pixel whose tap lies outside the image
-// contributes nothing: both operands of that row are staged as zero.  A channel quad at or beyond the pitch is not read; elements at
-// or beyond Cin are replaced by zero.
+// tile, slot, tap); workgroup, LDS images, operand map and sums are exact_gemm_device.hpp's.  A pixel whose tap lies outside the
+// image contributes nothing: both operands of that row are staged as zero.  A channel quad at or beyond the pitch is not read;
+// elements at or beyond Cin are replaced by zero.
 __global__ __launch_bounds__(kThreads) void conv3x3s2_wgrad_kernel(const float* __restrict__ dz, const float* __restrict__ x, int ldx,
                                                                     double* __restrict__ part, int M, int H, int W, int Cin, int CinP,
                                                                     int Cout, long rows_per_slot) {
   __shared__ float sA[kBK * kPitch];
   __shared__ float sB[kBK * kPitch];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave >> 1, wn = wave & 1;
   const int tiles2 = CinP / 128;
   const int n1_0 = ((int)blockIdx.x / tiles2) * 128, n2_0 = ((int)blockIdx.x % tiles2) * 128;
   const int tap = blockIdx.z, ky = tap / 3, kx = tap % 3, OH = H >> 1, OW = W >> 1, OHW = OH * OW;
   const long r0 = (long)blockIdx.y * rows_per_slot, r1 = r0 + rows_per_slot < M ? r0 + rows_per_slot : M;
-  const int srow = tid >> 5, scol = (tid & 31) * 4;
-  const float* ap = dz + (size_t)n1_0 + scol;
-  const int ci0 = n2_0 + scol;
+  const float* ap = dz + (size_t)n1_0 + stage_col();
+  const int ci0 = n2_0 + stage_col();
   const bool b_in = ci0 < ldx && ci0 < Cin;      // ldx % 4 == 0: the float4 lies inside the row
   const float* bp = x + ci0;
   f4 ra[4], rb[4];
   auto fetch = [&](long r) {
 #pragma unroll
     for (int p = 0; p < 4; ++p) {
-      const long m = r + srow + 8 * p;
+      const long m = r + stage_row() + 8 * p;
       bool in = m < r1;
       long src = 0;
       if (in) {
@@ -82,62 +71,12 @@ __global__ __launch_bounds__(kThreads) void conv3x3s2_wgrad_kernel(const float* 
       rb[p] = b;
     }
   };
-  f32x16 acc[2][2];
-  double carry[2][2][16];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f, carry[i][j][e] = 0.0;
-  auto fold = [&]() {
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) carry[i][j][e] += (double)acc[i][j][e], acc[i][j][e] = 0.f;
-  };
-  const float* la = sA + (lane >> 5) * kPitch + wm * 64 + (lane & 31);
-  const float* lb = sB + (lane >> 5) * kPitch + wn * 64 + (lane & 31);
+  Tile t;
+  t.clear();
   if (r0 < r1) fetch(r0);
-  int stage = 0;
-  for (long r = r0; r < r1; r += kBK) {
-    __syncthreads();  // every wave has read the previous stage
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-      st4v(sA + (srow + 8 * p) * kPitch + scol, ra[p]);
-      st4v(sB + (srow + 8 * p) * kPitch + scol, rb[p]);
-    }
-    __syncthreads();
-    if (r + kBK < r1) fetch(r + kBK);
-#pragma unroll 4
-    for (int s = 0; s < kBK / 2; ++s) {
-      const float a0 = la[2 * s * kPitch], a1 = la[2 * s * kPitch + 32];
-      const float b0 = lb[2 * s * kPitch], b1 = lb[2 * s * kPitch + 32];
-      acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
-      acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
-      acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
-      acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
-    }
-    if (++stage == kChainStages) {
-      fold();
-      stage = 0;
-    }
-  }
-  fold();
-  // D: column = lane & 31 (ci), row = (e & 3) + 8 (e >> 2) + 4 (lane >> 5) (co)
+  k_loop<kPitch, kPitch>(t, sA, sB, r0, r1, kBK, fetch, [&] { store_stage<false, false>(sA, sB, ra, rb); });
   double* out = part + ((size_t)blockIdx.y * 9 + tap) * Cout * CinP;
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const int n1 = n1_0 + wm * 64 + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5);
-        const int n2 = n2_0 + wn * 64 + j * 32 + (lane & 31);
-        out[(size_t)n1 * CinP + n2] = carry[i][j][e];
-      }
+  for_each_d(n1_0, n2_0, [=, &t](int i, int j, int e, int co, int ci) { out[(size_t)co * CinP + ci] = t.carry[i][j][e]; });
 }
 
 // dW[co][ci][tap] = fl(the slots in index order), ci < Cin.  Thread i = (tap, co, ci < CinP), ci fastest.
@@ -159,7 +98,7 @@ __global__ __launch_bounds__(kThreads) void conv3x3s2_wgrad_finalize_kernel(cons
 // with the Cout channels ascending, in stages of 32:
 //   py = 0: ky = 1 reads dz row i;      py = 1: ky = 0 reads dz row i + 1 (none for the last input row: staged as zero, not read),
 //   then ky = 2 reads dz row i;         columns alike.
-//   dz      read as it lies, float4 along co, stored transposed into the [k][row] image (pitch 133) as grouped_dinput_kernel does.
+//   dz      read as it lies, float4 along co, stored transposed (exact_gemm_device.hpp).
 //   w       f32[9 Cout][ldw], row (ky 3 + kx) Cout + co, column ci: the k-rows of the B operand.  A float4 at or beyond ldw is not
 //           read; elements at or beyond Cin are replaced by zero.
 //   dx      columns [0, Cin) receive the sums, [Cin, lddx) zero; nothing beyond lddx is written.
@@ -168,19 +107,17 @@ __global__ __launch_bounds__(kThreads) void conv3x3s2_dinput_kernel(const float*
                                                                      int Cout, int tiles_n) {
   __shared__ float sA[kBK * kPitchT];
   __shared__ float sB[kBK * kPitch];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave >> 1, wn = wave & 1;
   const int py = (int)blockIdx.y >> 1, px = (int)blockIdx.y & 1;
   const int OH = H >> 1, OW = W >> 1, OHW = OH * OW;
   const long Mc = (long)N * OHW;
   const long m0 = (long)((int)blockIdx.x / tiles_n) * 128;
   const int n0 = ((int)blockIdx.x % tiles_n) * 128;
   const int ntx = 1 + px, ntaps = (1 + py) * ntx, per_tap = Cout / kBK, stages = ntaps * per_tap;
-  // staging A: thread -> rows (tid >> 3) + 32 q, k columns 4 (tid & 7) .. + 3
-  const int arow = tid >> 3, ac4 = tid & 7;
+  // the pixels of the thread's four A rows
   int a_n[4], a_i[4], a_j[4];
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
-    const long m = m0 + arow + 32 * q;
+    const long m = m0 + stage_row_t() + 32 * q;
     if (m < Mc) {
       const int pix = (int)(m % OHW);
       a_n[q] = (int)(m / OHW), a_i[q] = pix / OW, a_j[q] = pix % OW;
@@ -188,8 +125,7 @@ __global__ __launch_bounds__(kThreads) void conv3x3s2_dinput_kernel(const float*
       a_n[q] = -1, a_i[q] = 0, a_j[q] = 0;
     }
   }
-  // staging B: thread -> k-rows (tid >> 5) + 8 q, columns 4 (tid & 31) .. + 3
-  const int brow = tid >> 5, bcol = n0 + (tid & 31) * 4;
+  const int bcol = n0 + stage_col();
   const bool b_in = bcol < ldw && bcol < Cin;      // ldw % 4 == 0: the float4 lies inside the row
   f4 ra[4], rb[4];
   auto fetch = [&](int s) {
@@ -202,71 +138,30 @@ __global__ __launch_bounds__(kThreads) void conv3x3s2_dinput_kernel(const float*
     for (int q = 0; q < 4; ++q) {
       const int oy = a_i[q] + oyo, ox = a_j[q] + oxo;
       const bool in = a_n[q] >= 0 && oy < OH && ox < OW;
-      ra[q] = in ? ld4v(dz + (((size_t)a_n[q] * OH + oy) * OW + ox) * Cout + c0 + 4 * ac4) : f4{0.f, 0.f, 0.f, 0.f};
-      f4 b = b_in ? ld4v(wrow + (size_t)(brow + 8 * q) * ldw) : f4{0.f, 0.f, 0.f, 0.f};
+      ra[q] = in ? ld4v(dz + (((size_t)a_n[q] * OH + oy) * OW + ox) * Cout + c0 + stage_k_t()) : f4{0.f, 0.f, 0.f, 0.f};
+      f4 b = b_in ? ld4v(wrow + (size_t)(stage_row() + 8 * q) * ldw) : f4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int j = 0; j < 4; ++j) b[j] = bcol + j < Cin ? b[j] : 0.f;
       rb[q] = b;
     }
   };
-  f32x16 acc[2][2];
-  double carry[2][2][16];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f, carry[i][j][e] = 0.0;
-  auto fold = [&]() {
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) carry[i][j][e] += (double)acc[i][j][e], acc[i][j][e] = 0.f;
-  };
-  const float* la = sA + (lane >> 5) * kPitchT + wm * 64 + (lane & 31);
-  const float* lb = sB + (lane >> 5) * kPitch + wn * 64 + (lane & 31);
+  Tile t;
+  t.clear();
   fetch(0);
-  int chain = 0;
-  for (int s = 0; s < stages; ++s) {
-    __syncthreads();      // every wave has read the previous stage
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) sA[(4 * ac4 + j) * kPitchT + arow + 32 * q] = ra[q][j];
-      st4v(sB + (brow + 8 * q) * kPitch + (tid & 31) * 4, rb[q]);
-    }
-    __syncthreads();
-    if (s + 1 < stages) fetch(s + 1);
-#pragma unroll 4
-    for (int ks = 0; ks < kBK / 2; ++ks) {
-      const float a0 = la[2 * ks * kPitchT], a1 = la[2 * ks * kPitchT + 32];
-      const float b0 = lb[2 * ks * kPitch], b1 = lb[2 * ks * kPitch + 32];
-      acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
-      acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
-      acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
-      acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
-    }
-    if (++chain == kChainStages) {
-      fold();
-      chain = 0;
-    }
-  }
-  fold();
-  // D: column = lane & 31 (ci), row = (e & 3) + 8 (e >> 2) + 4 (lane >> 5) (pixel of the class)
+  k_loop<kPitchT, kPitch>(t, sA, sB, 0, stages, 1, fetch, [&] { store_stage<true, false>(sA, sB, ra, rb); });
+  // a row of D is a pixel of the class: its address once, then both column tiles
 #pragma unroll
   for (int i = 0; i < 2; ++i)
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
-      const long m = m0 + wm * 64 + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5);
+      const long m = d_row(m0, i, e);
       if (m >= Mc) continue;
       const int n = (int)(m / OHW), pix = (int)(m % OHW);
       float* o = dx + (((size_t)n * H + 2 * (pix / OW) + py) * W + 2 * (pix % OW) + px) * lddx;
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
-        const int col = n0 + wn * 64 + j * 32 + (lane & 31);
-        if (col < lddx) o[col] = col < Cin ? (float)carry[i][j][e] : 0.f;
+        const int col = d_col(n0, j);
+        if (col < lddx) o[col] = col < Cin ? (float)t.carry[i][j][e] : 0.f;
       }
     }
 }
@@ -365,11 +260,11 @@ int gdrnpp_conv3x3s2_wgrad_f32(const float* dz, const float* x, int ldx, float* 
   const size_t need = gdrnpp_conv3x3s2_wgrad_f32_workspace_bytes(N, H, W, Cin, ldx, Cout);
   GDRNPP_REQUIRE(workspace_bytes >= need, GDRNPP_EINVAL, "%s: workspace of %zu bytes, %zu needed", what, workspace_bytes, need);
   const int M = N * (H / 2) * (W / 2), CinP = pad128(Cin);
-  const TnPlan p = wgrad_plan(M, CinP, Cout);
+  const SlotPlan p = wgrad_plan(M, CinP, Cout);
   hipStream_t st = (hipStream_t)stream;
   double* part = (double*)workspace;
   hipLaunchKernelGGL(conv3x3s2_wgrad_kernel, dim3((unsigned)((Cout / 128) * (CinP / 128)), (unsigned)p.slots, 9), dim3(kThreads), 0, st, dz, x, ldx,
-                     part, M, H, W, Cin, CinP, Cout, p.rows);
+                     part, M, H, W, Cin, CinP, Cout, p.rows_per_slot);
   const size_t n = (size_t)9 * CinP * Cout;
   hipLaunchKernelGGL(conv3x3s2_wgrad_finalize_kernel, dim3((unsigned)((n + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, part, p.slots, Cin,
                      CinP, Cout, dW);
