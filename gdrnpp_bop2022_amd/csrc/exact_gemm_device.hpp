@@ -1,7 +1,8 @@
 // Device code shared by the exact-f32 MFMA kernels of the backward pass (mlp_bwd.hip: gemm_tn, gemm_rows; conv_gn_bwd.hip:
-// conv3x3_wgrad; pnp_bwd.hip: conv3x3s2_wgrad, conv3x3s2_dinput; head_tail_bwd.hip: grouped_wgrad, grouped_dinput): the workgroup
-// scheme, its LDS images, the accumulators with their fp64 carries, the k-loop and the D map.  A kernel keeps what is its own: where
-// a stage's rows come from (its fetch), what a row slot or a depth slot is, and where the 128 x 128 tile goes (its store).
+// conv3x3_wgrad; pnp_bwd.hip: conv3x3s2_wgrad, conv3x3s2_dinput; head_tail_bwd.hip: grouped_wgrad, grouped_dinput; conv_bn_bwd.hip:
+// conv_wgrad, conv3x3s2_dinput_any): the workgroup scheme, its LDS images, the accumulators with their fp64 carries, the k-loop and
+// the D map.  A kernel keeps what is its own: where a stage's rows come from (its fetch), what a row slot or a depth slot is, and
+// where the 128 x 128 tile goes (its store).
 // DESIGN.md "exact_gemm_device.hpp" has the scheme and the measured resources.
 //
 // D[i][j] = sum_k A[k][i] B[k][j] on v_mfma_f32_32x32x2_f32, both operands as [k][128] images in LDS.  With the sum running over

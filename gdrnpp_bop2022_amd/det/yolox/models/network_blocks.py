@@ -1,11 +1,14 @@
-"""Building blocks of the YOLOX detector (Ge et al., "YOLOX: Exceeding YOLO Series in 2021"), inference only.
+"""Building blocks of the YOLOX detector (Ge et al., "YOLOX: Exceeding YOLO Series in 2021").
 
 Sub-module names follow the published implementation so its checkpoints load with ``strict=True``:
 ``BaseConv.{conv,bn,act}``, ``Bottleneck.{conv1,conv2}``, ``CSPLayer.{conv1,conv2,conv3,m}``, ``SPPBottleneck.{conv1,m,conv2}``,
 ``Focus.conv``.  The forwards below are the plain-PyTorch module path (CPU, fixtures, A/B baseline); the GPU forward of a
-whole ``YOLOX`` walks the same modules through ``hip_forward``."""
+whole ``YOLOX`` walks the same modules through ``hip_forward``.  In training mode a ``BaseConv`` asks ``train_layers.conv_bn_silu``
+first: with ``hip_layers.set_train_kernels(True)`` its three layers run, forward and backward, on csrc/conv_bn_bwd.hip."""
 import torch
 import torch.nn as nn
+
+from .train_layers import conv_bn_silu
 
 
 def _no_depthwise(depthwise: bool) -> None:
@@ -29,6 +32,10 @@ class BaseConv(nn.Module):
         self.act = _activation(act)
 
     def forward(self, x):
+        if self.training:      # the three layers as one autograd node on this library's kernels, where train_layers takes them
+            y = conv_bn_silu(self.conv, self.bn, x)
+            if y is not None:
+                return y
         return self.act(self.bn(self.conv(x)))
 
 

@@ -6,8 +6,11 @@ csrc/yolox_net.hip (``hip_forward``); everywhere else it is the plain-PyTorch mo
 
 ``forward(x, targets)`` on a train-mode model returns the reference's ``(out_dict, loss_dict)`` with ``loss_iou``, ``loss_conf``,
 ``loss_l1`` and ``loss_cls``; ``targets`` f32[B,G,5] = (class, cx, cy, w, h) in pixels of ``x``, zero rows behind an image's gts.  The
-SimOTA assignment and the losses run on csrc/yolox_loss.hip (``losses.yolox_losses``); the network layers under the loss
-(convolutions, BatchNorm with batch statistics) stay on PyTorch's graph in training mode."""
+SimOTA assignment and the losses run on csrc/yolox_loss.hip (``losses.yolox_losses``).  With ``hip_layers.set_train_kernels(True)`` every
+``BaseConv`` under the loss (convolution, BatchNorm with batch statistics, SiLU) runs forward and backward on csrc/conv_bn_bwd.hip
+(``train_layers.ConvBnSilu``): bit-reproducible, every sum in a fixed order.  The concatenations, the Bottleneck's ``y + x``, the SPP
+max pools, the nearest upsampling, ``space_to_depth`` and the head's bias-only prediction layers (widths 4, 1 and ``num_classes``)
+stay on PyTorch's operators, on channels_last tensors.  With the switch off, the default, the whole graph is PyTorch's."""
 import torch.nn as nn
 
 from ....gdrn_modeling import hip_layers

@@ -154,7 +154,8 @@ def _dwconv_hip_ok(conv: nn.Conv2d, x: torch.Tensor) -> bool:
 # upsample2x (Upsample2x), and the head's tail — the class-sliced 1x1 output layer, the class gather, the region softmax, the xyz
 # de-normalisation and the concatenation into Patch-PnP's input (HeadTail) — and Patch-PnP in its shipped ConvNeXt configuration on
 # the prepared input: the three [conv3x3 / stride 2, GroupNorm, GELU] layers (Conv3x3S2GnAct), the NCHW flatten (FlattenNCHW), fc1 and
-# fc2 with their GELU (LinearGelu) and the two pose heads (PnPHeads).  The ResNet path, AMP and
+# fc2 with their GELU (LinearGelu) and the two pose heads (PnPHeads).  The detector's BaseConv layers take the same switch in
+# det/yolox/models/train_layers.py (ConvBnSilu), which imports this module.  The ResNet path, AMP and
 # Patch-PnP outside that configuration (act "relu", another norm, mask attention, odd sizes, the module path ``forward``) keep
 # PyTorch's graph.
 _TRAIN_KERNELS = False

@@ -48,6 +48,8 @@ from .roi import (REPLACE_BG_COLUMNS, REPLACE_BG_CUTS, REPLACE_BG_MODES, ROI_BIN
                   replace_bg, replace_bg_table, roi_align, roi_pool, roi_table, roi_train_targets, rois_from_dets)
 from .yolox import (CONV_ACTS, conv_bias_act_f32, letterbox_sizes, pack_conv_weight_kmajor, spp_maxpool_5_9_13,  # noqa: F401
                     upsample_nearest2x_slice, yolox_focus, yolox_letterbox, yolox_postprocess)
+from .yolox import (bn_silu_apply, bn_silu_backward, bn_train_stats, conv3x3s2_dinput_any_f32, conv_backward, conv_train_f32,  # noqa: F401
+                    conv_wgrad_f32)
 from .yolox import YOLOX_CLS_LOSSES, YOLOX_IOU_LOSSES, YOLOX_LOSS_KEYS, yolox_assign, yolox_losses, yolox_losses_backward  # noqa: F401
 
 

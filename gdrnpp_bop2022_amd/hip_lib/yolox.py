@@ -1,10 +1,11 @@
 """The YOLOX detector: its forward on NHWC slice buffers (csrc/yolox_net.hip), its two ends, letterbox and
-post-processing (csrc/yolox_pre.hip), and its training: SimOTA assignment and losses (csrc/yolox_loss.hip)."""
+post-processing (csrc/yolox_pre.hip), and its training: SimOTA assignment and losses (csrc/yolox_loss.hip) and the forward and backward
+of a [convolution, BatchNorm with batch statistics, SiLU] layer (csrc/conv_bn_bwd.hip)."""
 from __future__ import annotations
 
 import torch
 
-from .abi import DEFINES, dev_ptr, f32_ptr, launch, load, opt_f32_ptr
+from .abi import DEFINES, channels_last_f32, dev_ptr, f32_ptr, launch, load, opt_f32_ptr
 
 
 def yolox_postprocess(det_preds, num_classes: int, conf_thre: float = 0.7, nms_thre: float = 0.45, class_agnostic: bool = False,
@@ -194,3 +195,151 @@ def yolox_losses_backward(raw, anchors, labels, matched_gt, out, scale, *, iou_l
     launch("gdrnpp_yolox_losses_backward", *ptrs, dev_ptr(matched_gt, torch.int32, "matched_gt"), dev_ptr(out, torch.float64, "out"),
            f32_ptr(scale, "scale"), b, a, c, g, *opts, grad.data_ptr())
     return grad
+
+
+# ---- training a BaseConv: convolution, BatchNorm2d with batch statistics, SiLU (csrc/conv_bn_bwd.hip) --------------------------------
+# All tensors channels_last [N,C,H,W], the NHWC rows the kernels read; the per-channel vectors are f32[C].
+
+def _rows(t_cl, what: str):
+    n, c, h, w = channels_last_f32(t_cl, what)
+    if t_cl.dim() != 4 or c % 4:
+        raise RuntimeError(f"{what}: a 4-D tensor with C % 4 == 0, got {tuple(t_cl.shape)}")
+    return n * h * w, c
+
+
+def _channel_ptrs(what: str, c: int, **vectors):
+    for name, v in vectors.items():
+        if v.numel() != c:
+            raise RuntimeError(f"{what}: {name} must hold {c} values, got {tuple(v.shape)}")
+    return [f32_ptr(v, name) for name, v in vectors.items()]
+
+
+def bn_train_stats(z_cl, eps: float, running_mean=None, running_var=None, momentum: float = 0.1):
+    """``gdrnpp_bn_train_stats_nhwc``: the batch statistics of z [N,C,H,W] -> (mean f32[C], invstd f32[C] = 1 / sqrt(biased var + eps)),
+    what PyTorch's batch_norm saves.  ``running_mean`` / ``running_var``, where given, are updated IN PLACE with ``momentum`` and the
+    unbiased variance.  N H W >= 2."""
+    what = "bn_train_stats"
+    m, c = _rows(z_cl, what)
+    nbytes = load().gdrnpp_bn_train_stats_workspace_bytes(m, c)      # 0: the entry point refuses the shape, in its words
+    ws = torch.empty((max(nbytes, 16) // 8,), dtype=torch.float64, device=z_cl.device)
+    mean = torch.empty((c,), dtype=torch.float32, device=z_cl.device)
+    invstd = torch.empty_like(mean)
+    launch("gdrnpp_bn_train_stats_nhwc", z_cl.data_ptr(), mean.data_ptr(), invstd.data_ptr(), opt_f32_ptr(running_mean, "running_mean"),
+           opt_f32_ptr(running_var, "running_var"), m, c, float(eps), float(momentum), ws.data_ptr(), nbytes,
+           timed=("hbm:bn_train_stats", 0.0, 4.0 * z_cl.numel()))
+    return mean, invstd
+
+
+def bn_silu_apply(z_cl, mean, invstd, gamma, beta):
+    """``gdrnpp_bn_silu_apply_nhwc``: y = silu(gamma (z - mean) invstd + beta), channels_last as z."""
+    what = "bn_silu_apply"
+    m, c = _rows(z_cl, what)
+    y = torch.empty_like(z_cl)      # preserves channels_last
+    launch("gdrnpp_bn_silu_apply_nhwc", z_cl.data_ptr(), *_channel_ptrs(what, c, mean=mean, invstd=invstd, gamma=gamma, beta=beta), y.data_ptr(),
+           m, c, timed=("hbm:bn_silu_apply", 0.0, 8.0 * z_cl.numel()))
+    return y
+
+
+def bn_silu_backward(grad_y_cl, z_cl, mean, invstd, gamma, beta, want=(True, True, True)):
+    """``gdrnpp_bn_silu_backward``: the gradients of y = silu(BatchNorm(z)) under batch statistics -> (dz, dgamma, dbeta).  ``want``:
+    three flags in that order — an entry is None where its flag is false and its launches are left out; the others keep their bits."""
+    what = "bn_silu_backward"
+    want = tuple(bool(f) for f in want)
+    if len(want) != 3 or not any(want):
+        raise RuntimeError(f"{what}: want must hold three flags, at least one of them set")
+    m, c = _rows(z_cl, what)
+    if tuple(grad_y_cl.shape) != tuple(z_cl.shape):
+        raise RuntimeError(f"{what}: grad_y {tuple(grad_y_cl.shape)} does not fit z {tuple(z_cl.shape)}")
+    channels_last_f32(grad_y_cl, what)
+    nbytes = load().gdrnpp_bn_silu_backward_workspace_bytes(m, c)
+    ws = torch.empty((max(nbytes, 16) // 8,), dtype=torch.float64, device=z_cl.device)
+    dz = torch.empty_like(z_cl) if want[0] else None
+    dgamma = torch.empty((c,), dtype=torch.float32, device=z_cl.device) if want[1] else None
+    dbeta = torch.empty((c,), dtype=torch.float32, device=z_cl.device) if want[2] else None
+    launch("gdrnpp_bn_silu_backward", grad_y_cl.data_ptr(), z_cl.data_ptr(), *_channel_ptrs(what, c, mean=mean, invstd=invstd, gamma=gamma, beta=beta),
+           *(None if t is None else t.data_ptr() for t in (dz, dgamma, dbeta)), m, c, ws.data_ptr(), nbytes,
+           timed=("hbm:bn_silu_backward", 0.0, 4.0 * z_cl.numel() * (2 + 3 * want[0])))
+    return dz, dgamma, dbeta
+
+
+def _conv_out(h: int, w: int, ks: int, stride: int):
+    pad = (ks - 1) // 2
+    return (h + 2 * pad - ks) // stride + 1, (w + 2 * pad - ks) // stride + 1
+
+
+def conv_train_f32(x_cl, weight, bias=None, stride: int = 1):
+    """The training forward's convolution: z = conv(x, weight) (+ bias), ks x ks / ``stride`` / pad (ks - 1) // 2, on
+    ``gdrnpp_conv_bias_act_f32`` -> channels_last [N,Cout,OH,OW].  The operand is made per call: the weight changes every step."""
+    n, cin, h, w = channels_last_f32(x_cl, "conv_train_f32")
+    cout, ks = weight.shape[0], weight.shape[2]
+    oh, ow = _conv_out(h, w, ks, stride)
+    z = torch.empty((n, cout, oh, ow), dtype=torch.float32, device=x_cl.device, memory_format=torch.channels_last)
+    conv_bias_act_f32(x_cl.permute(0, 2, 3, 1), 0, cin, pack_conv_weight_kmajor(weight), bias, z.permute(0, 2, 3, 1), 0, cout, ks, stride)
+    return z
+
+
+def conv_wgrad_f32(dz_cl, x_cl, ks: int, stride: int):
+    """dW f32[Cout,Cin,ks,ks] of a ks x ks / ``stride`` / pad (ks - 1) // 2 convolution for dz [N,Cout,OH,OW] and its input x
+    [N,Cin,H,W], both channels_last (``gdrnpp_conv_wgrad_f32``: implicit TN GEMM on the exact-f32 matrix instruction, fixed slots, fp64
+    finalize, one rounding).  ks in {1, 3}, stride in {1, 2}, any Cin % 4 == 0 and Cout % 4 == 0."""
+    what = "conv_wgrad_f32"
+    n, cout, oh, ow = channels_last_f32(dz_cl, what)
+    xn, cin, h, w = channels_last_f32(x_cl, what)
+    if ks not in (1, 3) or stride not in (1, 2) or (xn, *_conv_out(h, w, ks, stride)) != (n, oh, ow):
+        raise RuntimeError(f"{what}: dz {tuple(dz_cl.shape)} does not fit x {tuple(x_cl.shape)} at ks={ks}, stride={stride}")
+    nbytes = load().gdrnpp_conv_wgrad_f32_workspace_bytes(n, h, w, cin, cout, ks, stride)      # 0: the entry point refuses the shape, in its words
+    ws = torch.empty((max(nbytes, 16) // 8,), dtype=torch.float64, device=x_cl.device)
+    dw = torch.empty((cout, cin, ks, ks), dtype=torch.float32, device=x_cl.device)
+    launch("gdrnpp_conv_wgrad_f32", dz_cl.data_ptr(), x_cl.data_ptr(), dw.data_ptr(), n, h, w, cin, cout, ks, stride, ws.data_ptr(), nbytes,
+           timed=("mfma_f32:conv_wgrad", 2.0 * n * oh * ow * cout * ks * ks * cin, 4.0 * n * (h * w * cin + oh * ow * cout) + 4.0 * ks * ks * cin * cout))
+    return dw
+
+
+def conv3x3s2_dinput_any_f32(dz_cl, w_op, cin: int):
+    """dx [N,cin,2 OH,2 OW] channels_last of a 3x3 / stride 2 / pad 1 convolution for dz [N,Cout,OH,OW] channels_last and ``w_op``
+    f32[9 Cout, cin], row (ky 3 + kx) Cout + co (``gdrnpp_conv3x3s2_dinput_any_f32``, by parity class; any cin % 4 == 0, Cout % 4 == 0)."""
+    what = "conv3x3s2_dinput_any_f32"
+    n, cout, oh, ow = channels_last_f32(dz_cl, what)
+    if tuple(w_op.shape) != (9 * cout, cin):
+        raise RuntimeError(f"{what}: w_op must be f32[{9 * cout}, {cin}], got {tuple(w_op.shape)}")
+    dx = torch.empty((n, cin, 2 * oh, 2 * ow), dtype=torch.float32, device=dz_cl.device, memory_format=torch.channels_last)
+    launch("gdrnpp_conv3x3s2_dinput_any_f32", dz_cl.data_ptr(), f32_ptr(w_op, "w_op"), dx.data_ptr(), n, 2 * oh, 2 * ow, cin, cout,
+           timed=("mfma_f32:conv3x3s2_dinput_any", 2.0 * n * oh * ow * cout * 9 * cin, 4.0 * n * oh * ow * (4 * cin + cout) + 36.0 * cin * cout))
+    return dx
+
+
+def _dinput_weight(weight, stride: int):
+    """nn.Conv2d weight [Cout,Cin,ks,ks] -> the data gradient's operand, rows (ky, kx, co), columns ci.  Stride 1: flipped, for the
+    forward-shaped convolution of dz.  Stride 2: as it lies, for the parity kernel — a 1x1 weight as the centre tap of a 3x3 one,
+    whose other eight taps multiply zeros and whose three other parity classes so come out zero, as they are."""
+    cout, cin, ks, _ = weight.shape
+    w = weight.detach()
+    if stride == 1:
+        return w.flip(2, 3).permute(2, 3, 0, 1).reshape(ks * ks * cout, cin).contiguous()
+    if ks == 1:
+        out = torch.zeros((3, 3, cout, cin), dtype=torch.float32, device=weight.device)
+        out[1, 1] = w[:, :, 0, 0]
+        return out.view(9 * cout, cin)
+    return w.permute(2, 3, 0, 1).reshape(9 * cout, cin).contiguous()
+
+
+def conv_backward(x_cl, weight, stride: int, dz_cl, want=(True, True)):
+    """Gradients of z = conv(x, weight), ks x ks / ``stride`` / pad (ks - 1) // 2, for dz = dL/dz -> (dx, dweight).  ``want``: two flags
+    in that order — an entry is None where its flag is false and its launches are left out; the other keeps its bits.  dx at stride 1
+    is the forward-shaped convolution of dz with the flipped, transposed weight (``gdrnpp_conv_bias_act_f32``), at stride 2
+    ``conv3x3s2_dinput_any_f32``; dweight is ``conv_wgrad_f32``.  The operands are formed here, per call."""
+    want = tuple(bool(f) for f in want)
+    if len(want) != 2 or not any(want):
+        raise RuntimeError("conv_backward: want must hold two flags, at least one of them set")
+    cout, cin, ks, _ = weight.shape
+    dx = None
+    if want[0]:
+        w_op = _dinput_weight(weight, stride)
+        if stride == 1:
+            n, _, h, w = channels_last_f32(dz_cl, "conv_backward")
+            dx = torch.empty((n, cin, h, w), dtype=torch.float32, device=dz_cl.device, memory_format=torch.channels_last)
+            conv_bias_act_f32(dz_cl.permute(0, 2, 3, 1), 0, cout, w_op, None, dx.permute(0, 2, 3, 1), 0, cin, ks, 1)
+        else:
+            dx = conv3x3s2_dinput_any_f32(dz_cl, w_op, cin)
+    dw = conv_wgrad_f32(dz_cl, x_cl, ks, stride) if want[1] else None
+    return dx, dw

@@ -1193,6 +1193,43 @@ int gdrnpp_yolox_losses_backward(const float* raw, const float* anchors, const f
                                  const float* scale, int B, int A, int C, int G, int iou_type, int cls_type, float fl_alpha, float fl_gamma,
                                  int use_l1, float* grad_raw, void* stream);
 
+/* ---- training YOLOX's BaseConv: convolution, BatchNorm2d with batch statistics, SiLU (csrc/conv_bn_bwd.hip) ----
+ * The rules of the training sections above hold: NHWC fp32, no atomics, every sum over pixels through workspace slots whose count
+ * depends on the shape alone, added in slot order in fp64 and rounded once (two calls give equal bits), a NULL output is not computed
+ * and its launches are left out, argument errors return GDRNPP_EINVAL / GDRNPP_ELIMIT with gdrnpp_last_error text and launch
+ * nothing, a workspace query returns 0 for a shape outside its kernel.  The forward convolution (act = none, no bias) and the
+ * stride-1 data gradient (the flipped, transposed weight) are gdrnpp_conv_bias_act_f32; a convolution bias gradient is
+ * gdrnpp_colsum_f32.  M = N OH OW is the number of pixels, C % 4 == 0, C <= 4096.
+ *  bn_train_stats_nhwc : mean f32[C] and invstd f32[C] = 1 / sqrt(var + eps) of z f32[M, C] per channel, M >= 2 (M = 1 is an argument
+ *                 error, as in PyTorch); the mean and the biased variance are summed in fp64.  running_mean / running_var (each
+ *                 may be NULL) are updated in place: r = (1 - momentum) r + momentum (mean | var M / (M - 1)).
+ *  bn_silu_apply_nhwc : y = silu(a), a = gamma (z - mean) invstd + beta, a evaluated in fp64 and rounded once.
+ *  bn_silu_backward : for grad_y = dL/dy: dA = grad_y silu'(a), silu'(a) = s (1 + a (1 - s)), s = sigmoid(a), with a rebuilt from z by
+ *                 the apply kernel's own expression (the forward's bits; neither y nor a is kept); dbeta = sum dA, dgamma = sum dA
+ *                 xhat, dz = gamma invstd (dA - dbeta / M - xhat dgamma / M).  dz, dgamma, dbeta may each be NULL, not all.
+ *  conv_wgrad_f32 : dW[co][ci][ky][kx] = sum_{n,oy,ox} dz[n,oy,ox,co] x[n, stride oy + ky - pad, stride ox + kx - pad, ci] (zero
+ *                 outside the image), dW f32[Cout,Cin,ks,ks] contiguous, dz f32[N,OH,OW,Cout], x f32[N,H,W,Cin]; ks in {1, 3},
+ *                 stride in {1, 2}, pad = (ks - 1) / 2, H and W even at stride 2, ANY Cin % 4 == 0 and Cout % 4 == 0.  The sums of
+ *                 gdrnpp_conv3x3_wgrad_f32 with the N OH OW output pixels as rows; both channel counts are padded to 128 with zeros
+ *                 inside the kernel and only the real elements are stored: workspace slots x ks ks x Cin x Cout doubles, 512-row
+ *                 chunks dealt to at most min(64, 512 / (ks ks ceil(Cin / 128) ceil(Cout / 128))) slots.
+ *  conv3x3s2_dinput_any_f32 : gdrnpp_conv3x3s2_dinput_f32 for any Cin % 4 == 0, Cout % 4 == 0 and a contiguous dx f32[N,H,W,Cin];
+ *                 w f32[9 Cout, Cin], row (ky 3 + kx) Cout + co.  The depth in (ky, kx, co) order, a tap's channels padded to a
+ *                 multiple of 32 with zeros, in fp32 chains of 128 carried in fp64, one rounding; the order does not depend on N. */
+size_t gdrnpp_bn_train_stats_workspace_bytes(long M, int C);
+int gdrnpp_bn_train_stats_nhwc(const float* z, float* mean, float* invstd, float* running_mean, float* running_var, long M, int C,
+                               double eps, double momentum, void* workspace, size_t workspace_bytes, void* stream);
+int gdrnpp_bn_silu_apply_nhwc(const float* z, const float* mean, const float* invstd, const float* gamma, const float* beta, float* y,
+                              long M, int C, void* stream);
+size_t gdrnpp_bn_silu_backward_workspace_bytes(long M, int C);
+int gdrnpp_bn_silu_backward(const float* grad_y, const float* z, const float* mean, const float* invstd, const float* gamma,
+                            const float* beta, float* dz, float* dgamma, float* dbeta, long M, int C, void* workspace,
+                            size_t workspace_bytes, void* stream);
+size_t gdrnpp_conv_wgrad_f32_workspace_bytes(int N, int H, int W, int Cin, int Cout, int ks, int stride);
+int gdrnpp_conv_wgrad_f32(const float* dz, const float* x, float* dW, int N, int H, int W, int Cin, int Cout, int ks, int stride,
+                          void* workspace, size_t workspace_bytes, void* stream);
+int gdrnpp_conv3x3s2_dinput_any_f32(const float* dz, const float* w, float* dx, int N, int H, int W, int Cin, int Cout, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
