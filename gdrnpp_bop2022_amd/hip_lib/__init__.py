@@ -51,6 +51,8 @@ from .yolox import (CONV_ACTS, conv_bias_act_f32, letterbox_sizes, pack_conv_wei
 from .yolox import (bn_silu_apply, bn_silu_backward, bn_train_stats, conv3x3s2_dinput_any_f32, conv_backward, conv_train_f32,  # noqa: F401
                     conv_wgrad_f32)
 from .yolox import YOLOX_CLS_LOSSES, YOLOX_IOU_LOSSES, YOLOX_LOSS_KEYS, yolox_assign, yolox_losses, yolox_losses_backward  # noqa: F401
+from .yolox import (YOLOX_AUG_BRANCHES, YOLOX_AUG_COLUMNS, YOLOX_AUG_FLAGS, YOLOX_AUG_MODES, YOLOX_AUG_SOURCE_COLUMNS, yolox_aug_table,  # noqa: F401
+                    yolox_train_inputs)
 
 
 def __getattr__(name):

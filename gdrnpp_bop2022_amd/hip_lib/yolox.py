@@ -1,6 +1,7 @@
 """The YOLOX detector: its forward on NHWC slice buffers (csrc/yolox_net.hip), its two ends, letterbox and
 post-processing (csrc/yolox_pre.hip), and its training: SimOTA assignment and losses (csrc/yolox_loss.hip) and the forward and backward
-of a [convolution, BatchNorm with batch statistics, SiLU] layer (csrc/conv_bn_bwd.hip)."""
+of a [convolution, BatchNorm with batch statistics, SiLU] layer (csrc/conv_bn_bwd.hip), and its training batches: mosaic, affine, mixup,
+HSV, mirror and preproc for a batch in one call (csrc/yolox_aug.hip)."""
 from __future__ import annotations
 
 import torch
@@ -343,3 +344,69 @@ def conv_backward(x_cl, weight, stride: int, dz_cl, want=(True, True)):
             dx = conv3x3s2_dinput_any_f32(dz_cl, w_op, cin)
     dw = conv_wgrad_f32(dz_cl, x_cl, ks, stride) if want[1] else None
     return dx, dw
+
+
+# ---- training batches: mosaic, affine, mixup, HSV, mirror, preproc for a batch in one call (csrc/yolox_aug.hip) ------------------------
+# the columns of yolox_train_inputs' host table (include/gdrnpp_hip.h); the matrix and the scales hold the bits of an fp64
+YOLOX_AUG_SOURCE_COLUMNS = ("off", "w", "h", "dw", "dh", "mode", "scale_x", "scale_y", "l_x", "l_y", "s_x", "s_y", "pw", "ph")
+YOLOX_AUG_SOURCES = 5                                                         # four mosaic tiles (plain: the first), then the mixup image
+YOLOX_AUG_COLUMNS = (("branch", "flags", "m00", "m01", "m02", "m10", "m11", "m12", "mix_w", "mix_h", "mix_mode", "mix_scale_x", "mix_scale_y",
+                      "mix_x_off", "mix_y_off") + tuple(f"s{k}_{c}" for k in range(YOLOX_AUG_SOURCES) for c in YOLOX_AUG_SOURCE_COLUMNS))
+YOLOX_AUG_F64 = frozenset(("m00", "m01", "m02", "m10", "m11", "m12", "mix_scale_x", "mix_scale_y")
+                          + tuple(f"s{k}_scale_{a}" for k in range(YOLOX_AUG_SOURCES) for a in "xy"))
+YOLOX_AUG_BRANCHES = ("plain", "mosaic", "mixup")                             # branch = index
+YOLOX_AUG_MODES = ("copy", "area", "linear")                                  # cv2.resize's forms: mode = index
+YOLOX_AUG_FLAGS = {"hsv1": 1, "hsv1_rgb": 2, "mirror": 4, "fallback": 8, "hsv2": 16, "hsv2_rgb": 32, "mix_flip": 64}
+assert len(YOLOX_AUG_COLUMNS) == 85      # i64[B,85] in include/gdrnpp_hip.h
+
+
+def yolox_aug_table(rows):
+    """[{column: value}] -> the i64[B,85] host table of ``yolox_train_inputs``; a column left out is 0, the fp64 columns are stored as their
+    bits."""
+    import numpy as np
+
+    table = np.zeros((len(rows), len(YOLOX_AUG_COLUMNS)), np.int64)
+    index = {name: k for k, name in enumerate(YOLOX_AUG_COLUMNS)}
+    for b, row in enumerate(rows):
+        unknown = set(row) - set(index)
+        if unknown:
+            raise RuntimeError(f"yolox_aug_table: unknown columns {sorted(unknown)}; the columns are {YOLOX_AUG_COLUMNS}")
+        for name, value in row.items():
+            table[b, index[name]] = np.float64(value).view(np.int64) if name in YOLOX_AUG_F64 else int(value)
+    return table
+
+
+def yolox_train_inputs(src, table, lut, H: int, W: int, *, out=None):
+    """``gdrnpp_yolox_train_inputs``: the pixel work of ``MosaicDetection.__getitem__`` over ``TrainTransform`` for B items in one call.
+
+    src: a flat u8 device tensor of decoded source images, HWC, rows dense.  table: host i64[B,85] with the columns ``YOLOX_AUG_COLUMNS``
+    (``yolox_aug_table``): per item the branch (``YOLOX_AUG_BRANCHES``), the flags (``YOLOX_AUG_FLAGS``), the affine matrix, the mixup's
+    second resize and crop, and per source where it lies in ``src``, the size, form and scales of its cv2.resize and its paste.  lut:
+    u8[B,2,3,256] on the device, the hue / saturation / value LUTs of the two HSV passes.  The library checks every value the kernels
+    index with before it uploads the table in one copy; a bad row raises RuntimeError.
+    -> (out f32[B,3,H,W] holding integers 0..255, flags i32[B]: 1 where the affine matrix was singular).  Nothing is read back."""
+    import numpy as np
+
+    what = "yolox_train_inputs"
+    dev_ptr(src, torch.uint8, "src")
+    table = np.ascontiguousarray(table.cpu().numpy() if isinstance(table, torch.Tensor) else table)
+    if table.ndim != 2 or table.shape[1] != len(YOLOX_AUG_COLUMNS) or table.dtype != np.int64:
+        raise RuntimeError(f"{what}: table must be a host i64[B,{len(YOLOX_AUG_COLUMNS)}], got {table.shape} of {table.dtype}")
+    B, H, W = table.shape[0], int(H), int(W)
+    dev_ptr(lut, torch.uint8, "lut")
+    if tuple(lut.shape) != (B, 2, 3, 256):
+        raise RuntimeError(f"{what}: lut must be u8[{B},2,3,256], got {tuple(lut.shape)}")
+    dev = src.device
+    if out is None:
+        out = torch.empty((B, 3, H, W), dtype=torch.float32, device=dev)
+    f32_ptr(out, "out")
+    if tuple(out.shape) != (B, 3, H, W):
+        raise RuntimeError(f"{what}: out must be f32[{B},3,{H},{W}], got {tuple(out.shape)}")
+    flags = torch.zeros((B,), dtype=torch.int32, device=dev)
+    if B == 0:
+        return out, flags
+    nbytes = load().gdrnpp_yolox_train_inputs_workspace_bytes(B, H, W)      # 0: the entry point refuses the shape, in its words
+    ws = torch.empty((max(nbytes, 16) // 4,), dtype=torch.int32, device=dev)
+    launch("gdrnpp_yolox_train_inputs", src.data_ptr(), src.numel(), table.ctypes.data, lut.data_ptr(), B, H, W, out.data_ptr(), flags.data_ptr(),
+           ws.data_ptr(), nbytes, timed=("hbm:yolox_train_inputs", 0.0, 32.0 * B * H * W))
+    return out, flags

@@ -506,6 +506,39 @@ int gdrnpp_replace_bg(unsigned char* images, const unsigned char* masks, unsigne
                       const unsigned char* bg, long long bg_bytes, const long long* table, int* flags, void* workspace,
                       size_t workspace_bytes, void* stream);
 
+/* ---- YOLOX training batches (csrc/yolox_aug.hip) — the pixel work of `MosaicDetection.__getitem__`
+ * (det/yolox/data/datasets/mosaicdetection.py) over `TrainTransform` (det/yolox/data/data_augment.py) for B items in one call: mosaic,
+ * cv2.warpAffine, mixup, augment_hsv, mirror, preproc.  Device pointers: src, src_bytes bytes holding the decoded source images, u8 HWC,
+ * 3 bytes per pixel, rows dense; lut u8[B,2,3,256], the (hue, saturation, value) LUTs of HSV pass 1 and pass 2; out f32[B,3,H,W], integer
+ * values 0..255; flags i32[B].
+ *   table is a HOST array i64[B,85], one row per item, with the columns (hip_lib.YOLOX_AUG_COLUMNS)
+ *     0  branch    0 plain (source 0 through TrainTransform), 1 mosaic, 2 mosaic + mixup
+ *     1  flags     1 HSV pass 1, 2 pass 1 reads RGB (else BGR), 4 mirror, 8 fallback (TrainTransform kept no box and re-ran
+ *                  preproc(image_o): pass 1 and the mirror are dropped), 16 HSV pass 2, 32 pass 2 reads RGB, 64 mixup flip
+ *     2..7  m00 m01 m02 m10 m11 m12   the bits of six fp64: the affine matrix handed to cv2.warpAffine (branches 1, 2)
+ *     8  mix_w     9  mix_h      size of the second, jittered resize of the H x W cp canvas (branch 2)
+ *    10  mix_mode  11 mix_scale_x  12 mix_scale_y   its form and scales, as for a source
+ *    13  mix_x_off 14 mix_y_off  origin of the H x W crop of the zero-padded, jittered image
+ *    15 + 14 k ..  source k = 0..3: the mosaic tiles in paste order (branch 0 reads source 0 only); k = 4: the mixup image
+ *      +0 off      byte offset of the image in src        +1 w   +2 h   its size
+ *      +3 dw  +4 dh   size it is resized to      +5 mode   0 copy, 1 the 2:1 area mean, 2 linear: OpenCV's forms of an 8-bit cv2.resize
+ *      +6 scale_x  +7 scale_y   the bits of an fp64: OpenCV's interpolation scale 1 / (dst / src) (mode 2 only)
+ *      +8 l_x  +9 l_y   where the paste lands on its canvas      +10 s_x  +11 s_y   where it starts in the resized image
+ *      +12 pw  +13 ph   size of the pasted rectangle (0: nothing is pasted)
+ * The host does all size arithmetic and the affine matrix in the reference's Python floats; the kernels derive none.  Every value the
+ * kernels index with is checked here before the table is staged into the workspace in one copy: an image outside src, a paste outside
+ * its canvas (2W x 2H for the tiles, W x H for source 4 and the plain branch, whose paste is whole and top-left), sizes that do not fit
+ * their form, an offset outside the padded image, a matrix whose inverse leaves the fixed-point range return GDRNPP_EINVAL naming the
+ * row, and nothing is launched.  H, W <= 16383 and B <= 65535, or GDRNPP_ELIMIT.  B = 0 succeeds and launches nothing.
+ *   The matrix is inverted here as cv::warpAffine does; the tap coordinates are those of gdrnpp_crop_resize's warp (10-bit fixed point,
+ * 5 fractional bits), the 8-bit bilinear weights are integers of 15 bits, and a tap outside the canvas reads 114.  Mixup blends
+ * uint8(0.5f a + 0.5f b).  An HSV pass is 8-bit RGB -> HSV in integers (hue range 180), the three LUTs, and HSV -> RGB in fp32 with every
+ * operation rounded on its own.  flags[b] = 1 where the matrix was singular (OpenCV then warps with a zero map), else 0.
+ * workspace: gdrnpp_yolox_train_inputs_workspace_bytes(B, H, W) bytes of device memory, 16-byte aligned, used by this call alone. */
+size_t gdrnpp_yolox_train_inputs_workspace_bytes(int B, int H, int W);
+int gdrnpp_yolox_train_inputs(const unsigned char* src, long long src_bytes, const long long* table, const unsigned char* lut, int B, int H,
+                              int W, float* out, int* flags, void* workspace, size_t workspace_bytes, void* stream);
+
 /* device-to-device copy into a raw device pointer on `stream` — the transfer CppEGLRenderer::map_tensor performs with
  * cudaMemcpy2DFromArray in the reference (lib/egl_renderer/cpp/egl_renderer.cpp:262-298): attachment -> caller's tensor */
 int gdrnpp_copy_d2d(void* dst, const void* src, size_t bytes, void* stream);
