@@ -8,8 +8,9 @@
 // normalize = (x - PIXEL_MEAN)/PIXEL_STD in float64 -> float32 (core/base_data_loader.py:128-135).
 // OpenCV's arithmetic (third-party, not in the tree) is restated exactly as in oracle/warp_oracle.c: double LU for
 // getAffineTransform, double inverse, cvRound to 10-bit fixed point, 5 fractional bits, 15-bit integer weights for
-// u8 (incl. the {32767,0,0,1} entry 0), float weights for f32, border value 0.  Integer paths are bit-exact by
-// construction; the float bilinear keeps the left-to-right fp32 sum (no FMA).
+// u8 (incl. the fix-up of table entry 0), float weights for f32, border value 0; all of it is warp_affine.hpp's but
+// the float weights.  Integer paths are bit-exact by construction; the float bilinear keeps the left-to-right fp32
+// sum (no FMA).
 //
 // Design: grid (pixel tiles, ROI); thread = one output pixel (all channels), x fastest, so the three CHW output
 // planes are written as coalesced 256-byte rows per wave — the op is write-bound (1.08 MB/ROI written vs <= 0.16 MB
@@ -36,11 +37,8 @@ __global__ __launch_bounds__(256) void crop_img_depth_kernel(const unsigned char
                                                              int out, Norm3 nrm) {
   __shared__ double sM[6];
   const int bi = blockIdx.y;
-  if (threadIdx.x == 0) inverse_affine(centers[2 * bi], centers[2 * bi + 1], scales[bi], out, sM);
-  __syncthreads();
   double M[6];
-#pragma unroll
-  for (int k = 0; k < 6; ++k) M[k] = sM[k];
+  roi_map(centers, scales, bi, out, sM, M);
   const size_t im = (size_t)(im_idx ? im_idx[bi] : 0);
   for (int it = 0; it < kPixPerThread; ++it) {
   const int p = (blockIdx.x * kPixPerThread + it) * blockDim.x + threadIdx.x;
@@ -50,19 +48,17 @@ __global__ __launch_bounds__(256) void crop_img_depth_kernel(const unsigned char
     const unsigned char* src = images + im * H * W * 3;
     int sx, sy, alpha;
     src_coord(M, x, y, false, sx, sy, alpha);
-    const int fy = alpha >> INTER_BITS, fx = alpha & (INTER_TAB_SIZE - 1);
-    int w0 = (32 - fy) * (32 - fx) * 32, w1 = (32 - fy) * fx * 32, w2 = fy * (32 - fx) * 32, w3 = fy * fx * 32;
-    if (alpha == 0) { w0 = 32767; w3 = 1; }  // saturate_cast<short>(32768) + the table's sum fix-up
+    int w[4];
+    bilinear_weights_u8(alpha >> INTER_BITS, alpha & (INTER_TAB_SIZE - 1), w);
     const bool x0 = sx >= 0 && sx < W, x1 = sx + 1 >= 0 && sx + 1 < W, y0 = sy >= 0 && sy < H,
                y1 = sy + 1 >= 0 && sy + 1 < H;
     const unsigned char* r0 = src + ((size_t)sy * W + sx) * 3;
     const unsigned char* r1 = r0 + (size_t)W * 3;
 #pragma unroll
-    for (int k = 0; k < 3; ++k) {
+    for (int k = 0; k < 3; ++k) {              // a tap outside the image is the border value 0
       const int v00 = (x0 && y0) ? r0[k] : 0, v01 = (x1 && y0) ? r0[3 + k] : 0;
       const int v10 = (x0 && y1) ? r1[k] : 0, v11 = (x1 && y1) ? r1[3 + k] : 0;
-      int s = (v00 * w0 + v01 * w1 + v10 * w2 + v11 * w3 + (1 << 14)) >> 15;
-      s = s < 0 ? 0 : (s > 255 ? 255 : s);
+      const int s = bilinear_u8(v00, v01, v10, v11, w);
       roi_img[(((size_t)bi * 3 + k) * out + y) * out + x] = (float)(((double)s - nrm.mean[k]) / nrm.stdv[k]);
     }
   }
@@ -119,23 +115,19 @@ __global__ __launch_bounds__(256) void crop_img_depth_256_kernel(const unsigned 
   __shared__ float lut[3][256];
   const int bi = blockIdx.y, x = threadIdx.x;
   if (blockIdx.x >= out / kPixPerThread) {  // the extra workgroup of the ROI: its roi_coord_2d map (own affine map)
-    if (threadIdx.x == 0) inverse_affine(centers[2 * bi], centers[2 * bi + 1], scales[bi], out_small, sM);
-    __syncthreads();
     double Ms[6];
-#pragma unroll
-    for (int k = 0; k < 6; ++k) Ms[k] = sM[k];
+    roi_map(centers, scales, bi, out_small, sM, Ms);
     for (int p = threadIdx.x; p < out_small * out_small; p += 256) coord2d_pixel(Ms, H, W, p, out_small, bi, roi_coord2d);
     return;
   }
-  if (threadIdx.x == 0) inverse_affine(centers[2 * bi], centers[2 * bi + 1], scales[bi], out, sM);
+  roi_map_solve(centers, scales, bi, out, sM);
   if (roi_img) {
 #pragma unroll
     for (int k = 0; k < 3; ++k) lut[k][x] = (float)(((double)x - nrm.mean[k]) / nrm.stdv[k]);
   }
-  __syncthreads();
+  __syncthreads();                          // one barrier for the map and the table
   double M[6];
-#pragma unroll
-  for (int k = 0; k < 6; ++k) M[k] = sM[k];
+  roi_map_read(sM, M);
   const size_t im = (size_t)(im_idx ? im_idx[bi] : 0);
   const int adelta = cv_round(M[0] * x * AB_SCALE), bdelta = cv_round(M[3] * x * AB_SCALE);
   const unsigned char* const src = images + im * H * W * 3;
@@ -149,10 +141,8 @@ __global__ __launch_bounds__(256) void crop_img_depth_256_kernel(const unsigned 
       const int X0 = X00 + AB_SCALE / INTER_TAB_SIZE / 2, Y0 = Y00 + AB_SCALE / INTER_TAB_SIZE / 2;
       const int X = (X0 + adelta) >> (AB_BITS - INTER_BITS), Y = (Y0 + bdelta) >> (AB_BITS - INTER_BITS);
       const int sx = sat_short(X >> INTER_BITS), sy = sat_short(Y >> INTER_BITS);
-      const int fy = Y & (INTER_TAB_SIZE - 1), fx = X & (INTER_TAB_SIZE - 1);
-      int w0 = (32 - fy) * (32 - fx) * 32, w1 = (32 - fy) * fx * 32, w2 = fy * (32 - fx) * 32, w3 = fy * fx * 32;
-      if ((fy | fx) == 0) { w0 = 32767; w3 = 1; }  // saturate_cast<short>(32768) + the table's sum fix-up
-      int v00[3], v01[3], v10[3], v11[3];
+      int w[4], v00[3], v01[3], v10[3], v11[3];
+      bilinear_weights_u8(Y & (INTER_TAB_SIZE - 1), X & (INTER_TAB_SIZE - 1), w);
       if (sx >= 0 && sx + 2 < W && sy >= 0 && sy + 1 < H) {  // interior: 8 bytes per source row hold both pixels
         const unsigned char* r0 = src + ((size_t)sy * W + sx) * 3;
         const unsigned long long a = *reinterpret_cast<const u64_unaligned*>(r0);
@@ -173,11 +163,8 @@ __global__ __launch_bounds__(256) void crop_img_depth_256_kernel(const unsigned 
         }
       }
 #pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        int sv = (v00[k] * w0 + v01[k] * w1 + v10[k] * w2 + v11[k] * w3 + (1 << 14)) >> 15;
-        sv = sv < 0 ? 0 : (sv > 255 ? 255 : sv);
-        __builtin_nontemporal_store(lut[k][sv], roi_img + (((size_t)bi * 3 + k) * out + y) * out + x);
-      }
+      for (int k = 0; k < 3; ++k)
+        __builtin_nontemporal_store(lut[k][bilinear_u8(v00[k], v01[k], v10[k], v11[k], w)], roi_img + (((size_t)bi * 3 + k) * out + y) * out + x);
     }
     if (want_depth) {
       const int sx = sat_short((X00 + AB_SCALE / 2 + adelta) >> AB_BITS), sy = sat_short((Y00 + AB_SCALE / 2 + bdelta) >> AB_BITS);
@@ -193,11 +180,8 @@ __global__ __launch_bounds__(256) void crop_coord2d_kernel(int H, int W, const d
                                                            float* __restrict__ roi_coord2d, int out) {
   __shared__ double sM[6];
   const int bi = blockIdx.y;
-  if (threadIdx.x == 0) inverse_affine(centers[2 * bi], centers[2 * bi + 1], scales[bi], out, sM);
-  __syncthreads();
   double M[6];
-#pragma unroll
-  for (int k = 0; k < 6; ++k) M[k] = sM[k];
+  roi_map(centers, scales, bi, out, sM, M);
   const int p = blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= out * out) return;
   coord2d_pixel(M, H, W, p, out, bi, roi_coord2d);

@@ -82,32 +82,6 @@ __global__ __launch_bounds__(256) void mask_extent_kernel(const uint8_t* __restr
   }
 }
 
-// cv2.resize(crop, INTER_LINEAR) at destination (r, c): crop = cw x ch pixels at `crop`, rows `stride` pixels apart
-__device__ __forceinline__ void bg_pixel(const uint8_t* __restrict__ crop, size_t stride, int cw, int ch, int mode, double scale_x,
-                                         double scale_y, int r, int c, int v[3]) {
-  if (mode == kModeCopy) {
-    const uint8_t* p = crop + ((size_t)r * stride + c) * 3;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) v[k] = (int)p[k];
-  } else if (mode == kModeArea) {
-    const uint8_t* p0 = crop + ((size_t)(2 * r) * stride + 2 * c) * 3;
-    const uint8_t* p1 = p0 + stride * 3;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) v[k] = ((int)p0[k] + (int)p0[3 + k] + (int)p1[k] + (int)p1[3 + k] + 2) >> 2;
-  } else {
-    const Tap ty = linear_tap(r, scale_y, ch, false);
-    const Tap tx = linear_tap(c, scale_x, cw, true);
-    const uint8_t* r0 = crop + (size_t)ty.i0 * stride * 3;
-    const uint8_t* r1 = crop + (size_t)ty.i1 * stride * 3;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      const int h0 = (int)r0[tx.i0 * 3 + k] * tx.c0 + (int)r0[tx.i1 * 3 + k] * tx.c1;
-      const int h1 = (int)r1[tx.i0 * 3 + k] * tx.c0 + (int)r1[tx.i1 * 3 + k] * tx.c1;
-      v[k] = ((((ty.c0 * (h0 >> 4)) >> 16) + ((ty.c1 * (h1 >> 4)) >> 16) + 2) >> 2) & 255;      // the cast to uchar
-    }
-  }
-}
-
 // phase 2: the cut, mask_trunc and the composite
 __global__ __launch_bounds__(256) void replace_bg_kernel(uint8_t* __restrict__ images, const uint8_t* __restrict__ masks,
                                                          uint8_t* __restrict__ mask_trunc, const uint8_t* __restrict__ bg,
@@ -152,20 +126,15 @@ __global__ __launch_bounds__(256) void replace_bg_kernel(uint8_t* __restrict__ i
   if (keep) return;
   int v[3] = {0, 0, 0};                     // outside the paste: the zeros it was pasted on
   if (r < (int)row[cDh] && c < (int)row[cDw]) {
+    // cv2.resize(crop, INTER_LINEAR) at (r, c): the crop is cw x ch pixels of a pool image whose rows lie `stride` pixels apart
     const size_t stride = (size_t)row[cStride];
-    const uint8_t* crop = bg + (size_t)row[cOff] + ((size_t)row[cY0] * stride + (size_t)row[cX0]) * 3;
-    bg_pixel(crop, stride, (int)row[cCw], (int)row[cCh], (int)row[cMode], __longlong_as_double(row[cScaleX]),
-             __longlong_as_double(row[cScaleY]), r, c, v);
+    const StridedTaps crop{bg + (size_t)row[cOff] + ((size_t)row[cY0] * stride + (size_t)row[cX0]) * 3, stride};
+    resize_px(crop, (int)row[cCw], (int)row[cCh], (int)row[cMode], __longlong_as_double(row[cScaleX]), __longlong_as_double(row[cScaleY]), r,
+              c, v);
   }
   uint8_t* o = images + px * 3;
 #pragma unroll
   for (int k = 0; k < 3; ++k) o[k] = (uint8_t)v[k];
-}
-
-double as_double(long long bits) {
-  double d;
-  std::memcpy(&d, &bits, sizeof d);
-  return d;
 }
 
 }  // namespace
@@ -202,15 +171,11 @@ extern "C" int gdrnpp_replace_bg(unsigned char* images, const unsigned char* mas
     GDRNPP_REQUIRE(dw >= 1 && dh >= 1 && dw <= W && dh <= H, GDRNPP_EINVAL,
                    "%s: row %d: resized background %lld x %lld does not fit the %d x %d image (the reference's own paste fails here)",
                    what, b, dw, dh, W, H);
-    const long long mode = t[cMode], cut = t[cCut];
-    GDRNPP_REQUIRE(mode == kModeCopy || mode == kModeArea || mode == kModeLinear, GDRNPP_EINVAL, "%s: row %d: mode=%lld", what, b, mode);
-    GDRNPP_REQUIRE(mode != kModeCopy || (dw == cw && dh == ch), GDRNPP_EINVAL, "%s: row %d: copy of %lld x %lld into %lld x %lld", what, b,
-                   cw, ch, dw, dh);
-    GDRNPP_REQUIRE(mode != kModeArea || (2 * dw <= cw && 2 * dh <= ch), GDRNPP_EINVAL,
-                   "%s: row %d: 2:1 area mean of %lld x %lld into %lld x %lld reads beyond the crop", what, b, cw, ch, dw, dh);
-    const double sx = as_double(t[cScaleX]), sy = as_double(t[cScaleY]), u = as_double(t[cU]);
-    GDRNPP_REQUIRE(mode != kModeLinear || (sx > 0. && sy > 0. && sx * (double)dw < 1e9 && sy * (double)dh < 1e9), GDRNPP_EINVAL,
-                   "%s: row %d: scale_x=%g scale_y=%g", what, b, sx, sy);
+    char where[32];
+    std::snprintf(where, sizeof where, "row %d", b);
+    if (int e = check_request(what, where, ResizeRequest{cw, ch, dw, dh, t[cMode], as_double(t[cScaleX]), as_double(t[cScaleY])})) return e;
+    const long long cut = t[cCut];
+    const double u = as_double(t[cU]);
     GDRNPP_REQUIRE(cut >= kCutNone && cut <= kCutRight, GDRNPP_EINVAL, "%s: row %d: cut=%lld", what, b, cut);
     GDRNPP_REQUIRE(cut == kCutNone || (u >= 0. && u < 1.), GDRNPP_EINVAL, "%s: row %d: u=%g outside [0, 1)", what, b, u);
     any_cut = any_cut || cut != kCutNone;

@@ -55,17 +55,16 @@ __global__ __launch_bounds__(kThreads) void roi_targets_kernel(const RoiTargetAr
   const bool need_obj = a.roi_xyz || a.xyz_bin || (a.region && F > 0);
   const int o = need_obj ? a.obj[bi] : 0;
   const bool obj_ok = o >= 0 && o < a.n_obj;   // the binding checks it; a ROI whose obj is outside the tables gets zeros
-  if (tid == 0) inverse_affine(a.centers[2 * bi], a.centers[2 * bi + 1], a.scales[bi], out, sM);
+  roi_map_solve(a.centers, a.scales, bi, out, sM);
   if (a.region && F > 0 && obj_ok) {
     const double* f = a.fps + (size_t)o * F * 3;
     for (int i = tid; i < F * 3; i += kThreads) sF[i] = f[i];
   }
-  __syncthreads();
+  __syncthreads();                             // one barrier for the map and the points
   const int p = blockIdx.x * kThreads + tid;
   if (p >= out * out) return;
   double M[6];
-#pragma unroll
-  for (int k = 0; k < 6; ++k) M[k] = sM[k];
+  roi_map_read(sM, M);
   const int y = p / out, x = p - y * out;
   int sx, sy, alpha;
   src_coord(M, x, y, true, sx, sy, alpha);

@@ -1,6 +1,8 @@
-// OpenCV's affine-warp arithmetic on the device, shared by the kernels that crop a ROI (crop_resize.hip, roi_targets.hip):
-// getAffineTransform (double LU), the inverse map as warpAffine forms it, and the 10-bit fixed-point source coordinate of an
-// output pixel (restated as in oracle/warp_oracle.c).  Internal linkage: each translation unit gets its own copy.
+// OpenCV's cv2.warpAffine, whole (restated as in oracle/warp_oracle.c): getAffineTransform (double LU), the inversion of a 2x3 map
+// as warpAffine does it (host and device), the ROI's map solved once per workgroup, the 10-bit fixed-point source coordinate of an
+// output pixel, and the 8-bit bilinear pixel: its 15-bit integer weights and the sum of four taps.  crop_resize.hip, roi_targets.hip
+// (the ROI crops) and yolox_aug.hip (the YOLOX training batches' random affine) warp through these and bring their walk over the output,
+// their loads and their border value; a rounding rule of the warp is stated nowhere else.  Internal linkage: one copy per translation unit.
 #pragma once
 #include "common.hpp"
 
@@ -59,6 +61,21 @@ __device__ __forceinline__ bool lu_solve6(double (&A)[36], double (&b)[6]) {
   return true;
 }
 
+// cv::warpAffine's inversion of the 2x3 map M, in place; false where the determinant is 0 (OpenCV goes on with D = 0, and M
+// becomes the zero map).  Host and device: every user is compiled without contraction, the operation order is OpenCV's.
+__host__ __device__ __forceinline__ bool invert_affine(double* M) {
+  double D = M[0] * M[4] - M[1] * M[3];
+  const bool regular = D != 0;
+  D = D != 0 ? 1. / D : 0;
+  const double A11 = M[4] * D, A22 = M[0] * D;
+  M[0] = A11; M[1] *= -D;
+  M[3] *= -D; M[4] = A22;
+  const double b1 = -M[0] * M[2] - M[1] * M[5];
+  const double b2 = -M[3] * M[2] - M[4] * M[5];
+  M[2] = b1; M[5] = b2;
+  return regular;
+}
+
 // get_affine_transform(center, scale, rot=0, (out,out)) -> inverse map M (dst -> src) as warpAffine forms it
 __device__ void inverse_affine(double cx, double cy, double scale, int out, double* M) {
   float src[3][2], dst[3][2];
@@ -90,14 +107,24 @@ __device__ void inverse_affine(double cx, double cy, double scale, int out, doub
   }
 #pragma unroll
   for (int i = 0; i < 6; ++i) M[i] = b[i];
-  double D = M[0] * M[4] - M[1] * M[3];
-  D = D != 0 ? 1. / D : 0;
-  const double A11 = M[4] * D, A22 = M[0] * D;
-  M[0] = A11; M[1] *= -D;
-  M[3] *= -D; M[4] = A22;
-  const double b1 = -M[0] * M[2] - M[1] * M[5];
-  const double b2 = -M[3] * M[2] - M[4] * M[5];
-  M[2] = b1; M[5] = b2;
+  invert_affine(M);
+}
+
+// A ROI's map, once per workgroup: thread 0 solves it into the workgroup's LDS slot `sM` (6 doubles), and behind a barrier every
+// thread reads its own copy.  A kernel that stages other LDS data under the same barrier calls the two halves around its own barrier.
+__device__ __forceinline__ void roi_map_solve(const double* __restrict__ centers, const double* __restrict__ scales, int bi, int out, double* sM) {
+  if (threadIdx.x == 0) inverse_affine(centers[2 * bi], centers[2 * bi + 1], scales[bi], out, sM);
+}
+
+__device__ __forceinline__ void roi_map_read(const double* sM, double (&M)[6]) {
+#pragma unroll
+  for (int k = 0; k < 6; ++k) M[k] = sM[k];
+}
+
+__device__ __forceinline__ void roi_map(const double* __restrict__ centers, const double* __restrict__ scales, int bi, int out, double* sM, double (&M)[6]) {
+  roi_map_solve(centers, scales, bi, out, sM);
+  __syncthreads();
+  roi_map_read(sM, M);
 }
 
 __device__ __forceinline__ void src_coord(const double* M, int x, int y, bool nearest, int& sx, int& sy, int& alpha) {
@@ -115,6 +142,26 @@ __device__ __forceinline__ void src_coord(const double* M, int x, int y, bool ne
     sy = sat_short(Y >> INTER_BITS);
     alpha = (Y & (INTER_TAB_SIZE - 1)) * INTER_TAB_SIZE + (X & (INTER_TAB_SIZE - 1));
   }
+}
+
+// The 8-bit bilinear pixel (INTER_LINEAR of CV_8U).  Weights of the fraction (fy, fx), both in 1/32: cv::initInterTab2D's table entry
+// as 15-bit integers, taps in the order (y, x), (y, x + 1), (y + 1, x), (y + 1, x + 1).  Entry 0 is saturate_cast<short>(32768) with the
+// table's sum fix-up.
+__device__ __forceinline__ void bilinear_weights_u8(int fy, int fx, int w[4]) {
+  w[0] = (32 - fy) * (32 - fx) * 32;
+  w[1] = (32 - fy) * fx * 32;
+  w[2] = fy * (32 - fx) * 32;
+  w[3] = fy * fx * 32;
+  if ((fy | fx) == 0) {
+    w[0] = 32767;
+    w[3] = 1;
+  }
+}
+
+// ... and one channel from its four taps, which the caller has loaded with its border value where a tap lies outside the source
+__device__ __forceinline__ int bilinear_u8(int v00, int v01, int v10, int v11, const int w[4]) {
+  const int s = (v00 * w[0] + v01 * w[1] + v10 * w[2] + v11 * w[3] + (1 << 14)) >> 15;
+  return s < 0 ? 0 : (s > 255 ? 255 : s);
 }
 
 }  // namespace

@@ -108,39 +108,9 @@ struct CanvasTaps {
   __device__ __forceinline__ void operator()(int y, int x, int v[3]) const { unpack_px(img[(size_t)y * w + x], v); }
 };
 
-// cv2.resize(image of w x h, INTER_LINEAR) at destination (r, c), in the three forms of resize_u8.hpp
-template <class Taps>
-__device__ __forceinline__ void resize_px(const Taps& taps, int w, int h, int mode, double scale_x, double scale_y, int r, int c, int v[3]) {
-  if (mode == kModeCopy) {
-    taps(r, c, v);
-  } else if (mode == kModeArea) {
-    int p00[3], p01[3], p10[3], p11[3];
-    taps(2 * r, 2 * c, p00);
-    taps(2 * r, 2 * c + 1, p01);
-    taps(2 * r + 1, 2 * c, p10);
-    taps(2 * r + 1, 2 * c + 1, p11);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) v[k] = (p00[k] + p01[k] + p10[k] + p11[k] + 2) >> 2;
-  } else {
-    const Tap ty = linear_tap(r, scale_y, h, false);
-    const Tap tx = linear_tap(c, scale_x, w, true);
-    int p00[3], p01[3], p10[3], p11[3];
-    taps(ty.i0, tx.i0, p00);
-    taps(ty.i0, tx.i1, p01);
-    taps(ty.i1, tx.i0, p10);
-    taps(ty.i1, tx.i1, p11);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      const int h0 = p00[k] * tx.c0 + p01[k] * tx.c1;
-      const int h1 = p10[k] * tx.c0 + p11[k] * tx.c1;
-      v[k] = ((((ty.c0 * (h0 >> 4)) >> 16) + ((ty.c1 * (h1 >> 4)) >> 16) + 2) >> 2) & 255;      // the cast to uchar
-    }
-  }
-}
-
 // pixel (r, c) of source `s` (a table row's source block) after its resize
 __device__ __forceinline__ void source_px(const uint8_t* __restrict__ src, const long long* __restrict__ s, int r, int c, int v[3]) {
-  const SourceTaps taps{src + (size_t)s[sOff], (int)s[sW], false, false, false, nullptr, nullptr, nullptr};
+  const StridedTaps taps{src + (size_t)s[sOff], (size_t)s[sW]};
   resize_px(taps, (int)s[sW], (int)s[sH], (int)s[sMode], __longlong_as_double(s[sScaleX]), __longlong_as_double(s[sScaleY]), r, c, v);
 }
 
@@ -203,28 +173,16 @@ __global__ __launch_bounds__(256) void canvas_kernel(const uint8_t* __restrict__
 __device__ __forceinline__ void warp_px(const uint32_t* __restrict__ canvas, int cw, int ch, const double* Minv, int x, int y, int v[3]) {
   int sx, sy, alpha;
   src_coord(Minv, x, y, false, sx, sy, alpha);
-  const int fy = alpha >> INTER_BITS, fx = alpha & (INTER_TAB_SIZE - 1);
-  int w[4];
-  w[0] = (32 - fy) * (32 - fx) * 32;
-  w[1] = (32 - fy) * fx * 32;
-  w[2] = fy * (32 - fx) * 32;
-  w[3] = fy * fx * 32;
-  if (alpha == 0) {                         // saturate_cast<short>(32768) and the table's sum fix-up
-    w[0] = 32767;
-    w[3] = 1;
-  }
-  int acc[3] = {1 << 14, 1 << 14, 1 << 14};
+  int w[4], p[4][3];
+  bilinear_weights_u8(alpha >> INTER_BITS, alpha & (INTER_TAB_SIZE - 1), w);
 #pragma unroll
   for (int t = 0; t < 4; ++t) {
     const int xx = sx + (t & 1), yy = sy + (t >> 1);
     const bool in = xx >= 0 && xx < cw && yy >= 0 && yy < ch;
-    int p[3];
-    unpack_px(in ? canvas[(size_t)yy * cw + xx] : kPadPixel, p);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) acc[k] += p[k] * w[t];
+    unpack_px(in ? canvas[(size_t)yy * cw + xx] : kPadPixel, p[t]);
   }
 #pragma unroll
-  for (int k = 0; k < 3; ++k) v[k] = min(max(acc[k] >> 15, 0), 255);
+  for (int k = 0; k < 3; ++k) v[k] = bilinear_u8(p[0][k], p[1][k], p[2][k], p[3][k], w);
 }
 
 // launch 2: one output pixel per thread
@@ -277,34 +235,17 @@ __global__ __launch_bounds__(256) void output_kernel(const uint8_t* __restrict__
   for (int k = 0; k < 3; ++k) o[k * plane] = (float)v[k];
 }
 
-double as_double(long long bits) {
-  double d;
-  std::memcpy(&d, &bits, sizeof d);
-  return d;
-}
-
-long long as_bits(double d) {
-  long long b;
-  std::memcpy(&b, &d, sizeof b);
-  return b;
-}
-
 size_t table_bytes(int B) { return (size_t)B * kCols * sizeof(long long) + kDivInts * sizeof(int); }
 
 // checks one source block; cw x ch is the canvas it is pasted on
 int check_source(const char* what, int b, int k, const long long* s, long long src_bytes, long long cw, long long ch) {
-  const long long off = s[sOff], w = s[sW], h = s[sH], dw = s[sDw], dh = s[sDh], mode = s[sMode];
+  const long long off = s[sOff], w = s[sW], h = s[sH], dw = s[sDw], dh = s[sDh];
   GDRNPP_REQUIRE(w >= 1 && h >= 1 && w < 32768 && h < 32768 && off >= 0 && off <= src_bytes && w * h * 3 <= src_bytes - off, GDRNPP_EINVAL,
                  "%s: row %d source %d: a %lld x %lld image at offset %lld lies outside the %lld bytes of src", what, b, k, w, h, off, src_bytes);
   GDRNPP_REQUIRE(dw >= 1 && dh >= 1 && dw < 32768 && dh < 32768, GDRNPP_EINVAL, "%s: row %d source %d: resized to %lld x %lld", what, b, k, dw, dh);
-  GDRNPP_REQUIRE(mode == kModeCopy || mode == kModeArea || mode == kModeLinear, GDRNPP_EINVAL, "%s: row %d source %d: mode=%lld", what, b, k, mode);
-  GDRNPP_REQUIRE(mode != kModeCopy || (dw == w && dh == h), GDRNPP_EINVAL, "%s: row %d source %d: copy of %lld x %lld into %lld x %lld", what, b,
-                 k, w, h, dw, dh);
-  GDRNPP_REQUIRE(mode != kModeArea || (2 * dw <= w && 2 * dh <= h), GDRNPP_EINVAL,
-                 "%s: row %d source %d: 2:1 area mean of %lld x %lld into %lld x %lld reads beyond the image", what, b, k, w, h, dw, dh);
-  const double sx = as_double(s[sScaleX]), sy = as_double(s[sScaleY]);
-  GDRNPP_REQUIRE(mode != kModeLinear || (sx > 0. && sy > 0. && sx * (double)dw < 1e9 && sy * (double)dh < 1e9), GDRNPP_EINVAL,
-                 "%s: row %d source %d: scale_x=%g scale_y=%g", what, b, k, sx, sy);
+  char where[48];
+  std::snprintf(where, sizeof where, "row %d source %d", b, k);
+  if (int e = check_request(what, where, ResizeRequest{w, h, dw, dh, s[sMode], as_double(s[sScaleX]), as_double(s[sScaleY])})) return e;
   const long long lx = s[sLx], ly = s[sLy], px = s[sSx], py = s[sSy], pw = s[sPw], ph = s[sPh];
   GDRNPP_REQUIRE(pw >= 0 && ph >= 0 && px >= 0 && py >= 0 && px + pw <= dw && py + ph <= dh && lx >= 0 && ly >= 0 && lx + pw <= cw && ly + ph <= ch,
                  GDRNPP_EINVAL, "%s: row %d source %d: paste of %lld x %lld from (%lld, %lld) of %lld x %lld to (%lld, %lld) of %lld x %lld", what,
@@ -358,16 +299,7 @@ extern "C" int gdrnpp_yolox_train_inputs(const unsigned char* src, long long src
       M[k] = as_double(t[cM0 + k]);
       GDRNPP_REQUIRE(std::isfinite(M[k]) && std::fabs(M[k]) < 1e6, GDRNPP_EINVAL, "%s: row %d: M[%d]=%g", what, b, k, M[k]);
     }
-    // cv::warpAffine's inversion (oracle/warp_oracle.c invert_affine); this file is compiled without contraction
-    double D = M[0] * M[4] - M[1] * M[3];
-    if (D == 0) t[cFlags] |= fSingular;
-    D = D != 0 ? 1. / D : 0;
-    const double A11 = M[4] * D, A22 = M[0] * D;
-    M[0] = A11; M[1] *= -D;
-    M[3] *= -D; M[4] = A22;
-    const double b1 = -M[0] * M[2] - M[1] * M[5];
-    const double b2 = -M[3] * M[2] - M[4] * M[5];
-    M[2] = b1; M[5] = b2;
+    if (!invert_affine(M)) t[cFlags] |= fSingular;      // warp_affine.hpp; this file is compiled without contraction
     // cvRound of the 10-bit fixed-point coordinate has to stay an int: each of its two terms below 1e6 pixels
     GDRNPP_REQUIRE(std::fabs(M[0]) * W < 1e6 && std::fabs(M[3]) * W < 1e6 && std::fabs(M[1]) * H + std::fabs(M[2]) < 1e6 &&
                        std::fabs(M[4]) * H + std::fabs(M[5]) < 1e6,
@@ -379,15 +311,11 @@ extern "C" int gdrnpp_yolox_train_inputs(const unsigned char* src, long long src
       if (int e = check_source(what, b, kMixSource, s, src_bytes, W, H)) return e;
       GDRNPP_REQUIRE(s[sLx] == 0 && s[sLy] == 0 && s[sSx] == 0 && s[sSy] == 0 && s[sPw] == s[sDw] && s[sPh] == s[sDh], GDRNPP_EINVAL,
                      "%s: row %d: the mixup source is pasted whole, top-left", what, b);
-      const long long jw = t[cJw], jh = t[cJh], mode = t[cMode2], xo = t[cXOff], yo = t[cYOff];
+      const long long jw = t[cJw], jh = t[cJh], xo = t[cXOff], yo = t[cYOff];
       GDRNPP_REQUIRE(jw >= 1 && jh >= 1 && jw < 65536 && jh < 65536, GDRNPP_EINVAL, "%s: row %d: jittered size %lld x %lld", what, b, jw, jh);
-      GDRNPP_REQUIRE(mode == kModeCopy || mode == kModeArea || mode == kModeLinear, GDRNPP_EINVAL, "%s: row %d: mode2=%lld", what, b, mode);
-      GDRNPP_REQUIRE(mode != kModeCopy || (jw == W && jh == H), GDRNPP_EINVAL, "%s: row %d: copy of %d x %d into %lld x %lld", what, b, W, H, jw, jh);
-      GDRNPP_REQUIRE(mode != kModeArea || (2 * jw <= W && 2 * jh <= H), GDRNPP_EINVAL, "%s: row %d: 2:1 area mean of %d x %d into %lld x %lld", what,
-                     b, W, H, jw, jh);
-      const double sx = as_double(t[cScale2X]), sy = as_double(t[cScale2Y]);
-      GDRNPP_REQUIRE(mode != kModeLinear || (sx > 0. && sy > 0. && sx * (double)jw < 1e9 && sy * (double)jh < 1e9), GDRNPP_EINVAL,
-                     "%s: row %d: scale2_x=%g scale2_y=%g", what, b, sx, sy);
+      char where[48];
+      std::snprintf(where, sizeof where, "row %d jitter", b);      // the second resize, of the cp canvas: mode2, scale2_x, scale2_y
+      if (int e = check_request(what, where, ResizeRequest{W, H, jw, jh, t[cMode2], as_double(t[cScale2X]), as_double(t[cScale2Y])})) return e;
       GDRNPP_REQUIRE(xo >= 0 && yo >= 0 && xo + W <= (jw > W ? jw : W) && yo + H <= (jh > H ? jh : H), GDRNPP_EINVAL,
                      "%s: row %d: crop offset (%lld, %lld) leaves the padded image", what, b, xo, yo);
     }

@@ -22,7 +22,7 @@
 
 namespace {
 
-using namespace gdrnpp::resize_u8;          // kMode*, Tap, linear_tap: shared with replace_bg.hip
+using namespace gdrnpp::resize_u8;          // the resize itself: forms, taps, pixel, request
 constexpr float kPad = 114.f;
 
 template <bool FOCUS>
@@ -31,7 +31,7 @@ __global__ __launch_bounds__(256) void letterbox_kernel(const uint8_t* __restric
                                                         int ldy) {
   const int cx = blockIdx.x * 64 + threadIdx.x, cy = blockIdx.y * 4 + threadIdx.y, b = blockIdx.z;
   if (cx >= (Wt >> 1) || cy >= (Ht >> 1)) return;
-  const uint8_t* src = img + (size_t)b * H * W * 3;
+  const StridedTaps taps{img + (size_t)b * H * W * 3, (size_t)W};
   float v[2][2][3];                         // [row of the cell][column of the cell][colour]
 #pragma unroll
   for (int r = 0; r < 2; ++r) {
@@ -45,27 +45,7 @@ __global__ __launch_bounds__(256) void letterbox_kernel(const uint8_t* __restric
         v[r][q][0] = v[r][q][1] = v[r][q][2] = kPad;
         continue;
       }
-      if (mode == kModeCopy) {
-        const uint8_t* p = src + ((size_t)oy * W + ox) * 3;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) v[r][q][c] = (float)p[c];
-      } else if (mode == kModeArea) {
-        const uint8_t* p0 = src + ((size_t)(2 * oy) * W + 2 * ox) * 3;
-        const uint8_t* p1 = p0 + (size_t)W * 3;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) v[r][q][c] = (float)(((int)p0[c] + (int)p0[3 + c] + (int)p1[c] + (int)p1[3 + c] + 2) >> 2);
-      } else {
-        const Tap tx = linear_tap(ox, scale_x, W, true);
-        const uint8_t* r0 = src + (size_t)ty.i0 * W * 3;
-        const uint8_t* r1 = src + (size_t)ty.i1 * W * 3;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-          const int h0 = (int)r0[tx.i0 * 3 + c] * tx.c0 + (int)r0[tx.i1 * 3 + c] * tx.c1;
-          const int h1 = (int)r1[tx.i0 * 3 + c] * tx.c0 + (int)r1[tx.i1 * 3 + c] * tx.c1;
-          const int s = (((ty.c0 * (h0 >> 4)) >> 16) + ((ty.c1 * (h1 >> 4)) >> 16) + 2) >> 2;
-          v[r][q][c] = (float)(s & 255);    // the cast to uchar
-        }
-      }
+      resize_px(taps, mode, ty, linear_tap(ox, scale_x, W, true), oy, ox, v[r][q]);
     }
   }
   if (FOCUS) {
@@ -209,16 +189,13 @@ extern "C" int gdrnpp_yolox_letterbox(const unsigned char* images_u8, int B, int
   } else {
     GDRNPP_REQUIRE(((uintptr_t)out & 7) == 0, GDRNPP_EINVAL, "gdrnpp_yolox_letterbox: the output must be 8-byte aligned");
   }
-  int mode = kModeLinear;
-  if (rh == H && rw == W) mode = kModeCopy;
-  else if (H == 2 * rh && W == 2 * rw) mode = kModeArea;
-  const double scale_y = 1. / ((double)rh / H), scale_x = 1. / ((double)rw / W);   // OpenCV: 1 / inv_scale
+  const ResizeRequest q = dsize_request(W, H, rw, rh);
   const dim3 grid((Wt / 2 + 63) / 64, (Ht / 2 + 3) / 4, B), block(64, 4);
   hipStream_t st = (hipStream_t)stream;
   if (focus)
-    hipLaunchKernelGGL(letterbox_kernel<true>, grid, block, 0, st, images_u8, H, W, rh, rw, mode, scale_y, scale_x, out + y_off, Ht, Wt, ldy);
+    hipLaunchKernelGGL(letterbox_kernel<true>, grid, block, 0, st, images_u8, H, W, rh, rw, (int)q.mode, q.scale_y, q.scale_x, out + y_off, Ht, Wt, ldy);
   else
-    hipLaunchKernelGGL(letterbox_kernel<false>, grid, block, 0, st, images_u8, H, W, rh, rw, mode, scale_y, scale_x, out, Ht, Wt, 0);
+    hipLaunchKernelGGL(letterbox_kernel<false>, grid, block, 0, st, images_u8, H, W, rh, rw, (int)q.mode, q.scale_y, q.scale_x, out, Ht, Wt, 0);
   return gdrnpp::check_launch("gdrnpp_yolox_letterbox");
 }
 

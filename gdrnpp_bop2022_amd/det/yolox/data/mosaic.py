@@ -7,7 +7,7 @@ import numpy as np
 import torch
 
 from .... import hip_lib
-from ....gdrn_modeling.train_inputs import resize_request
+from ....hip_lib.cv_resize import resize_request
 from .data_augment import (adjust_box_anns, apply_affine_to_bboxes, get_affine_matrix, hsv_luts, preproc_sizes,
                            train_transform_plan)
 

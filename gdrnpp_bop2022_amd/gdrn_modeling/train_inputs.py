@@ -22,49 +22,15 @@ import numpy as np
 import torch
 
 from .. import hip_lib
+from ..hip_lib.cv_resize import MODE_AREA, MODE_COPY, MODE_LINEAR, cv_round, resize_request  # noqa: F401  (cv2.resize's request: hip_lib's, read here too)
 
 BG_DEFAULTS = dict(CHANGE_BG_PROB=0.5, TRUNCATE_FG=False, BG_KEEP_ASPECT_RATIO=True, BG_TYPE="VOC_table", WITH_BG_DEPTH=False,
                    BG_IMGS_ROOT="datasets/VOCdevkit/VOC2012/", NUM_BG_IMGS=10000)                  # configs/_base_/common_base.py:49-57
-MODE_COPY, MODE_AREA, MODE_LINEAR = (hip_lib.REPLACE_BG_MODES.index(m) for m in ("copy", "area", "linear"))
-DBL_EPSILON = float(np.finfo(np.float64).eps)
 
 
 def _input(cfg, key):
     node = cfg["INPUT"] if "INPUT" in cfg else {}
     return node[key] if key in node else BG_DEFAULTS[key]
-
-
-def cv_round(x) -> int:
-    """OpenCV's cvRound / saturate_cast<int>(double): to the nearest integer, halves to the even one."""
-    return int(np.rint(np.float64(x)))
-
-
-def resize_request(cw, ch, *, dsize=None, fx=None, fy=None) -> dict:
-    """The sizes, form and interpolation scales of an 8-bit ``cv2.resize(crop, dsize, fx=fx, fy=fy, interpolation=INTER_LINEAR)`` of a
-    cw x ch crop -> dict(dw, dh, mode, scale_x, scale_y).
-
-    OpenCV's modules/imgproc/src/resize.cpp as recalled — OpenCV is not installed where this project is built and tested and was not
-    run: without a dsize, dsize = (cvRound(cw fx), cvRound(ch fy)) and the interpolation scale is 1. / fx, NOT src / dst; with a dsize
-    the scale is 1. / (dst / src).  Then, in this order: dsize == ssize is a copy; a scale within DBL_EPSILON of exactly 2 on both axes
-    turns INTER_LINEAR into the 2 x 2 area mean; everything else is the fixed-point linear path with these scales."""
-    if dsize is None:
-        inv_x, inv_y = float(fx), float(fy)
-        dw, dh = cv_round(cw * inv_x), cv_round(ch * inv_y)
-    else:
-        dw, dh = int(dsize[0]), int(dsize[1])
-        inv_x, inv_y = float(dw) / cw, float(dh) / ch
-    if dw < 1 or dh < 1:
-        raise ValueError(f"resize_request: a {cw} x {ch} crop resized to {dw} x {dh}: cv2.resize refuses an empty destination")
-    scale_x, scale_y = 1.0 / inv_x, 1.0 / inv_y
-    if (dw, dh) == (cw, ch):
-        mode = MODE_COPY
-    elif all(abs(s - cv_round(s)) < DBL_EPSILON and cv_round(s) == 2 for s in (scale_x, scale_y)):
-        if 2 * dw > cw or 2 * dh > ch:
-            raise NotImplementedError(f"resize_request: 2:1 area mean of {cw} x {ch} into {dw} x {dh}: OpenCV's ragged last cell is not restated")
-        mode = MODE_AREA
-    else:
-        mode = MODE_LINEAR
-    return dict(dw=dw, dh=dh, mode=mode, scale_x=scale_x, scale_y=scale_y)
 
 
 def bg_geometry(bg_h, bg_w, im_H, im_W, keep_aspect=True, rng=None) -> dict:

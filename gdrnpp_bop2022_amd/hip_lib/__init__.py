@@ -8,13 +8,15 @@ non-zero status, a ``RuntimeError`` is raised (reference behavio
 
 This file is the namespace and nothing else.  The modules, in dependency order (a module imports only from those in front of it):
 ``abi`` (signature table, structs and constants read from the header, loader, pointer checks, the one launch path), ``dispatch`` (kernel-choice thresholds), ``range_words``
-(three-product range words and launch count), then one module per kernel family: ``gemm``, ``net``, ``pose``, ``roi``, ``yolox``.
+(three-product range words and launch count), ``cv_resize`` (the request of an 8-bit cv2.resize, which the tables of ``roi`` and ``yolox`` carry), then one module per
+kernel family: ``gemm``, ``net``, ``pose``, ``roi``, ``yolox``.
 State that somebody assigns lives in its owner and is assigned there (``hip_lib.dispatch.SPLIT2_MIN_TILES = 1``); the three
 ``SPLIT2_*`` thresholds can be READ here, always as the owner's current value.
 """
-from . import abi, dispatch, gemm, net, pose, range_words, roi, yolox  # noqa: F401
+from . import abi, cv_resize, dispatch, gemm, net, pose, range_words, roi, yolox  # noqa: F401
 from .abi import (LIB_PATH, SIGNATURES, LaunchTimer, check, copy_d2d, current_stream, dev_ptr, gdrnpp_meshes,  # noqa: F401
                   gdrnpp_roi_table, get_option, load, set_launch_timer, set_option, spin)
+from .cv_resize import RESIZE_MODES, cv_round, resize_request  # noqa: F401
 from .dispatch import (set_conv_splitk, shared_min_rows, shared_min_tiles, shared_min_tiles_scope, split2_tiles_ok,  # noqa: F401
                        split_gemm_tiles)
 from .gemm import (A_F16X2_ROWS, C_F16X2_ROWS, X3, conv2d_f32_split, conv3x3_f32_split, conv3x3_groupnorm_act,  # noqa: F401

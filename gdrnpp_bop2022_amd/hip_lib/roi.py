@@ -7,6 +7,7 @@ import ctypes
 import torch
 
 from .abi import dev_ptr, f32_ptr, gdrnpp_roi_table, launch, load, opt_f32_ptr
+from .cv_resize import RESIZE_MODES
 
 
 def crop_resize_roi(images, depths, im_idx, centers, scales, out_res: int = 256, out_res_small: int = 64,
@@ -247,7 +248,7 @@ def roi_train_targets(packed, table, centers, scales, im_size, *, src=None, mask
 # the columns of replace_bg's host table (include/gdrnpp_hip.h); scale_x, scale_y and u hold the bits of an fp64
 REPLACE_BG_COLUMNS = ("do", "bg_off", "bg_stride", "x0", "y0", "cw", "ch", "dw", "dh", "mode", "scale_x", "scale_y", "cut", "u")
 REPLACE_BG_F64 = ("scale_x", "scale_y", "u")
-REPLACE_BG_MODES = ("copy", "area", "linear")                                 # cv2.resize's forms: mode = index
+REPLACE_BG_MODES = RESIZE_MODES                                               # cv2.resize's forms: mode = index
 REPLACE_BG_CUTS = ("none", "upper", "bottom", "left", "right")                # trunc_mask's branches: cut = index
 
 

@@ -7,6 +7,7 @@ from __future__ import annotations
 import torch
 
 from .abi import DEFINES, channels_last_f32, dev_ptr, f32_ptr, launch, load, opt_f32_ptr
+from .cv_resize import RESIZE_MODES
 
 
 def yolox_postprocess(det_preds, num_classes: int, conf_thre: float = 0.7, nms_thre: float = 0.45, class_agnostic: bool = False,
@@ -355,7 +356,7 @@ YOLOX_AUG_COLUMNS = (("branch", "flags", "m00", "m01", "m02", "m10", "m11", "m12
 YOLOX_AUG_F64 = frozenset(("m00", "m01", "m02", "m10", "m11", "m12", "mix_scale_x", "mix_scale_y")
                           + tuple(f"s{k}_scale_{a}" for k in range(YOLOX_AUG_SOURCES) for a in "xy"))
 YOLOX_AUG_BRANCHES = ("plain", "mosaic", "mixup")                             # branch = index
-YOLOX_AUG_MODES = ("copy", "area", "linear")                                  # cv2.resize's forms: mode = index
+YOLOX_AUG_MODES = RESIZE_MODES                                                # cv2.resize's forms: mode = index
 YOLOX_AUG_FLAGS = {"hsv1": 1, "hsv1_rgb": 2, "mirror": 4, "fallback": 8, "hsv2": 16, "hsv2_rgb": 32, "mix_flip": 64}
 assert len(YOLOX_AUG_COLUMNS) == 85      # i64[B,85] in include/gdrnpp_hip.h
 

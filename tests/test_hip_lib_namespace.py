@@ -1,4 +1,4 @@
-"""``gdrnpp_bop2022_amd/hip_lib`` is the namespace of eight modules with a strict import order, one launch path (``abi.launch``) and
+"""``gdrnpp_bop2022_amd/hip_lib`` is the namespace of nine modules with a strict import order, one launch path (``abi.launch``) and
 state that lives with its owner.  CPU only: the package is imported, the shared library is never loaded."""
 import ast
 import importlib
@@ -22,6 +22,7 @@ NAMESPACE = {
                  "shared_min_tiles_scope", "split2_tiles_ok", "split_gemm_tiles"],
     "range_words": ["X3_NONFINITE", "X3_SLOTS", "X3_SMALL_ROWS", "range_words_of", "split2_nonfinite", "split2_range_words", "x3_flag_scope",
                     "x3_flags", "x3_launch_count", "x3_flag_ptr"],
+    "cv_resize": ["RESIZE_MODES", "cv_round", "resize_request"],      # the request of cv2.resize: one owner for roi's and yolox's tables
     "gemm": ["X3", "conv2d_f32_split", "conv3x3_f32_split", "conv3x3_groupnorm_act", "conv_transpose2d_f32_split",
              "conv_transpose2d_groupnorm_act", "convnext_mlp_f32_fused", "f16x2_rows_decode", "linear_f32_split", "linear_f32_split_grouped",
              "linear_f32_splitk", "mlp_fused_rows_in_range", "mlp_fused_supported", "pack_conv3x3_weight_bf16x3", "pack_conv_weight_bf16x3",
@@ -61,7 +62,7 @@ def test_hip_lib_resolves_every_name_as_the_owners_object():
             assert obj is getattr(_mod(owner), name), name
             if callable(obj):
                 assert obj.__module__ == f"{PKG}.{owner}", name
-    assert sum(len(v) for v in NAMESPACE.values()) == 100
+    assert sum(len(v) for v in NAMESPACE.values()) == 103
     assert sorted(os.listdir(PKG_DIR)) == sorted(["__init__.py"] + [m + ".py" for m in MODULES] + (["__pycache__"] if os.path.isdir(os.path.join(PKG_DIR, "__pycache__")) else []))
 
 
