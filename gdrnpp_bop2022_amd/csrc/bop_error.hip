@@ -69,7 +69,7 @@ __global__ __launch_bounds__(kThreads) void bop_error_points(
 
 #pragma unroll
   for (int s = 0; s < kSymChunk; ++s) {
-    const double a = wave_max(m3[s]), c = wave_max(m2[s]);
+    const double a = gdrnpp::wave::wave_max(m3[s]), c = gdrnpp::wave::wave_max(m2[s]);
     if (lane == 0) { s_max[wave][2 * s] = a; s_max[wave][2 * s + 1] = c; }
   }
   __syncthreads();

@@ -1,5 +1,6 @@
 // libgdrnpp_hip.so — library-level entry points (version, last error).
 #include "gemm_split.hpp"
+#include "wave_ops.hpp"
 #include <cstring>
 #include <atomic>
 #include <mutex>
@@ -76,7 +77,7 @@ __global__ void stream_read_kernel(const float* __restrict__ p, size_t n, float*
   } else {
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) acc += p[i];
   }
-  for (int off = 32; off >= 1; off >>= 1) acc += __shfl_xor(acc, off, 64);
+  acc = gdrnpp::wave::wave_sum(acc);
   if ((threadIdx.x & 63) == 0) atomicAdd(out + blockIdx.x, acc);
 }
 // stream-overlap probe: one wave spins on the constant-rate wall clock (s_memrealtime) until `ticks` have passed

@@ -17,6 +17,7 @@
 //   im2col      the adjoint of deconv_col2im_kernel (net_kernels.hip): the operand of the transposed convolution's two gradient GEMMs.
 // No atomics and no scratch; every sum has a fixed order, so two calls give equal bits.
 #include "exact_gemm_device.hpp"
+#include "gn_stats.hpp"
 #include <algorithm>
 #include <cstdint>
 
@@ -26,51 +27,10 @@ using namespace gdrnpp::exactgemm;
 using gdrnpp::aligned16;
 using gdrnpp::gelu_erf;
 using gdrnpp::gelu_grad;
+using gdrnpp::gn::gn_group_stats;
 
 // ---- GroupNorm (+ GELU) backward ------------------------------------------------------------------------------------------------
-// mean and rstd of image n's groups into LDS: gn_apply_kernel's expression and summation order (net_kernels.hip), so that xhat has
-// the forward's bits.  256 threads; the caller synchronises.
-__device__ __forceinline__ void gn_group_stats(const double* __restrict__ part, int n, int P, int G, int HW, int cpg, float eps,
-                                               float* s_mean, float* s_rstd) {
-  if (G * 8 <= (int)blockDim.x) {
-    const int g8 = threadIdx.x >> 3, sub = threadIdx.x & 7;
-    double a = 0.0, c2 = 0.0;
-    if (g8 < G) {
-      for (int p = sub; p < P; p += 8) {
-        const double* o = part + (((size_t)n * P + p) * G + g8) * 2;
-        a += o[0];
-        c2 += o[1];
-      }
-    }
-#pragma unroll
-    for (int off = 4; off >= 1; off >>= 1) {
-      a += __shfl_xor(a, off, 64);
-      c2 += __shfl_xor(c2, off, 64);
-    }
-    if (g8 < G && sub == 0) {
-      const double cnt = (double)HW * cpg;
-      const double m = a / cnt;
-      double var = c2 / cnt - m * m;
-      if (var < 0.0) var = 0.0;
-      s_mean[g8] = (float)m;
-      s_rstd[g8] = (float)(1.0 / sqrt(var + (double)eps));
-    }
-  } else if ((int)threadIdx.x < G) {
-    double a = 0.0, c2 = 0.0;
-    for (int p = 0; p < P; ++p) {
-      const double* o = part + (((size_t)n * P + p) * G + threadIdx.x) * 2;
-      a += o[0];
-      c2 += o[1];
-    }
-    const double cnt = (double)HW * cpg;
-    const double m = a / cnt;
-    double var = c2 / cnt - m * m;
-    if (var < 0.0) var = 0.0;
-    s_mean[threadIdx.x] = (float)m;
-    s_rstd[threadIdx.x] = (float)(1.0 / sqrt(var + (double)eps));
-  }
-}
-
+// mean and rstd of image n's groups come from gn_group_stats (gn_stats.hpp), the forward's own function: xhat has the forward's bits.
 // The pixels of an image are dealt to at most 64 slots of at least 32 pixels; the count depends on HW alone.
 struct GnPlan { int slots, pixels; };
 inline GnPlan gn_plan(int HW) {

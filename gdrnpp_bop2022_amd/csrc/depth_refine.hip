@@ -26,6 +26,7 @@
 // a class share it): 4 maps x 16 KiB + the used quarter of the 256x256 depth crop + I x (12 V + 12 F) mesh bytes.
 #include "common.hpp"
 #include "raster.hpp"
+#include "wave_ops.hpp"
 #include <cfloat>
 
 namespace {
@@ -78,8 +79,7 @@ constexpr int kMaxStagedVerts = 2688;  // 105 KiB of LDS (with the 54 KiB of sta
 constexpr int kMaxLargeS = 1024;       // queue of wave-rasterised triangles (overflow falls back to per-lane)
 
 __device__ __forceinline__ double block_sum_s(double v, double* s_red) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
+  v = wave::wave_sum(v);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   __syncthreads();
   if (lane == 0) s_red[wave] = v;
@@ -89,8 +89,7 @@ __device__ __forceinline__ double block_sum_s(double v, double* s_red) {
   return r;
 }
 __device__ __forceinline__ float block_max_s(float v, float* s_red) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
+  v = wave::wave_max(v);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   __syncthreads();
   if (lane == 0) s_red[wave] = v;
@@ -430,8 +429,7 @@ __global__ __launch_bounds__(kTS) void depth_refine_kernel(const RefineArgs a) {
       keys[k] = f2key(ds[k] - ren[k]);
       mine += sel[k] ? 1 : 0;
     }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) mine += __shfl_xor(mine, off, 64);
+    mine = wave::wave_sum(mine);
     if ((tid & 63) == 0 && mine) atomicAdd(&s_nsel, mine);
     __syncthreads();
     const int nsel = s_nsel;

@@ -18,20 +18,17 @@
 //   final_kernel       one wave per ROI        replays the sequential best-model / iteration-count logic over the counts,
 //                      rebuilds the winner's inlier mask and runs EPnP over the inliers with wave-shuffle reductions
 #include "common.hpp"
+#include "wave_ops.hpp"
 
 namespace {
+
+using gdrnpp::wave::wave_sum;
 
 constexpr int kModelPts = 5;
 
 struct Cam { double fu, fv, uc, vc; };
 
 __device__ __forceinline__ bool is_finite(double v) { return fabs(v) <= 1.7976931348623157e308; }  // false for NaN / inf
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
 
 // cyclic Jacobi on a symmetric N x N matrix (row-major a), eigenvectors in the COLUMNS of v, eigenvalues ascending
 template <int N>
@@ -725,7 +722,7 @@ __global__ __launch_bounds__(64) void final_kernel(const float* __restrict__ img
         m[i] = in ? 1 : 0;
         good += in ? 1 : 0;
       }
-      for (int off = 32; off >= 1; off >>= 1) good += __shfl_xor(good, off, 64);
+      good = wave_sum(good);
       ok = true;
     }
   }

@@ -27,7 +27,7 @@
 
 namespace {
 
-using gdrnpp::pairs::wave_sum_fixed;
+using gdrnpp::wave::wave_sum_down;
 
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
@@ -208,7 +208,7 @@ __global__ __launch_bounds__(kThreads) void dense_kernel(const DenseArgs a) {
   const int wave = tid >> 6, lane = tid & 63;
 #pragma unroll
   for (int c = 0; c < kCols; ++c) {
-    const double v = wave_sum_fixed(acc[c]);
+    const double v = wave_sum_down(acc[c]);
     if (lane == 0) s_red[wave][c] = v;
   }
   __syncthreads();
@@ -392,7 +392,7 @@ __global__ __launch_bounds__(kThreads) void pose_kernel(const PoseArgs a) {
   }
 #pragma unroll
   for (int k = 0; k < kPoseAcc; ++k) {
-    const double v = wave_sum_fixed(acc[k]);
+    const double v = wave_sum_down(acc[k]);
     if (lane == 0) s_red[wave][k] = v;
   }
   __syncthreads();

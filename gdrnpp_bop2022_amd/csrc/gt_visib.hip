@@ -49,12 +49,14 @@
 // pixels) bounds the call with masks: HBM writes.  The measured fractions are in DESIGN.md (tools/gt_info_bench.py).
 #include "common.hpp"
 #include "tile_raster.hpp"
+#include "wave_ops.hpp"
 #include <climits>
 
 namespace {
 
 using namespace gdrnpp;
 using namespace gdrnpp::tiles;
+using wave::wave_max, wave::wave_min, wave::wave_sum;
 
 constexpr int kInfo = 11;  // all, valid, visib, obj x0 y0 x1 y1, visib x0 y0 x1 y1
 
@@ -105,18 +107,6 @@ __global__ __launch_bounds__(kThreads) void gt_project(const GtArgs a) {
   for (int k = 0; k < 3; ++k) t[k] = a.t[3 * pose + k];
   stage_vertices_and_box(a.verts + 3 * (size_t)v0, nv, K, R, t, a.hv + (pose * (size_t)a.max_verts) * kVtx, a.z_near, a.z_far, a.Wc, a.Hc,
                          s_red, box);
-}
-
-__device__ __forceinline__ int wave_min(int v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = min(v, __shfl_xor(v, off, 64));
-  return v;
-}
-
-__device__ __forceinline__ int wave_max(int v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = max(v, __shfl_xor(v, off, 64));
-  return v;
 }
 
 __global__ __launch_bounds__(kThreads) void gt_tiles(const GtArgs a, int tiles_x, int ntiles) {

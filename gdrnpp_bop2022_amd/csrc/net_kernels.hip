@@ -14,6 +14,7 @@
 // order differs, so parity is a tolerance (1e-5 rel, tests/test_gpu_net_kernels.py), not bit equality.
 #include "common.hpp"
 #include "dpp_sum.hpp"
+#include "gn_stats.hpp"
 #include "layernorm_rows.hpp"
 #include "split2_common.hpp"
 #include <mutex>
@@ -562,46 +563,7 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const float* __restrict__
   __shared__ float s_mean[64], s_rstd[64];
   const int Q = C >> 2, cpg = C / G;
   const int n = blockIdx.y;
-  // Group statistics from the P x G fp64 partials.  Every workgroup needs them before it can stream: 8 lanes per group share the P
-  // partials (8 independent loads in flight per lane instead of a chain of 64 per group thread: the serial form held each of the
-  // 8192 workgroups of a 64x64 launch ~6 us before its first store — a quarter of its lifetime), then a 3-step shuffle tree.
-  if (G * 8 <= (int)blockDim.x) {
-    const int g8 = threadIdx.x >> 3, sub = threadIdx.x & 7;
-    double a = 0.0, c2 = 0.0;
-    if (g8 < G) {
-      for (int p = sub; p < P; p += 8) {
-        const double* o = part + (((size_t)n * P + p) * G + g8) * 2;
-        a += o[0];
-        c2 += o[1];
-      }
-    }
-#pragma unroll
-    for (int off = 4; off >= 1; off >>= 1) {
-      a += __shfl_xor(a, off, 64);
-      c2 += __shfl_xor(c2, off, 64);
-    }
-    if (g8 < G && sub == 0) {
-      const double cnt = (double)HW * cpg;
-      const double m = a / cnt;
-      double var = c2 / cnt - m * m;
-      if (var < 0.0) var = 0.0;
-      s_mean[g8] = (float)m;
-      s_rstd[g8] = (float)(1.0 / sqrt(var + (double)eps));
-    }
-  } else if ((int)threadIdx.x < G) {
-    double a = 0.0, c2 = 0.0;
-    for (int p = 0; p < P; ++p) {
-      const double* o = part + (((size_t)n * P + p) * G + threadIdx.x) * 2;
-      a += o[0];
-      c2 += o[1];
-    }
-    const double cnt = (double)HW * cpg;
-    const double m = a / cnt;
-    double var = c2 / cnt - m * m;
-    if (var < 0.0) var = 0.0;
-    s_mean[threadIdx.x] = (float)m;
-    s_rstd[threadIdx.x] = (float)(1.0 / sqrt(var + (double)eps));
-  }
+  gdrnpp::gn::gn_group_stats(part, n, P, G, HW, cpg, eps, s_mean, s_rstd);
   __syncthreads();
   const long total = (long)HW * Q;
   // Four elements per trip with their loads issued together: one 16-byte load in flight per thread held the pass at ~4 TB/s

@@ -1,6 +1,6 @@
 // The device and host layer shared by the pose-error kernels that score (estimate, ground truth) pairs over an object's symmetry
-// transformations: bop_error.hip (MSSD / MSPD) and sym_error.hip (reS / teS / projS) in full, pose_error.hip for re_deg and the fixed-order
-// sum.  The bodies are those the three files were merged with, moved here unchanged as forceinline functions: every expression keeps its
+// transformations: bop_error.hip (MSSD / MSPD) and sym_error.hip (reS / teS / projS) in full, pose_error.hip for re_deg (their
+// wave reductions are wave_ops.hpp's).  The bodies are those the three files were merged with, moved here unchanged as forceinline functions: every expression keeps its
 // operand order and its fma / non-fma form, so the results are the same bits.
 //
 // The chunk scheme: a workgroup of kThreads owns one (pair, chunk of kSymChunk symmetries).  Its first threads compose the chunk's
@@ -14,6 +14,7 @@
 // Workspace: the device copy of sym_off (off_bytes), then cols doubles per (pair, chunk of the object with the most symmetries).
 #pragma once
 #include "common.hpp"
+#include "wave_ops.hpp"
 #include <cmath>
 
 namespace gdrnpp {
@@ -23,25 +24,6 @@ constexpr int kThreads = 256;   // 4 waves; a thread's points are tid, tid + 256
 constexpr int kWaves = kThreads / 64;
 constexpr int kSymChunk = 8;    // symmetries per workgroup: each keeps its accumulators in every thread's registers
 constexpr int kXf = 12;         // doubles per composed transform: A_s row-major, then b_s
-
-__device__ __forceinline__ double wave_max(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off, 64));
-  return v;
-}
-
-__device__ __forceinline__ double wave_min(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = fmin(v, __shfl_xor(v, off, 64));
-  return v;
-}
-
-__device__ __forceinline__ double wave_sum_fixed(double v) {
-  // fixed tree over the 64 lanes: the same order in every run
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;
-}
 
 // R p + t, one expression for the estimate and for every ground-truth transform
 __device__ __forceinline__ void pose_pt(const double* __restrict__ X, double px, double py, double pz, double& x, double& y,

@@ -17,6 +17,7 @@
 // Per-tile maxima go to the workspace f32[b][hw / 128][1024]; fp32 max is exact and order-independent, so the result is
 // bit-reproducible without atomics on any stream.
 #include "common.hpp"
+#include "wave_ops.hpp"
 
 #include <cmath>
 
@@ -205,9 +206,7 @@ __device__ __forceinline__ void fc_row(const float* __restrict__ wrow, const flo
     }
   }
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1)
-#pragma unroll
-    for (int r = 0; r < kFcRois; ++r) s[r] += __shfl_xor(s[r], o, 64);
+  for (int r = 0; r < kFcRois; ++r) s[r] = gdrnpp::wave::wave_sum(s[r]);
 }
 
 // feat = lrelu(fc2(lrelu(fc1(max over tiles)))) for kFcRois ROIs per workgroup of 16 waves

@@ -28,7 +28,7 @@
 #include <cfloat>
 
 using gdrnpp::pairs::re_deg;          // the trace form sym_error.hip takes its reS from
-using gdrnpp::pairs::wave_sum_fixed;
+using gdrnpp::wave::wave_sum_down;
 
 namespace {
 
@@ -196,8 +196,8 @@ __global__ __launch_bounds__(kPts) void pose_error_points(
     pj = sqrt(du * du + dv * dv);
   }
   // fixed order: a shuffle tree per wave, then the four waves in order
-  ad = wave_sum_fixed(ad);
-  pj = wave_sum_fixed(pj);
+  ad = wave_sum_down(ad);
+  pj = wave_sum_down(pj);
   if (lane == 0) { s_sum[wave][0] = ad; s_sum[wave][1] = pj; }
   __syncthreads();
   if (threadIdx.x == 0) {

@@ -9,6 +9,7 @@
 // (one workgroup per row, the same fixed order with 256 partial sums), which reads that row's gradient a second time.
 // 16-byte accesses where every pointer of the item allows them, dword accesses otherwise: the arithmetic per element is the same.
 #include "common.hpp"
+#include "wave_ops.hpp"
 
 namespace {
 
@@ -47,12 +48,6 @@ __device__ __forceinline__ void ranger_elem(float g, float& p, float& m, float& 
 
 __device__ __forceinline__ bool aligned16(const void* q) { return (reinterpret_cast<unsigned long long>(q) & 15ull) == 0; }
 
-__device__ __forceinline__ double wave_sum_all(double x) {     // every lane receives the same bits: a + b is commutative
-#pragma unroll
-  for (int o = 1; o < gdrnpp::kWave; o <<= 1) x += __shfl_xor(x, o, gdrnpp::kWave);
-  return x;
-}
-
 __global__ __launch_bounds__(kMeanThreads) void ranger_long_row_means_kernel(const gdrnpp_ranger_tensor* __restrict__ tensors,
                                                                              const gdrnpp_ranger_long_row* __restrict__ rows,
                                                                              float* __restrict__ means) {
@@ -68,13 +63,8 @@ __global__ __launch_bounds__(kMeanThreads) void ranger_long_row_means_kernel(con
     if (fix) x = fix_nonfinite(x);
     s += (double)x;
   }
-  part[threadIdx.x] = s;
-  __syncthreads();
-  for (int o = kMeanThreads / 2; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) part[threadIdx.x] += part[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) means[blockIdx.x] = (float)(part[0] / (double)L);
+  const double total = gdrnpp::wave::block_sum_halving<kMeanThreads>(s, part);
+  if (threadIdx.x == 0) means[blockIdx.x] = (float)(total / (double)L);
 }
 
 template <bool VEC>
@@ -188,7 +178,7 @@ __global__ __launch_bounds__(kThreads) void ranger_step_kernel(const gdrnpp_rang
       float* row = tile + r * L;
       double s = 0.0;
       for (int i = lane; i < L; i += gdrnpp::kWave) s += (double)row[i];
-      const float mu = (float)(wave_sum_all(s) / (double)L);
+      const float mu = (float)(gdrnpp::wave::wave_sum_ascending(s) / (double)L);   // every lane receives the same bits
       for (int i = lane; i < L; i += gdrnpp::kWave) row[i] -= mu;
     }
     __syncthreads();

@@ -97,7 +97,7 @@ __global__ __launch_bounds__(kThreads) void sym_error_points(
   // fixed order: a shuffle tree per wave, then the four waves in order
 #pragma unroll
   for (int s = 0; s < kSymChunk; ++s) {
-    const double a = wave_sum_fixed(acc[s]);
+    const double a = gdrnpp::wave::wave_sum_down(acc[s]);
     if (lane == 0) s_sum[wave][s] = a;
   }
   __syncthreads();
@@ -135,8 +135,8 @@ __global__ __launch_bounds__(64) void sym_error_rt(int n_obj, const int* __restr
       re = fmin(re, r);
       te = fmin(te, t);
     }
-    re = wave_min(re);
-    te = wave_min(te);
+    re = gdrnpp::wave::wave_min(re);
+    te = gdrnpp::wave::wave_min(te);
   }
   if (threadIdx.x == 0) {
     out[3 * pair] = re;

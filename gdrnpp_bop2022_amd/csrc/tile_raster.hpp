@@ -23,12 +23,6 @@ __device__ __forceinline__ void render_K(const double* __restrict__ Kp, double* 
   K[6] = 0.0; K[7] = 0.0; K[8] = 1.0;
 }
 
-__device__ __forceinline__ int wave_sum(int v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
 // One workgroup of kThreads: stages h = K (R v + t), u = h0 / h2, v = h1 / h2 of the nv vertices at mv into hv[nv][kVtx] and writes the
 // pose's conservative pixel box of a W x H render to box[4] = i_lo, i_hi, j_lo, j_hi (inclusive; empty when lo > hi; the whole render
 // once a vertex is nearer than z_near).  s_red: kWaves x 6 doubles of LDS.  Holds one __syncthreads: every thread of the workgroup calls.

@@ -17,9 +17,12 @@
 // Per iteration the correspondences (64 B/point in the fp64 ABI) are re-read from
 // L2; algorithmic HBM bytes = 64*pn + 72 + 48 in, 48 out per problem.
 #include "common.hpp"
+#include "wave_ops.hpp"
 #include <cfloat>
 
 namespace {
+
+using gdrnpp::wave::wave_sum;
 
 struct J3 {  // dual number with 3 infinitesimals (d/dw0, d/dw1, d/dw2)
   double v, d[3];
@@ -69,12 +72,6 @@ __device__ void rotation_and_derivs(const double* w, double* R, double dR[3][9])
     R[i] = M[i].v;
     dR[0][i] = M[i].d[0]; dR[1][i] = M[i].d[1]; dR[2][i] = M[i].d[2];
   }
-}
-
-__device__ __forceinline__ double wave_sum(double x) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) x += __shfl_xor(x, off, 64);
-  return x;
 }
 
 // One pass over the correspondences: cost, g = J^T r, H = J^T J (full 6x6, symmetric)

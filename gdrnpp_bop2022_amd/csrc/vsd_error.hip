@@ -45,12 +45,14 @@
 // of the face walk and of the compare loop.
 #include "common.hpp"
 #include "tile_raster.hpp"
+#include "wave_ops.hpp"
 #include <climits>
 
 namespace {
 
 using namespace gdrnpp;
 using namespace gdrnpp::tiles;   // tile_raster.hpp: kThreads, kTile, kVtx ..., the staging and the face walk shared with gt_visib.hip
+using wave::wave_sum;
 
 constexpr int kMaxTau = 16;
 

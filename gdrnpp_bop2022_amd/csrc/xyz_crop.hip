@@ -53,12 +53,14 @@
 // magnitude above what a pose can reach.  The measured figure is in DESIGN.md (tools/xyz_crop_bench.py).
 #include "common.hpp"
 #include "tile_raster.hpp"
+#include "wave_ops.hpp"
 #include <climits>
 
 namespace {
 
 using namespace gdrnpp;
 using namespace gdrnpp::tiles;
+using wave::wave_max, wave::wave_min, wave::wave_sum;
 
 constexpr int kRow = 12;  // status, count, x1 y1 x2 y2, box i_lo i_hi j_lo j_hi, offset in pixels (low, high word)
 constexpr int kBox = 6, kOff = 10;
@@ -152,18 +154,6 @@ __global__ __launch_bounds__(kThreads) void xyz_offsets(const XyzArgs a) {
     __syncthreads();
   }
   if (tid == 0) { a.totals[0] = s_done; a.totals[1] = (long long)s_used; }
-}
-
-__device__ __forceinline__ int wave_min(int v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = min(v, __shfl_xor(v, off, 64));
-  return v;
-}
-
-__device__ __forceinline__ int wave_max(int v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = max(v, __shfl_xor(v, off, 64));
-  return v;
 }
 
 __device__ __forceinline__ unsigned short half_bits(float v) {

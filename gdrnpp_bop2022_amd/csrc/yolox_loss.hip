@@ -17,6 +17,7 @@
 // Losses: per-anchor terms in fp64 from the fp32 inputs (decode included), per-workgroup partials added in a fixed tree, the partials
 // added in workgroup order: equal bits on every run.  The backward recomputes from the same inputs.
 #include "common.hpp"
+#include "wave_ops.hpp"
 #include <cfloat>
 #include <climits>
 #include <cmath>
@@ -400,14 +401,8 @@ __device__ void anchor_terms(const LossArgs& a, int i, double* term, const doubl
 
 // Sum of v over the workgroup in a fixed tree; the result in thread 0.
 __device__ double block_sum(double v, double* lds) {
-  lds[threadIdx.x] = v;
-  __syncthreads();
-  for (int off = kThreads / 2; off > 0; off >>= 1) {
-    if ((int)threadIdx.x < off) lds[threadIdx.x] += lds[threadIdx.x + off];
-    __syncthreads();
-  }
-  const double r = lds[0];
-  __syncthreads();
+  const double r = gdrnpp::wave::block_sum_halving<kThreads>(v, lds);
+  __syncthreads();   // the next call writes the slots again
   return r;
 }
 
