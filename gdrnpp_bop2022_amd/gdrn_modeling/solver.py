@@ -7,7 +7,9 @@ rebuilt on the host every step (gradient pointers change with ``zero_grad(set_to
 nothing is read back.  Everything else (CPU tensors, other dtypes, non-contiguous parameters) runs the same step on torch operators, one
 tensor at a time; on a GPU those are counted in ``torch_path_tensors`` the way ``hip_layers`` counts launches outside the library.
 
-What is not here: the ``do_train`` loop, data loading and augmentation, DDP and AMP, ``ModelEMA``, gradient clipping
+``build_model_ema`` reads ``cfg.MODEL.EMA`` and returns the loop's ``ModelEMA`` (lib/torch_utils/torch_utils.py, the detector's class).
+
+What is not here: the ``do_train`` loop, data loading and augmentation, DDP and AMP, gradient clipping
 (``CLIP_GRADIENTS.ENABLED`` raises), the reference's other optimisers and schedulers, and hipGraph capture of the step."""
 from __future__ import annotations
 
@@ -291,6 +293,18 @@ def build_lr_scheduler(cfg, optimizer, total_iters, return_function=False):
         optimizer, total_iters=total_iters, warmup_factor=s.WARMUP_FACTOR, warmup_iters=s.WARMUP_ITERS, warmup_method=s.WARMUP_METHOD,
         anneal_method=s.ANNEAL_METHOD, anneal_point=s.ANNEAL_POINT, steps=_get(s, "REL_STEPS", [2 / 3.0, 8 / 9.0]),
         target_lr_factor=_get(s, "TARGET_LR_FACTOR", 0), poly_power=_get(s, "POLY_POWER", 1.0), step_gamma=s.GAMMA, return_function=return_function)
+
+
+def build_model_ema(cfg, model):
+    """``cfg.MODEL.EMA`` -> ``ModelEMA(model, **INIT_CFG)`` (``decay``, ``updates``), or None unless ``ENABLED`` is set.  The keys are read
+    with defaults: a config without the block trains without an EMA, as the reference's base config does.  Build it after the weights
+    are loaded, and set ``ema.updates`` to the start iteration on resume (engine.py:234-237 of the reference)."""
+    from ..lib.torch_utils.torch_utils import ModelEMA
+
+    block = _get(_get(cfg, "MODEL", {}), "EMA", None)
+    if block is None or not _get(block, "ENABLED", False):
+        return None
+    return ModelEMA(model, **dict(_get(block, "INIT_CFG", {})))
 
 
 def model_param_groups(cfg, backbone, geo_head, pnp_net):

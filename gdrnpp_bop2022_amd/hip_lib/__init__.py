@@ -40,6 +40,7 @@ from .net import (downsample_backward, downsample_weight_nk, layernorm_patch2x2,
                   stem_conv4x4_ln_backward)
 from .net import (RANGER_COEFS, RANGER_LONG_ROW, RANGER_LOOKAHEAD, RANGER_NAN_TO_NUM, RANGER_RECTIFIED, RANGER_TENSOR, RANGER_TILE,  # noqa: F401
                   RANGER_WORK, RangerTables, ranger_plan, ranger_same_layout, ranger_step, ranger_tensor_ok)
+from .net import EMA_TENSOR, EMA_TILE, EMA_WORK, EmaTables, ema_plan, ema_tensor_ok, ema_update  # noqa: F401
 from .pose import (GT_INFO_COLUMNS, XYZ_CROP_COLUMNS, MeshSet, bop_errors, decode_correspondences, depth_refine, epnp_batched, epnp_ransac,  # noqa: F401
                    flow_forward, fps, gt_visibility, gt_xyz_crops, nnd_backward, nnd_forward, pack_pose_records, paste_masks_rle, pnp_iter_from_correspondences, pose_from_pred,
                    pose_errors, pose_from_pred_centroid_z, refine_kernel_name, refine_to_records, render_depth, set_refine_event_sink,

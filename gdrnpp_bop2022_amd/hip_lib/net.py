@@ -702,3 +702,99 @@ def ranger_step(tables: RangerTables, params, grads, exp_avgs, exp_avg_sqs, slow
     tables.uploads += 1
     launch("gdrnpp_ranger_step", tables.table.data_ptr(), n, work.data_ptr(), n_work, long_rows.data_ptr() if n_long else None, n_long,
            means.data_ptr() if n_long else None)
+
+
+# ---- ModelEMA update over all floating-point tensors of a model (csrc/model_ema.hip) ------------------------------------------------------
+# The header declares the two tables as bytes and describes their records in its comment; csrc/model_ema.hip asserts the same offsets.
+EMA_TILE = 8192                                      # elements per work item (one workgroup): the kernel's GDRNPP_EMA_TILE, its straight-line path
+EMA_TENSOR = np.dtype({"names": ["ema", "model", "numel"], "formats": ["<u8", "<u8", "<i8"], "offsets": [0, 8, 16], "itemsize": 24})
+EMA_WORK = np.dtype({"names": ["start", "tensor", "count"], "formats": ["<i8", "<i4", "<i4"], "offsets": [0, 8, 12], "itemsize": 16})
+
+
+def ema_plan(numels, tile: int = EMA_TILE):
+    """The work items of ``gdrnpp_model_ema_update`` for tensors of ``numels`` elements -> ``EMA_WORK``[n_work]: every tensor cut into
+    pieces of ``tile`` elements and a shorter last one; an empty tensor gets none.  Host code, no device needed."""
+    work = []
+    for t, n in enumerate(numels):
+        start = np.arange(0, int(n), tile, dtype=np.int64)
+        w = np.zeros(len(start), EMA_WORK)
+        w["start"], w["tensor"], w["count"] = start, t, np.minimum(tile, int(n) - start)
+        work.append(w)
+    return np.concatenate(work) if work else np.zeros(0, EMA_WORK)
+
+
+class EmaTables:
+    """What one ``ModelEMA`` keeps between updates for ``ema_update``: the per-tensor table and the work items on the device, under the
+    key they were built from (the ``(data_ptr, numel)`` of every EMA and model tensor), and the pinned staging buffers of their upload.
+    Unlike the Ranger step's table nothing here changes from one update to the next (the coefficients are arguments of the launch), so
+    a steady-state update uploads nothing; the tables are built again when the key changes (a parameter's ``.data`` replaced, a model
+    moved)."""
+
+    def __init__(self, device):
+        self.device = torch.device(device)
+        self.key = None
+        self.n_tensors = self.n_work = self.numel = 0
+        self.table = self.work = None        # uint8 device buffers
+        self.staging = []                    # pinned uint8 buffers of the last build, kept until the next one (their copies are asynchronous)
+        self.uploads = 0                     # asynchronous table copies issued so far (two per build)
+        self.builds = 0
+
+    def close(self):
+        """Wait for the device and drop the tables and the staging buffers (their memory goes back to torch's allocators here and now)."""
+        torch.cuda.synchronize(self.device)
+        self.key, self.table, self.work, self.staging = None, None, None, []
+        self.n_tensors = self.n_work = self.numel = 0
+
+    def _upload(self, host):
+        src = torch.empty((max(host.nbytes, 16),), dtype=torch.uint8, pin_memory=True)
+        src.numpy()[:host.nbytes] = host.view(np.uint8).reshape(-1)
+        dst = torch.empty((src.numel(),), dtype=torch.uint8, device=self.device)
+        dst.copy_(src, non_blocking=True)
+        self.staging.append(src)
+        self.uploads += 1
+        return dst
+
+    def build(self, key, ema_tensors, model_tensors):
+        if self.staging:         # a rebuild: the copies of the last build may still read the buffers about to be dropped
+            torch.cuda.synchronize(self.device)
+        self.staging = []
+        host = np.zeros(len(ema_tensors), EMA_TENSOR)
+        host["ema"] = [t.data_ptr() for t in ema_tensors]
+        host["model"] = [t.data_ptr() for t in model_tensors]
+        host["numel"] = [t.numel() for t in ema_tensors]
+        work = ema_plan(host["numel"])
+        self.n_tensors, self.n_work, self.numel = len(host), len(work), int(host["numel"].sum())
+        self.table, self.work = (self._upload(host), self._upload(work)) if len(work) else (None, None)
+        self.key = key
+        self.builds += 1
+
+
+def ema_tensor_ok(e, m) -> bool:
+    """Whether ``ema_update`` takes the pair: both dense fp32 tensors on one GPU (contiguous, or 4-D channels_last), of one shape and
+    one layout (``ranger_same_layout``: element i of one is element i of the other in memory order)."""
+    return ranger_tensor_ok(e) and ranger_tensor_ok(m, e)
+
+
+def ema_update(tables: EmaTables, ema_tensors, model_tensors, decay: float, one_minus_decay: float, validate: bool = True):
+    """``gdrnpp_model_ema_update``: ``e = fadd(fmul(e, decay), fmul(one_minus_decay, m))`` over every listed pair, in place, in one launch.
+    Two lists of f32 device tensors, pair i laid out alike (``ema_tensor_ok``).  The coefficients are rounded to fp32 here and passed by
+    value.  The device tables are those of ``tables`` while the ``(data_ptr, numel)`` of both lists are the ones they were built from,
+    else they are built and uploaded now (two asynchronous copies); nothing is read back and nothing waits.  ``validate=False`` is for a
+    caller that has just held every pair to ``ema_tensor_ok`` itself (``ModelEMA``).  The caller advances the EMA tensors' version counters."""
+    n = len(ema_tensors)
+    if len(model_tensors) != n:
+        raise RuntimeError("ema_update: the two lists differ in length")
+    if n == 0:
+        return
+    if validate:
+        for i, (e, m) in enumerate(zip(ema_tensors, model_tensors)):
+            if not ema_tensor_ok(e, m) or e.device != tables.device:
+                raise RuntimeError(f"ema_update: pair {i} must be two dense float32 tensors on {tables.device} of one shape and layout, got "
+                                   f"{tuple(e.shape)} {e.dtype} {e.device} and {tuple(m.shape)} {m.dtype} {m.device}")
+    key = tuple((e.data_ptr(), m.data_ptr(), e.numel()) for e, m in zip(ema_tensors, model_tensors))
+    if key != tables.key:
+        tables.build(key, ema_tensors, model_tensors)
+    if tables.n_work == 0:
+        return
+    launch("gdrnpp_model_ema_update", tables.table.data_ptr(), tables.n_tensors, tables.work.data_ptr(), tables.n_work,
+           float(np.float32(decay)), float(np.float32(one_minus_decay)), timed=("hbm:model_ema", 0.0, 12.0 * tables.numel))

@@ -1190,6 +1190,25 @@ typedef struct gdrnpp_ranger_long_row {
 int gdrnpp_ranger_step(const gdrnpp_ranger_tensor* tensors, int n_tensors, const gdrnpp_ranger_work* work, int n_work,
                        const gdrnpp_ranger_long_row* long_rows, int n_long_rows, float* long_means, void* stream);
 
+/* ---- ModelEMA update over every floating-point tensor of a model (csrc/model_ema.hip) — update() of det/yolox/utils/ema.py:50-60 and
+ * lib/torch_utils/torch_utils.py:247-258 ----
+ * One launch updates all (EMA tensor, model tensor) pairs.  Two DEVICE tables, built by the caller once per model; their records are
+ * plain little-endian words without padding (csrc/model_ema.hip asserts the layout, hip_lib/net.py builds it):
+ *   tensors    24 bytes per pair: float* ema at 0 (the EMA's f32 array, read and written), const float* model at 8 (the model's, read
+ *              only), long long numel at 16 (elements of each).
+ *   work       16 bytes per item: long long start at 0, int tensor at 8, int count at 12 — the tensors cut into pieces, one workgroup
+ *              each.  Pieces of 8192 elements (the kernel's tile, a multiple of 4) take its straight-line path; any count is correct.
+ * Per element, in fp32 with every product and the sum rounded on its own (no fused multiply-add):
+ *   ema = fadd(fmul(ema, decay), fmul(one_minus_decay, model))
+ * which is torch's `v *= d; v += (1.0 - d) * m` on fp32 tensors bit for bit when decay = (float)d and one_minus_decay = (float)(1.0 - d),
+ * the subtraction done in double.  The coefficients are arguments: they change with every update, the tables do not.
+ * 16-byte accesses where ema + start and model + start are both 16-byte aligned, dword accesses otherwise.
+ * The tables are not validated (they live on the device), but nothing outside an EMA tensor is written whatever they say: an item
+ * whose tensor index is outside [0, n_tensors) or whose start is outside [0, numel) is skipped, and its count is cut to the tensor's
+ * end.  n_work == 0 is a success without a launch. */
+int gdrnpp_model_ema_update(const void* tensors, int n_tensors, const void* work, int n_work, float decay, float one_minus_decay,
+                            void* stream);
+
 /* ---- YOLOX training (csrc/yolox_loss.hip) — get_losses / get_assignments / get_in_boxes_info / dynamic_k_matching of
  * det/yolox/models/yolo_head.py:256-627 and IOUloss of det/yolox/models/losses.py, for the whole batch with no host round trip ----
  * raw f32[B,A,5+C]: the head's undecoded rows (reg 4, objectness logit, C class logits), levels concatenated in level order, each
