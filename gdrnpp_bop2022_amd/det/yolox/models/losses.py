@@ -83,6 +83,8 @@ def decode_boxes(raw, anchors):
 @torch.no_grad()
 def simota_assign_torch(raw, anchors, labels):
     """SimOTA for the whole batch in torch operators, one [B,G,A] IoU and cost tensor, no [G,A,C] tensor and no per-image loop.
+    Exact ties go to the lowest index, as in csrc/yolox_loss.hip: equal costs of one gt to the lowest anchor (a stable sort;
+    ``topk`` promises no order among equal values), equal costs of one anchor to the lowest label row (``argmin`` returns the first).
     -> (matched_gt i32[B,A] with -1 = background, matched_iou [B,A], num_fg i32[B], num_gt i32[B])."""
     B, A, S = raw.shape
     C, G = S - 5, labels.shape[1]
@@ -124,7 +126,8 @@ def simota_assign_torch(raw, anchors, labels):
     top_iou = torch.where(use, iou, torch.zeros_like(iou)).topk(k, dim=2).values.sum(2)           # zeros pad an image with < 10 candidates
     dynamic_k = top_iou.int().clamp(min=1)
     cost = torch.where(use, cost, torch.full_like(cost, float("inf")))
-    low, low_idx = cost.topk(k, dim=2, largest=False)
+    low_idx = cost.argsort(dim=2, stable=True)[..., :k]                                           # equal costs: the lowest anchor first
+    low = cost.gather(2, low_idx)
     chosen = (torch.arange(k, device=dev) < dynamic_k[..., None]) & torch.isfinite(low)
     matching = torch.zeros((B, G, A), dtype=torch.bool, device=dev).scatter_(2, low_idx, chosen)
     n_chosen = matching.sum(1)

@@ -17,6 +17,10 @@ the assignment.  Asserted per case, stored as ``margin_<kind>`` and ``margin_min
   dynamic_k   sum of the top-10 IoUs against the integers 2 .. 11 (below 2 the clamp makes dynamic_k 1 either way)
   cost_k      k-th against (k+1)-th cost of every gt, in units of 1 + 1e-3 |cost| (penalised costs of 1e5 round to 8e-3 in fp32)
   conflict    the two lowest costs over all gts of every multiply-chosen anchor, same units
+The dense case (448 x 448, A = 4116: 16 - 17 anchors per lane of the assignment kernel's 256) takes its images from
+tests/yolox_loss_edge_cases.py::dense_image: large gts with good predictions scattered over the whole box.  Asserted of its crowded
+image, as ``lane_facts`` counts them: >= 128 lanes (anchor % 256) hold more than 10 candidates, >= 5 chosen anchors and >= 5 of the
+anchors that form some gt's 10 largest IoUs are the 11th or a later candidate of their lane's walk.
 ``e_cost`` is the largest distance, in the same units, of the fp32 restatement's candidate costs from fp64: MARGIN is 1e-3, and
 asserted to exceed 16 e_cost.
 
@@ -65,6 +69,7 @@ for name in ("det.yolox.utils", "det.yolox.utils.model_utils"):
     sys.modules[name].__path__ = []
 sys.modules["det.yolox.utils"].bboxes_iou = _boxes.bboxes_iou
 
+import yolox_loss_edge_cases as E  # noqa: E402
 import yolox_loss_ref as R  # noqa: E402
 from det.yolox.models.yolo_head import YOLOXHead  # noqa: E402
 
@@ -76,6 +81,8 @@ CASES = {
     "a_giou_focal_l1": dict(size=(64, 96), C=3, layout="a", G=7, opts=dict(iou_loss_type="giou", cls_loss_type="focal", use_l1=True)),
     "b_iou_bce_l1": dict(size=(160, 160), C=3, layout="b", G=8, opts=dict(iou_loss_type="iou", cls_loss_type="bce", use_l1=True)),
     "b21_giou_focal": dict(size=(160, 160), C=21, layout="b", G=8, opts=dict(iou_loss_type="giou", cls_loss_type="focal", use_l1=False)),
+    "dense_giou_focal_l1": dict(size=(E.DENSE_SIZE, E.DENSE_SIZE), C=E.DENSE_C, layout="dense", G=E.DENSE_G,
+                                opts=dict(iou_loss_type="giou", cls_loss_type="focal", use_l1=True)),
 }
 FL_ALPHA, FL_GAMMA = 0.25, 2.0
 
@@ -92,6 +99,9 @@ def build_inputs(case, seed):
     hw = [(H // s, W // s) for s in STRIDES]
     anchors = R.anchor_table(hw, STRIDES, torch.float32)
     A = anchors.shape[0]
+    if c["layout"] == "dense":                               # no gt, one gt, a crowd of seven with the twin pair
+        raw, labels = E.dense_batch(seed)
+        return hw, anchors, torch.from_numpy(raw.copy()), torch.from_numpy(labels.copy())
     rng = np.random.default_rng(seed)
 
     def rand_gt(scale_lo=0.2, scale_hi=0.5):
@@ -192,11 +202,16 @@ def main():
         for seed in range(200):
             hw, anchors, raw, labels = build_inputs(case, seed)
             margins, facts, e_cost, info64 = check_margins(anchors, raw, labels)
-            if min(margins.values()) > MARGIN and facts["conflicts"] > 0 and max(facts["dynamic_k"]) >= 3:
+            lanes = E.lane_facts(info64["per_image"][-1]) if c["layout"] == "dense" else None
+            if (min(margins.values()) > MARGIN > 16 * e_cost and facts["conflicts"] > 0 and max(facts["dynamic_k"]) >= 3
+                    and (lanes is None or (lanes["full_lanes"] >= 128 and min(lanes["late_chosen"], lanes["late_top_iou"]) >= 5))):
                 break
         else:
             raise AssertionError(f"{case}: no seed with every margin above {MARGIN}")
         assert min(margins.values()) > MARGIN > 16 * e_cost, (margins, e_cost)
+        if lanes is not None:
+            assert lanes["full_lanes"] >= 128 and lanes["late_chosen"] >= 5 and lanes["late_top_iou"] >= 5 and lanes["max_per_lane"] > E.TOPK, lanes
+            print(f"{case}: lanes of the crowded image {lanes}")
         losses, ratio, matched_gt, matched_iou, grad = run_reference(case, anchors, raw, labels)
         # the restatement in fp64: its assignment must be the reference's, and its distance from the reference's fp32 is e_ref
         leaf = raw.double().requires_grad_(True)

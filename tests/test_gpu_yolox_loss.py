@@ -11,7 +11,9 @@ corners carry <= 3 ulp of a coordinate <= 160 px (expf <= 2 ulp, one product, on
 wide, so the cancellation amplifies by <= 80: 256 ulp of 1 = 1.5e-5 bounds it.
 Measured on an MI355X (all four cases): every loss and every gradient element within 0.5 fp32 ulp of ref64 (the kernels form every
 term in fp64 and round once; largest loss distance 7.0e-7 at loss_conf = 23.4 against a bar of 3.3e-6, largest gradient distance
-1.4e-8 against e_ref 7e-8 .. 2.5e-7); max |matched_iou - ref64| = 4.5e-7, the reference's own fp32 distance to the digit."""
+1.4e-8 against e_ref 7e-8 .. 2.5e-7); max |matched_iou - ref64| = 4.5e-7, the reference's own fp32 distance to the digit.
+The dense case (448 x 448, A = 4116, every lane of match_kernel with more than 10 candidates): loss_conf = 161.25 at 7.2e-6 from ref64 against a
+bar of 3.1e-5, the other losses <= 3.3e-8, gradient 5.8e-9 (0.5 ulp), matched_iou 3.0e-7."""
 import os
 
 import numpy as np
@@ -27,7 +29,7 @@ from tests import yolox_loss_ref as R
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 HERE = os.path.dirname(os.path.abspath(__file__))
-CASES = ("a_iou_bce", "a_giou_focal_l1", "b_iou_bce_l1", "b21_giou_focal")
+CASES = ("a_iou_bce", "a_giou_focal_l1", "b_iou_bce_l1", "b21_giou_focal", "dense_giou_focal_l1")
 _CACHE = {}
 
 
